@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: 5-D Black-Scholes barycentric point-evals/sec on MI355X.
 
-Contract (driver):  python bench.py --gpus N --steps K --warmup W
+Contract (driver):  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps of the headline workload and prints ONE JSON line (`value`,
+  `ms_per_step`, the headline `roofline` from the same steps).  Everything else below that takes runs of its own
+  (the multi-rank `gather` legs, the companions, `midsize`, `c1`, `end_to_end`, `cpu_baseline`) runs only with --full.
+  --dump-outputs DIR writes the headline's last timed step as DIR/<workload>.npy (float64; rank 0: the collected
+  result of all ranks; above DUMP_LIMIT_BYTES a fixed seeded sample of rows, in their original order).
   No PyTorch anywhere: the C ABI (libpcx_hip.so) does the compute, the RCCL gather
   (pcx_comm_*) and the copies; ranks meet through pychebyshev_amd.distributed.HostGroup.
   N = 1   : one process.
@@ -23,13 +28,15 @@ N > 1 each timed step ends with the RCCL gather of the N result blocks on rank 0
 path's only exchange; it overlaps the next step's kernel).  The same K steps are timed
 again (a) without any gather, (b) with rank 0 downloading the gathered result, and (c) with
 every rank downloading its block straight into one pinned shared-memory host array (no
-collective) -- reported under "gather" beside the headline.
+collective) -- reported under "gather" beside the headline (--full only).
 
-Also on the JSON line:
+On the JSON line of every run:
   roofline     dominant kernel: algorithmic flop per launch / mean launch duration from
                HIP events on the launch stream, vs the FP64 MFMA peak; `traffic` is the
                HBM bytes per launch from the committed PMC profile (cached; see
                traffic_source), not collected in this run.
+
+Only with --full:
   end_to_end   the host-pointer entry point on the same batch (H2D + kernel + D2H) through the Python method (a fresh
                result array per call), with the PCIe GB/s; `preallocated`: the C-ABI call into result arrays the
                caller owns; `page_locked`: on caller arrays page-locked beforehand (pcx_host_register).
@@ -106,6 +113,24 @@ def uniform_points(domain, n, seed):
     """One rng.uniform(lo, hi, n) per dimension, stacked column-wise (the reference's recipe)."""
     rng = np.random.default_rng(seed)
     return np.column_stack([rng.uniform(lo, hi, n) for lo, hi in domain])
+
+
+DUMP_LIMIT_BYTES = 48 << 20       # --dump-outputs: larger results are written as a seeded sample of this many bytes of rows
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(directory, name, result, width):
+    """Write one result of the timed path as `directory`/`name`.npy in float64: rows of `width` values (a 1-D
+    array when width is 1).  Above DUMP_LIMIT_BYTES, the rows picked by default_rng(DUMP_SAMPLE_SEED) without
+    replacement, kept in their original order: the same rows for the same arguments in every run."""
+    rows = np.asarray(result, dtype=np.float64).reshape(-1, width)
+    keep = DUMP_LIMIT_BYTES // (8 * width)
+    if len(rows) > keep:
+        rows = rows[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(len(rows), keep, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, name + ".npy")
+    np.save(path, np.ascontiguousarray(rows[:, 0] if width == 1 else rows))
+    return path
 
 
 def usable_cores() -> int:
@@ -538,13 +563,14 @@ def run_rank(args) -> int:
         import zlib
         return float(zlib.crc32(np.ascontiguousarray(arr).view(np.uint8)))
 
-    def measure(wl, steps, warmup, mode):
+    def measure(wl, steps, warmup, mode, keep_result=False):
         """W untimed + K timed steps of one workload, batch resident in HBM beforehand.
         mode: "none" (kernel only), "rccl" (gather of all blocks on rank 0's GPU each step),
         "rccl+d2h" (... and rank 0 downloads the gathered result), "d2h" (every rank downloads
         its block into the shared pinned host array), "h2d+d2h" (every step ALSO uploads the rank's points from
         page-locked host memory first: the whole host-to-host path on every GPU at once).
-        Returns a dict; times are max over ranks."""
+        Returns a dict; times are max over ranks.  keep_result: rec["result"] on rank 0 = the last timed step's
+        result as a caller of the path receives it (the collected blocks of all ranks when there is a collection)."""
         n = wl.points_per_gpu
         n_out = n * wl.evals_per_point
         pts = np.ascontiguousarray(wl.points(rank))
@@ -660,6 +686,13 @@ def run_rank(args) -> int:
                     if bad or not np.isfinite(host).all():
                         raise SystemExit(f"shared host result: the blocks of ranks {bad} differ from what those ranks computed")
                 verified = world
+        result = None
+        if keep_result and rank == 0:
+            result = got
+            if group is not None and mode in ("rccl", "rccl+d2h"):
+                result = full
+            elif group is not None and shared is not None:
+                result = host
         pinned = shared.pinned if shared is not None else None
         if shared is not None:
             shared.close()
@@ -674,6 +707,8 @@ def run_rank(args) -> int:
                "avg_launch_ms_per_rank": group.gather_floats(avg_launch) if group is not None else [avg_launch],
                "side_ms": float(np.mean(gather_ms)) if gather_ms else None, "pinned": pinned,
                "blocks_verified": verified, "points_page_locked": pts_locked if upload else None}
+        if keep_result:
+            rec["result"] = result
         return rec
 
     def rate(wl, rec, steps):
@@ -908,8 +943,10 @@ def run_rank(args) -> int:
     if args.variant and hasattr(wl, "m"):
         chk(wl.m.lib.pcx_bary_set_kernel(wl.m.handle, args.variant))
     n = wl.points_per_gpu
-    head = measure(wl, args.steps, args.warmup, headline_mode)
-    gathers = gather_report(wl, args.steps, args.warmup, head) if multi else None
+    head = measure(wl, args.steps, args.warmup, headline_mode, keep_result=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl.key, head.pop("result"), wl.evals_per_point)
+    gathers = gather_report(wl, args.steps, args.warmup, head) if multi and args.full else None
 
     def midsize_companion():
         """Mid-size full tensors (VERDICT r3 #6 names 21^3, 30^3, 40^3, 65^3, 64^4): device-resident vectorized_eval_batch of
@@ -1061,10 +1098,10 @@ def run_rank(args) -> int:
             free_events()
 
     # the metric names both interpolants and BASELINE.json lists the Greeks run as a config:
-    # the default (barycentric) run also times config 3 (TT) and config 4 (Greeks) with the
+    # with --full the barycentric run also times config 3 (TT) and config 4 (Greeks) with the
     # same discipline and reports them beside the headline value, never mixed into it
     companions = {}
-    if args.workload == "bary5d" and not args.no_companion:
+    if args.full and args.workload == "bary5d" and not args.no_companion:
         for name, field in (("greeks5d", "greeks"), ("tt5d", "tt"), ("tt10d", "tt10d")):
             try:
                 got = companion(name)
@@ -1151,8 +1188,9 @@ def run_rank(args) -> int:
         line["roofline"]["avg_launch_ms_per_rank"] = head["avg_launch_ms_per_rank"]
         if wl.build_info:
             line["config"]["build"] = wl.build_info
-        if multi:
+        if gathers is not None:
             line["gather"] = gathers
+        if multi:
             buses = [r_.get("pci_bus_id") for r_ in ranks_on]
             line["comm"] = {"backend": "rccl" if comm is not None else None,
                             "rccl_version": comm.rccl_version if comm is not None else None,
@@ -1164,7 +1202,7 @@ def run_rank(args) -> int:
                             "ranks": ranks_on}
             line["config"]["blocks_verified"] = head.get("blocks_verified")
         line.update(companions)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         def guarded(what, fn):
             # reported legs: a failure here (say, no C compiler for the oracle on this box) must not cost the line
             try:
@@ -1203,15 +1241,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="bary5d", choices=["bary5d", "greeks5d", "tt5d", "tt10d"])
     ap.add_argument("--points", type=int, default=0, help="query points per GPU per step")
+    ap.add_argument("--full", action="store_true", default=os.environ.get("PCX_BENCH_FULL") == "1",
+                    help="after the headline, also run every leg that takes runs of its own: the multi-rank gather legs, "
+                         "the companions, end_to_end and cpu_baseline (default: off; PCX_BENCH_FULL=1 sets it)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the headline's last timed step as DIR/<workload>.npy (float64, at most %d MiB: larger "
+                         "results as a fixed seeded sample of rows)" % (DUMP_LIMIT_BYTES >> 20))
     ap.add_argument("--no-cpu-baseline", action="store_true",
-                    help="skip the CPU baseline and the host-pointer end_to_end legs")
+                    help="--full: skip the CPU baseline and the host-pointer end_to_end legs")
     ap.add_argument("--no-companion", action="store_true",
-                    help="bary5d only: skip the Greeks (config 4), TT (config 3) and 10-D TT (config 5) companions")
+                    help="--full, bary5d only: skip the Greeks (config 4), TT (config 3) and 10-D TT (config 5) companions")
     ap.add_argument("--gather", default="auto", choices=["auto", "none", "rccl", "rccl+d2h", "d2h"],
                     help="what each timed step of the headline does with the result blocks (N > 1)")
     ap.add_argument("--variant", type=int, default=0,
                     help="barycentric kernel: 0 auto, 1 rows, 2 MFMA 16x16x4, 3 MFMA 4x4x4_4b")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_children(args.gpus)
     return run_rank(args)

@@ -26,6 +26,7 @@ Sets:
   g16_auto_n       error_threshold builds: final n_nodes, evaluation counts, estimates, values
   g17_c_example    value + first partials of the 5-D .pcb fixture at one point (examples/pcb_eval.c)
   g14_spline_pcb   class-tag-2 .pcb: the reference's spline fixture and a 2-D spline file written by it
+  g18_ref_reader   the reference's C .pcb reader (examples/binary_reader there) at 12 points of the 5-D fixture
 """
 from __future__ import annotations
 
@@ -479,6 +480,18 @@ def main():
     g14["sp2_eval"] = sp2.eval_batch(p14, [0, 0])
     g14["sp2_dx"] = sp2.eval_batch(p14, [1, 0])
     save("g14_spline_pcb", **g14)
+
+    # ---------------------------------------------------------------- g18 (the reference's C reader)
+    # oracle/_ref/reader (make -C oracle ref: <ref>/examples/binary_reader/reader.c compiled where it lies) at the
+    # points of tests/test_oracle.py::test_against_compiled_reference_reader, its printed values as read back
+    import subprocess
+    subprocess.run(["make", "-C", os.path.join(HERE, "..", "..", "oracle"), "ref", f"REF={args.ref}"], check=True)
+    reader = os.path.join(HERE, "..", "..", "oracle", "_ref", "reader")
+    p18 = np.random.default_rng(11).uniform(-1, 1, (12, 5))
+    p18[0] = [0.1, -0.2, 0.3, 0.4, -0.5]
+    v18 = [float(subprocess.run([reader, os.path.join(HERE, "approx_5d_bs.pcb")] + [repr(float(v)) for v in p],
+                                check=True, capture_output=True, text=True).stdout) for p in p18]
+    save("g18_ref_reader", points=p18, out=np.array(v18))
 
     print(f"done in {time.time() - t0:.1f}s")
 

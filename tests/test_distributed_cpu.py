@@ -369,3 +369,20 @@ def test_bench_launcher_stops_the_other_ranks_when_one_fails(tmp_path, monkeypat
     rc = bench.launch_children(4, script=str(script), argv=[])
     assert rc == 7 and time.monotonic() - t0 < 60          # not the 120 s rendezvous timeout of the surviving ranks
     assert "rank 3 exited with code 7" in capfd.readouterr().err
+
+
+def test_bench_dump_outputs_writes_the_result_or_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: a result under the size limit is written whole in float64 (rows of `width` values);
+    above it, the same seeded rows in their original order on every call."""
+    bench = _load_bench()
+    x = np.arange(3000, dtype=np.float64)
+    bench.dump_outputs(str(tmp_path / "a"), "w1", x, 1)
+    bench.dump_outputs(str(tmp_path / "a"), "w3", x, 3)
+    assert np.array_equal(np.load(tmp_path / "a" / "w1.npy"), x)
+    assert np.array_equal(np.load(tmp_path / "a" / "w3.npy"), x.reshape(-1, 3))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8 * 3 * 100)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), "w3", x, 3)
+    b, c = np.load(tmp_path / "b" / "w3.npy"), np.load(tmp_path / "c" / "w3.npy")
+    assert b.shape == (100, 3) and b.dtype == np.float64 and np.array_equal(b, c)
+    assert np.all(np.diff(b[:, 0]) > 0) and np.array_equal(b[:, 1] - b[:, 0], np.ones(100))

@@ -11,7 +11,7 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import ROOT, GOLDEN
+from conftest import ROOT, GOLDEN, assert_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -94,9 +94,32 @@ def _bench(args, env_extra, timeout=600):
     return json.loads(lines[0])
 
 
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path, oracle_mod):
+    """A plain run does the headline only (no leg that takes runs of its own), `steps` is the number of timed steps,
+    and --dump-outputs writes the last timed step's values: the oracle's on the same seeded points, and the same
+    values for the same arguments in a second run."""
+    args = ["--gpus", "1", "--steps", "4", "--warmup", "1", "--points", "200000", "--dump-outputs"]
+    line = _bench(args + [str(tmp_path / "a")], {})
+    assert line["steps"] == 4 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["value"] == pytest.approx(200000 * 4 / (line["ms_per_step"] * 4 / 1e3), rel=1e-9)
+    for key in ("gather", "greeks", "tt", "tt10d", "midsize", "c1", "end_to_end", "cpu_baseline"):
+        assert key not in line
+    got = np.load(tmp_path / "a" / "bary5d.npy")
+    assert got.shape == (200000,) and got.dtype == np.float64 and np.isfinite(got).all()
+    import bench
+    from pychebyshev_amd import ChebyshevApproximation
+    info = ChebyshevApproximation.nodes(5, bench.BS5_DOMAIN, bench.BS5_NODES)
+    tensor = np.array([bench.bs_5d(list(p)) for p in info["full_grid"]]).reshape(info["shape"])
+    om = oracle_mod.BaryModel.from_domain(bench.BS5_DOMAIN, bench.BS5_NODES, tensor)
+    pts = bench.uniform_points(bench.BS5_DOMAIN, 200000, 99)[:4096]
+    assert_parity(got[:4096], oracle_mod.bary_eval_batch(om, pts, [0] * 5), 1e-12, "bench dump vs oracle")
+    _bench(args + [str(tmp_path / "b")], {})
+    assert np.array_equal(np.load(tmp_path / "b" / "bary5d.npy"), got)
+
+
 def test_bench_single_rank_with_rccl_forced():
     """--gpus 1 with the communicator forced on: every step ends with the RCCL gather."""
-    line = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--points", "200000", "--no-companion",
+    line = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--points", "200000", "--full", "--no-companion",
                    "--no-cpu-baseline"], {"PCX_BENCH_FORCE_COMM": "1"})
     assert line["n_gpus"] == 1 and line["config"]["gather"] == "rccl"
     assert line["comm"]["backend"] == "rccl" and line["comm"]["torch"] is False
@@ -118,7 +141,7 @@ def test_bench_single_rank_with_rccl_forced():
 def test_bench_goes_on_when_the_rccl_bootstrap_misses_its_deadline():
     """A communicator that is not there in time (deadline 0 here) must not hang the bench: the step falls
     back to the host-memory gather and the line says why."""
-    line = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--points", "200000", "--no-companion",
+    line = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--points", "200000", "--full", "--no-companion",
                    "--no-cpu-baseline"], {"PCX_BENCH_FORCE_COMM": "1", "PCX_BENCH_RCCL_TIMEOUT": "0"})
     assert line["config"]["gather"] == "d2h" and line["comm"]["backend"] is None
     assert "did not finish" in line["comm"]["rccl_error"]
@@ -127,7 +150,7 @@ def test_bench_goes_on_when_the_rccl_bootstrap_misses_its_deadline():
 
 def test_bench_launches_two_ranks_itself():
     """Plain `python bench.py --gpus 2`: the script starts the ranks (both on GPU 0 here)."""
-    line = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--points", "200000", "--no-companion"],
+    line = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--points", "200000", "--full", "--no-companion"],
                   {"PCX_BENCH_SHARE_DEVICE": "1"})
     assert line["n_gpus"] == 2 and line["config"]["gather"] == "d2h"
     assert line["comm"]["backend"] is None and "duplicate" in line["comm"]["rccl_error"]
@@ -155,7 +178,7 @@ def test_bench_under_the_driver_launcher():
         env.pop(k, None)
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                           "--master-addr", "127.0.0.1", "--master-port", port, os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--steps", "3", "--warmup", "1", "--points", "200000", "--no-companion"],
+                          "--gpus", "2", "--steps", "3", "--warmup", "1", "--points", "200000", "--full", "--no-companion"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

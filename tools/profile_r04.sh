@@ -26,6 +26,8 @@ for k, v in table.items():
 json.dump(keep, open(old, "w"), indent=1)
 json.dump(keep, open(os.path.join(root, "gpurun_out", "r04", "pmc_traffic.json"), "w"), indent=1)
 PY
+# the bench lines below are full runs (bench.py --full): the checker reads the companions, the multi-rank lines the gather legs
+export PCX_BENCH_FULL=1
 python3 bench.py > gpurun_out/r04/bench_bary5d.json 2> gpurun_out/r04/bench_bary5d.err || echo "bench failed"
 for wl in bary5d greeks5d tt5d tt10d; do cp gpurun_out/prof_$wl/r04_${wl}_summary.json profiles/ 2>/dev/null; done
 cp gpurun_out/r04/bench_bary5d.json profiles/r04_bench_bary5d.json
