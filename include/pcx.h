@@ -146,6 +146,18 @@ int pcx_bary_eval_multi_batch_dev(pcx_bary *h, const double *d_pts, int64_t N,
  * the host (prod n_d doubles) -- lets tests check kernel K3 on its own.               */
 int pcx_bary_derivative_tensor(pcx_bary *h, const int32_t *deriv, double *tensor_out);
 
+/* Chebyshev coefficient tensor of the handle's values (reference _sensitivity.py:14-49: per
+ * dimension reverse, DCT-II, / n, halve c_0), C order, prod n_d doubles: d mode products
+ * on the device.                                                                        */
+int pcx_bary_chebyshev_coefficients(pcx_bary *h, double *coeffs_out);
+
+/* First- and total-order Sobol indices and the variance of the handle's interpolant
+ * (reference _sensitivity.py:67-140), including its rules: d = 1 -> both indices 1.0 when
+ * variance > 0; variance == 0 -> all indices 0.0; any non-finite coefficient ->
+ * PCX_ERR_INVALID with "coefficients contain NaN or Inf" in pcx_last_error().
+ * first_out and total_out hold d doubles each.                                           */
+int pcx_bary_sobol(pcx_bary *h, double *variance_out, double *first_out, double *total_out);
+
 /* Contract axis `axis` of a C-order tensor (d dims, n_nodes) with `vec` (n_nodes[axis]
  * doubles): out has the remaining d-1 dims.  The device half of
  * ChebyshevApproximation.slice (barycentric.py:2064-2154, _extrude_slice.py:79-92).   */

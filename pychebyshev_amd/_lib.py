@@ -80,6 +80,8 @@ SIGNATURES = {
     "pcx_bary_eval_multi_batch_dev": (_I, [_V, _V, _L, c_i32p, _I, _V, _V]),
     "pcx_bary_group_eval_multi_batch": (_I, [c_vpp, _I, c_f64p, _L, c_i32p, _I, c_f64p, _I]),
     "pcx_bary_derivative_tensor": (_I, [_V, c_i32p, c_f64p]),
+    "pcx_bary_chebyshev_coefficients": (_I, [_V, c_f64p]),
+    "pcx_bary_sobol": (_I, [_V, c_f64p, c_f64p, c_f64p]),
     "pcx_tensor_contract_axis": (_I, [_I, _I, c_i32p, c_f64p, _I, c_f64p, c_f64p]),
     "pcx_bary_set_kernel": (_I, [_V, _I]),
     "pcx_bary_set_group_span": (_I, [_V, _I]),

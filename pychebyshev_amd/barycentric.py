@@ -17,8 +17,8 @@ as the reference builds it, and copied to the device when the first evaluation h
 
 ``special_points`` with knots dispatch to :class:`pychebyshev_amd.spline.ChebyshevSpline` as in
 the reference.  ``error_threshold`` (auto-N) builds, ``error_estimate``, ``slice`` and
-``integrate`` run their tensor contractions on the device.  Not provided: algebra, roots /
-optimisation, extrude, Sobol indices, plotting.
+``integrate`` run their tensor contractions on the device, and so do the coefficient transform and
+energy reduction of ``sobol_indices``.  Not provided: algebra, roots / optimisation, extrude, plotting.
 """
 from __future__ import annotations
 
@@ -887,6 +887,34 @@ class ChebyshevApproximation(ErgonomicsMixin, DerivativeIdMixin):
         if self._cached_error_estimate is None:
             self._cached_error_estimate = float(sum(self._error_estimate_per_dim()))
         return self._cached_error_estimate
+
+    # ---------------------------------------------------------------- sensitivity
+    def _chebyshev_coefficients(self) -> np.ndarray:
+        """Chebyshev coefficient tensor of the interpolant (reference ``_compute_chebyshev_coefficients``,
+        _sensitivity.py:14-49), computed on the device as d mode products (``pcx_bary_chebyshev_coefficients``)."""
+        if self.tensor_values is None:
+            raise RuntimeError("Call build() first")
+        m = self._model()
+        out = np.empty(tuple(int(v) for v in self.n_nodes))
+        _lib.check(m.lib.pcx_bary_chebyshev_coefficients(m.handle, _lib.p_f64(out)), m.lib)
+        return out
+
+    def sobol_indices(self) -> dict:
+        """First- and total-order Sobol sensitivity indices from the Chebyshev spectral expansion
+        (reference barycentric.py:1341-1371, _sensitivity.py:67-140): ``{"first_order": {dim: index},
+        "total_order": {dim: index}, "variance": float}``.  The coefficient transform and the energy
+        reduction run on the device (``pcx_bary_sobol``); a non-finite coefficient raises ``ValueError``."""
+        if self.tensor_values is None:
+            raise RuntimeError("Call build() first")
+        m = self._model()
+        d = self.num_dimensions
+        var = ctypes.c_double(0.0)
+        first = np.empty(d)
+        total = np.empty(d)
+        _lib.check(m.lib.pcx_bary_sobol(m.handle, ctypes.byref(var), _lib.p_f64(first), _lib.p_f64(total)), m.lib)
+        return {"first_order": {k: float(first[k]) for k in range(d)},
+                "total_order": {k: float(total[k]) for k in range(d)},
+                "variance": float(var.value)}
 
     def fast_eval(self, point, derivative_order=None, *, derivative_id=None) -> float:
         """Deprecated alias kept for drop-in compatibility (reference :789-869): same value as

@@ -6,6 +6,7 @@
 #include "pcx_bary_internal.h"
 #include "bary_kernels.h"
 #include "gather_kernels.h"
+#include "sobol_kernels.h"
 
 // ---------------------------------------------------------------------------------
 // barycentric handle
@@ -85,6 +86,8 @@ extern "C" int pcx_bary_destroy(pcx_bary *h) {
     h->s_partial.release();
     h->pin.release();
     (void)hipFree(h->d_nodes); (void)hipFree(h->d_wts); (void)hipFree(h->d_diff);
+    (void)hipFree(h->d_cheb);
+    h->s_cheb[0].release(); h->s_cheb[1].release(); h->s_sobol.release();
     (void)hipFree(h->d_snodes);
     (void)hipFree(h->d_gsnodes);
     (void)hipFree(h->d_rowcode); (void)hipFree(h->d_kcode);
@@ -1556,6 +1559,140 @@ extern "C" int pcx_bary_derivative_tensor(pcx_bary *h, const int32_t *deriv, dou
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(tensor_out, dt->plain, h->total * sizeof(double), hipMemcpyDeviceToHost));
+    return PCX_OK;
+    PCX_API_END
+}
+
+// ---------------------------------------------------------------------------------
+// Chebyshev coefficients and Sobol indices (reference _sensitivity.py)
+// ---------------------------------------------------------------------------------
+// Per dimension the reference reverses the values, applies a DCT-II, divides by n and halves c_0 (_sensitivity.py:14-49):
+// M[m, i] = (2 / n) cos(pi m (2 (n-1-i) + 1) / (2n)), row 0 halved.  The angle is reduced to [0, 2 pi) in integers
+// first, so every entry is a correctly reduced cosine whatever n.  Uploaded once per handle, laid out like d_diff.
+static int bary_cheb_matrices(pcx_bary *h) {
+    if (h->d_cheb) return PCX_OK;
+    const int d = h->dims.d;
+    std::vector<double> M((size_t)h->doff[d - 1] + (size_t)h->dims.n[d - 1] * h->dims.n[d - 1]);
+    for (int k = 0; k < d; ++k) {
+        const long n = h->dims.n[k];
+        double *Mk = M.data() + h->doff[k];
+        for (long m = 0; m < n; ++m)
+            for (long i = 0; i < n; ++i) {
+                const long p = (m * (2 * (n - 1 - i) + 1)) % (4 * n);      // angle = pi p / (2n)
+                Mk[m * n + i] = (2.0 / (double)n) * std::cos(M_PI * (double)p / (2.0 * (double)n)) * (m == 0 ? 0.5 : 1.0);
+            }
+    }
+    DevBuf b;
+    int rc = b.alloc(M.size() * sizeof(double));
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(b.p, M.data(), M.size() * sizeof(double), hipMemcpyHostToDevice));
+    h->d_cheb = b.release<double>();
+    return PCX_OK;
+}
+
+// The coefficient tensor of the handle's values: d k_mode_product passes (dimension 0 first) ping-ponging between the
+// handle's two coefficient scratch buffers; *coeffs points into one of them.  Everything is allocated before the first
+// launch.  Caller holds h->mu.  Work is enqueued on h->stream.
+static int bary_cheb_coeffs(pcx_bary *h, const double **coeffs) {
+    int rc = bary_cheb_matrices(h);
+    if (rc) return rc;
+    DerivedTensor *base = nullptr;
+    if ((rc = bary_get_tensor(h, nullptr, &base))) return rc;
+    for (Scratch &sc : h->s_cheb)
+        if ((rc = sc.reserve((size_t)h->total * sizeof(double)))) return rc;
+    const int d = h->dims.d;
+    const double *src = base->plain;
+    double *dst = (double *)h->s_cheb[0].ptr, *other = (double *)h->s_cheb[1].ptr;
+    const int blocks = (int)((h->total + 255) / 256);
+    for (int k = 0; k < d; ++k) {
+        long outer = 1, inner = 1;
+        for (int q = 0; q < k; ++q) outer *= h->dims.n[q];
+        for (int q = k + 1; q < d; ++q) inner *= h->dims.n[q];
+        hipLaunchKernelGGL(k_mode_product, dim3(blocks), dim3(256), 0, h->stream, src, dst, h->d_cheb + h->doff[k], outer,
+                           h->dims.n[k], inner);
+        src = dst;
+        std::swap(dst, other);
+    }
+    HIP_TRY(hipGetLastError());
+    *coeffs = src;
+    return PCX_OK;
+}
+
+extern "C" int pcx_bary_chebyshev_coefficients(pcx_bary *h, double *coeffs_out) {
+    PCX_API_BEGIN
+    if (!h || !coeffs_out) return fail(PCX_ERR_INVALID, "NULL argument");
+    HIP_TRY(hipSetDevice(h->device));
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->call_mark = h->clock;
+    const double *coeffs = nullptr;
+    int rc = bary_cheb_coeffs(h, &coeffs);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(coeffs_out, coeffs, (size_t)h->total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return PCX_OK;
+    PCX_API_END
+}
+
+extern "C" int pcx_bary_sobol(pcx_bary *h, double *variance_out, double *first_out, double *total_out) {
+    PCX_API_BEGIN
+    if (!h || !variance_out || !first_out || !total_out) return fail(PCX_ERR_INVALID, "NULL argument");
+    HIP_TRY(hipSetDevice(h->device));
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->call_mark = h->clock;
+    const int d = h->dims.d;
+    SobolDims sd{};
+    sd.L = h->dims.n[d - 1];
+    sd.rows = h->total / sd.L;
+    int W = 1;
+    while (W < 64 && W < sd.L) W <<= 1;
+    for (sd.lw = 0; (1 << sd.lw) < W; ++sd.lw) {}
+    for (int k = 0; k < PCX_MAX_DIMS; ++k) sd.n[k] = k < d ? (unsigned)h->dims.n[k] : 1u;
+    sd.pid = 1.0;
+    for (int k = 0; k < d; ++k) sd.pid *= M_PI;
+    const long per_block = (long)(PCX_SOBOL_THREADS / 64) * (64 / W) * PCX_SOBOL_UNROLL;     // rows per block pass
+    const int blocks = (int)std::min<long>(PCX_SOBOL_MAX_BLOCKS, (sd.rows + per_block - 1) / per_block);
+    const int S = PCX_SOBOL_SLOTS(d);
+    int rc = h->s_sobol.reserve(((size_t)blocks + 1) * S * sizeof(double));     // slab rows, then the result row
+    if (rc) return rc;
+    double *slab = (double *)h->s_sobol.ptr, *res = slab + (size_t)blocks * S;
+    const double *coeffs = nullptr;
+    if ((rc = bary_cheb_coeffs(h, &coeffs))) return rc;
+    const bool narrow = sd.rows <= 0xffffffffL;
+    switch (d) {
+#define CASE_D(v)                                                                                                        \
+    case v:                                                                                                              \
+        if (narrow) hipLaunchKernelGGL((k_sobol_energy<v, unsigned>), dim3(blocks), dim3(PCX_SOBOL_THREADS), 0, h->stream, \
+                                       coeffs, slab, sd);                                                   \
+        else hipLaunchKernelGGL((k_sobol_energy<v, unsigned long long>), dim3(blocks), dim3(PCX_SOBOL_THREADS), 0,       \
+                                h->stream, coeffs, slab, sd);                                               \
+        break;
+        CASE_D(1) CASE_D(2) CASE_D(3) CASE_D(4) CASE_D(5) CASE_D(6) CASE_D(7) CASE_D(8)
+        CASE_D(9) CASE_D(10) CASE_D(11) CASE_D(12) CASE_D(13) CASE_D(14) CASE_D(15) CASE_D(16)
+#undef CASE_D
+        default: return fail(PCX_ERR_INVALID, "d=%d outside [1, %d]", d, PCX_MAX_DIMS);
+    }
+    hipLaunchKernelGGL(k_sobol_finish, dim3(1), dim3(PCX_SOBOL_FINISH_THREADS), 0, h->stream,
+                       (const double *)slab, blocks, S, res);
+    HIP_TRY(hipGetLastError());
+    double r[PCX_SOBOL_SLOTS(PCX_MAX_DIMS)];
+    HIP_TRY(hipMemcpyAsync(r, res, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (r[S - 1] != 0.0)
+        return fail(PCX_ERR_INVALID, "coefficients contain NaN or Inf; sobol_indices() requires finite spectral coefficients");
+    // the reference's rules (_sensitivity.py:87-140): one dimension -> 1.0 / 1.0 when there is any variance;
+    // no variance -> every index 0.0
+    const double var = r[0];
+    for (int k = 0; k < d; ++k) {
+        if (d == 1) {
+            first_out[k] = total_out[k] = var > 0.0 ? 1.0 : 0.0;
+        } else if (var == 0.0) {
+            first_out[k] = total_out[k] = 0.0;
+        } else {
+            first_out[k] = r[1 + k] / var;
+            total_out[k] = r[1 + d + k] / var;
+        }
+    }
+    *variance_out = var;
     return PCX_OK;
     PCX_API_END
 }

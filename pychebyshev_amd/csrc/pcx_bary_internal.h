@@ -38,6 +38,9 @@ struct pcx_bary {
     long total = 0;
     std::vector<int> doff;           // offsets of D_k in diff_cat
     double *d_nodes = nullptr, *d_wts = nullptr, *d_diff = nullptr;
+    double *d_cheb = nullptr;        // values -> Chebyshev coefficients matrix per dimension, at doff[k] (pcx_bary_sobol; lazy)
+    Scratch s_cheb[2];               // the coefficient passes ping-pong between these (prod n doubles each, kept after first use)
+    Scratch s_sobol;                 // k_sobol_energy's slab + k_sobol_finish's result
     // launch plan
     bool mfma_ok = false;
     BaryMfmaPlan plan;

@@ -15,7 +15,8 @@ launches all run on the device (``pcx_spline_eval_batch``: ``k_spline_piece_id``
 ``k_spline_scatter`` -> one ``k_bary_mfma`` launch per non-empty piece on its bucket).
 
 Auto-N pieces (``error_threshold``) build through the pieces' own doubling loop; ``.pcb`` files
-(class tag 2) are read and written byte-compatibly.  Not provided: algebra, calculus,
+(class tag 2) are read and written byte-compatibly.  ``sobol_indices`` aggregates the pieces' device-side indices
+on the host as the reference does.  Not provided: algebra, calculus,
 extrude/slice, auto_knots.
 """
 from __future__ import annotations
@@ -427,6 +428,27 @@ class ChebyshevSpline(ErgonomicsMixin, DerivativeIdMixin):
         ids = np.zeros(pts.shape[0], dtype=np.int32)
         _lib.check(s.lib.pcx_spline_piece_ids(s.handle, _lib.p_f64(pts), pts.shape[0], _lib.p_i32(ids)), s.lib)
         return ids
+
+    # ---------------------------------------------------------------- sensitivity
+    def sobol_indices(self) -> dict:
+        """Sobol indices of the piecewise interpolant (reference spline.py:735-800): each piece's variance and
+        indices come from the device (``pcx_bary_sobol`` on its handle); a piece weighs ``volume * variance``, so
+        the spline's variance is the sum of the weights and each index the weight-averaged piece index."""
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        d = self.num_dimensions
+        results = [(float(np.prod([hi - lo for lo, hi in p.domain])), p.sobol_indices())
+                   for p in self._pieces if p is not None]
+        weight = np.array([vol * res["variance"] for vol, res in results])
+        variance = float(weight.sum()) if results else 0.0
+        if variance == 0:
+            return {"first_order": {k: 0.0 for k in range(d)}, "total_order": {k: 0.0 for k in range(d)},
+                    "variance": 0.0}
+        out = {"variance": variance}
+        for key in ("first_order", "total_order"):
+            idx = np.array([[res[key][k] for k in range(d)] for _, res in results])
+            out[key] = {k: float(v) for k, v in enumerate(weight @ idx / variance)}
+        return {"first_order": out["first_order"], "total_order": out["total_order"], "variance": variance}
 
     # ---------------------------------------------------------------- properties
     @property

@@ -16,8 +16,10 @@ DCT -- runs on the device (``pcx_tt_cross_step``, ``pcx_tt_grid_eval``,
 ``pcx_tt_value_to_coeff_core``).  Evaluation (single, batch, finite-difference stencils)
 is always a ``pcx_tt_eval_batch`` launch; there is no CPU fallback.
 
+``sobol_indices`` contracts the coefficient cores on the host (NumPy, O(d n r^2): no hot path).
+
 Out of scope in this tier (raise ``NotImplementedError``): ``method='als'``
-builders, algebra, calculus, slicing, reordering, Sobol indices.
+builders, algebra, calculus, slicing, reordering.
 """
 from __future__ import annotations
 
@@ -97,6 +99,59 @@ def _tt_grid_values(cores: Sequence[np.ndarray], idx: np.ndarray) -> np.ndarray:
     _lib.check(lib.pcx_tt_grid_eval(_device(), d, _lib.p_i32(n), _lib.p_i32(ranks), _lib.p_f64(cat),
                                     _lib.p_i32(ii), ii.shape[0], _lib.p_f64(out)), lib)
     return out
+
+
+def _sobol_from_coeff_cores(cores: Sequence[np.ndarray]):
+    """Variance, first- and total-order Sobol indices of a TT in Chebyshev coefficient space, as arrays by
+    storage position (the reference's TT sensitivity, _sensitivity.py:143-270, restated).
+
+    Under the Chebyshev measure a coefficient c_a carries the energy c_a^2 prod_k g(a_k), g(0) = pi and
+    g(m > 0) = pi / 2.  With G_k[i, j] the Gram chains of the cores weighted by g (``gram[k]`` covers the
+    dimensions before k, ``tail[k]`` those from k on), the total energy is gram[d], the variance is that minus the
+    constant term's share c_0^2 pi^d, the part of it with a_j = 0 is gram[j] (x) pi C_j0 (x) C_j0 (x) tail[j+1],
+    and the first-order part of dimension j is the squared line of coefficients c(0, .., m, .., 0), m >= 1, times
+    pi^(d-1) pi / 2.  Cost O(d n r^2)."""
+    d = len(cores)
+    g = []
+    for c in cores:
+        gk = np.full(c.shape[1], np.pi / 2.0)
+        gk[0] = np.pi
+        g.append(gk)
+
+    def step_left(M, A, w):        # sum_p w[p] A[:, p, :]^T M A[:, p, :]
+        return np.einsum("ipa,ipb->ab", np.einsum("ij,jpb->ipb", M, A), A * w[None, :, None])
+
+    def step_right(M, A, w):       # sum_p w[p] A[:, p, :] M A[:, p, :]^T
+        return np.einsum("ipa,jpa->ij", np.einsum("ipb,ab->ipa", A, M), A * w[None, :, None])
+
+    gram = [np.ones((1, 1))]
+    for A, w in zip(cores, g):
+        gram.append(step_left(gram[-1], A, w))
+    tail = [np.ones((1, 1))]
+    for A, w in zip(reversed(cores), reversed(g)):
+        tail.append(step_right(tail[-1], A, w))
+    tail.reverse()                 # tail[k]: dimensions k .. d-1, tail[d] = 1
+
+    # degree-0 chains: lo[k] = C_00 ... C_(k-1)0 (a row), hi[k] = C_k0 ... C_(d-1)0 (a column)
+    lo = [np.ones(1)]
+    for A in cores:
+        lo.append(lo[-1] @ A[:, 0, :])
+    hi = [np.ones(1)]
+    for A in reversed(cores):
+        hi.append(A[:, 0, :] @ hi[-1])
+    hi.reverse()
+
+    energy = float(gram[d][0, 0])
+    variance = energy - float(lo[d][0]) ** 2 * np.pi ** d
+    if variance <= 0:
+        return np.zeros(d), np.zeros(d), float(max(variance, 0.0))
+    first, total = np.empty(d), np.empty(d)
+    for j, A in enumerate(cores):
+        line = np.einsum("i,ima,a->m", lo[j], A[:, 1:, :], hi[j + 1])
+        first[j] = float(line @ line) * ((np.pi / 2.0) * np.pi ** (d - 1))
+        A0 = A[:, 0, :]
+        total[j] = energy - np.pi * float(np.sum((gram[j] @ A0) * (A0 @ tail[j + 1])))
+    return first / variance, total / variance, float(variance)
 
 
 def _tt_svd_from_tensor(tensor: np.ndarray, max_rank: int, tol: float) -> List[np.ndarray]:
@@ -831,6 +886,19 @@ class ChebyshevTT(ErgonomicsMixin):
             raise ValueError(f"domain and n_nodes must have length {num_dimensions}")
         return {"nodes_per_dim": [chebyshev_nodes(domain[k][0], domain[k][1], n_nodes[k])
                                   for k in range(num_dimensions)]}
+
+    def sobol_indices(self) -> dict:
+        """First- and total-order Sobol indices by contracting the coefficient cores (reference
+        tensor_train.py:2823-2870): ``{"first_order": {dim: index}, "total_order": {dim: index},
+        "variance": float}``, keyed by the user's dimensions through ``dim_order``.  Host NumPy, cost
+        O(d n r^2): the cores are small and there is no dense tensor."""
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        first, total, variance = _sobol_from_coeff_cores(self._coeff_cores)
+        user = self._dim_order                  # storage position s holds user dimension user[s]
+        return {"first_order": {user[s]: float(first[s]) for s in range(self.num_dimensions)},
+                "total_order": {user[s]: float(total[s]) for s in range(self.num_dimensions)},
+                "variance": variance}
 
     def error_estimate(self) -> float:
         """Sum over dimensions of the largest last Chebyshev coefficient (reference :2469-2504)."""
