@@ -289,6 +289,29 @@ int pcx_tt_stream(pcx_tt *h, void **stream);
  * Models with a rank above 64 always run on a generic wave-per-point kernel.            */
 int pcx_tt_set_kernel(pcx_tt *h, int variant);
 
+/* ---- roots, minimum and maximum along one dimension -------------------------- */
+/* The device half of roots() / minimize() / maximize() (reference _calculus.py:198-297) over a batch of N fibres of
+ * n <= 64 nodes (PCX_ERR_INVALID above): mode 0 roots, 1 minimize, 2 maximize.  All pointers are host pointers.
+ * roots_out: N x max(n-1, 1), ascending within a row, NaN-padded (mode 0); val_out / loc_out: N (modes 1, 2);
+ * counts_out: N always, the roots (mode 0) or critical points (modes 1, 2) found, -1 where the colleague matrix was
+ * not finite or its QR iteration did not converge (that row's roots / value / location are NaN).
+ * pcx_cheb1d_calculus solves given fibres: values N x n at the ascending nodes of [lo, hi], barycentric weights,
+ * and the n x n row-major differentiation matrix diff (modes 1, 2; may be NULL for mode 0).                        */
+int pcx_cheb1d_calculus(int device, int n, double lo, double hi, const double *nodes, const double *weights,
+                        const double *diff, const double *values, int64_t N, int mode, double *roots_out,
+                        int32_t *counts_out, double *val_out, double *loc_out);
+/* The fibres of a handle along dimension `dim`: row r of `fixed` (N x (d-1)) holds the values of the other
+ * dimensions in increasing order; every value must lie in its dimension's domain (lo / hi: d doubles each, the
+ * handle's domain), else PCX_ERR_INVALID before any launch.  The fibres are the handle's values at its own nodes of
+ * `dim` and never leave the device.                                                                                */
+int pcx_bary_calculus_batch(pcx_bary *h, int dim, const double *lo, const double *hi, const double *fixed, int64_t N,
+                            int mode, double *roots_out, int32_t *counts_out, double *val_out, double *loc_out);
+/* The same for a tensor train: `dim` and the columns of `fixed` are in the user's frame (dim_order applied on the
+ * device), the domain is the handle's own; the fibre's nodes, weights and differentiation matrix are built as
+ * chebyshev_nodes / compute_barycentric_weights / compute_differentiation_matrix build them.                      */
+int pcx_tt_calculus_batch(pcx_tt *h, int dim, const double *fixed, int64_t N, int mode, double *roots_out,
+                          int32_t *counts_out, double *val_out, double *loc_out);
+
 /* ---- TT-Cross build steps (tensor_train.py:123-540) ------------------------- */
 /* One unfolding step of _tt_cross (:332-362 and :449-474): thin SVD of the m x c cross
  * matrix C (row-major), rank = max(1, min(cap, #{S > rel_thresh*S0}, min(m,c))), maxvol

@@ -82,6 +82,9 @@ SIGNATURES = {
     "pcx_bary_derivative_tensor": (_I, [_V, c_i32p, c_f64p]),
     "pcx_bary_chebyshev_coefficients": (_I, [_V, c_f64p]),
     "pcx_bary_sobol": (_I, [_V, c_f64p, c_f64p, c_f64p]),
+    "pcx_cheb1d_calculus": (_I, [_I, _I, _D, _D, c_f64p, c_f64p, c_f64p, c_f64p, _L, _I, c_f64p, c_i32p, c_f64p, c_f64p]),
+    "pcx_bary_calculus_batch": (_I, [_V, _I, c_f64p, c_f64p, c_f64p, _L, _I, c_f64p, c_i32p, c_f64p, c_f64p]),
+    "pcx_tt_calculus_batch": (_I, [_V, _I, c_f64p, _L, _I, c_f64p, c_i32p, c_f64p, c_f64p]),
     "pcx_tensor_contract_axis": (_I, [_I, _I, c_i32p, c_f64p, _I, c_f64p, c_f64p]),
     "pcx_bary_set_kernel": (_I, [_V, _I]),
     "pcx_bary_set_group_span": (_I, [_V, _I]),

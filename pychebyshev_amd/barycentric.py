@@ -18,7 +18,8 @@ as the reference builds it, and copied to the device when the first evaluation h
 ``special_points`` with knots dispatch to :class:`pychebyshev_amd.spline.ChebyshevSpline` as in
 the reference.  ``error_threshold`` (auto-N) builds, ``error_estimate``, ``slice`` and
 ``integrate`` run their tensor contractions on the device, and so do the coefficient transform and
-energy reduction of ``sobol_indices``.  Not provided: algebra, roots / optimisation, extrude, plotting.
+energy reduction of ``sobol_indices``.  ``roots`` / ``minimize`` / ``maximize`` and their batched forms solve every
+fibre on the device (``pcx_bary_calculus_batch``).  Not provided: algebra, extrude, plotting.
 """
 from __future__ import annotations
 
@@ -915,6 +916,77 @@ class ChebyshevApproximation(ErgonomicsMixin, DerivativeIdMixin):
         return {"first_order": {k: float(first[k]) for k in range(d)},
                 "total_order": {k: float(total[k]) for k in range(d)},
                 "variance": float(var.value)}
+
+    # ---------------------------------------------------------------- calculus
+    def _calculus_batch(self, dim: int, rows: np.ndarray, mode: int):
+        """``pcx_bary_calculus_batch`` over validated rows (see :func:`pychebyshev_amd._calculus.run_batch`)."""
+        from . import _calculus
+        m = self._model()
+        lo = _lib.f64([float(b[0]) for b in self.domain])
+        hi = _lib.f64([float(b[1]) for b in self.domain])
+        rows = _lib.f64(rows)
+        N = rows.shape[0]
+
+        def call(r, c, v, loc):
+            return m.lib.pcx_bary_calculus_batch(m.handle, int(dim), _lib.p_f64(lo), _lib.p_f64(hi), _lib.p_f64(rows), N,
+                                                 mode, r, c, v, loc)
+        return _calculus.run_batch(call, m.lib, int(self.n_nodes[dim]), N, mode)
+
+    def _calculus(self, dim, fixed, mode: str):
+        from . import _calculus
+        if self.tensor_values is None:
+            raise RuntimeError("Call build() first")
+        d = self.num_dimensions
+        dim, params = _calculus.validate_calculus_args(d, dim, fixed, self.domain)
+        row = _calculus.fixed_row(d, dim, params)
+        n = int(self.n_nodes[dim])
+        return _calculus.run_single(
+            lambda: self.vectorized_eval_batch(_calculus.fibre_points(d, dim, row, self.nodes[dim]), [0] * d),
+            lambda m: self._calculus_batch(dim, row, m), n, mode, self.nodes[dim], self.weights[dim],
+            self.diff_matrices[dim], (self.domain[dim][0], self.domain[dim][1]))
+
+    def roots(self, dim=None, fixed=None) -> np.ndarray:
+        """Sorted real roots along ``dim`` with every other dimension fixed (``fixed = {dim_index: value}``) by the
+        colleague-matrix method (reference barycentric.py:2277-2327, _calculus.py:198-244).  The fibre is evaluated
+        and solved on the device; above 64 nodes the solve runs on the host (NumPy ``chebroots``).  A non-finite
+        fibre raises ``numpy.linalg.LinAlgError``."""
+        return self._calculus(dim, fixed, "roots")
+
+    def minimize(self, dim=None, fixed=None):
+        """``(value, location)`` of the minimum along ``dim`` (reference barycentric.py:2329-2377): the roots of the
+        derivative series and the two ends are the candidates, the first smallest value wins."""
+        return self._calculus(dim, fixed, "min")
+
+    def maximize(self, dim=None, fixed=None):
+        """``(value, location)`` of the maximum along ``dim`` (reference barycentric.py:2379-2427)."""
+        return self._calculus(dim, fixed, "max")
+
+    def _calculus_rows(self, dim, fixed) -> np.ndarray:
+        from . import _calculus
+        if self.tensor_values is None:
+            raise RuntimeError("Call build() first")
+        return _calculus.validate_batch_args(self.num_dimensions, dim, fixed, self.domain, self.n_nodes)
+
+    def roots_batch(self, dim: int, fixed):
+        """Roots along ``dim`` for every row of ``fixed`` (host float64 ``(N, d-1)``: the other dimensions in
+        increasing order), in one device pass (extension).  Returns ``(roots, counts)``: ``roots`` float64
+        ``(N, max(n_dim-1, 1))`` ascending and NaN-padded, ``counts`` int32 ``(N,)``, -1 where the fibre was not finite
+        or the eigenvalue iteration failed.  At most 64 nodes along ``dim``."""
+        rows = self._calculus_rows(dim, fixed)
+        return self._calculus_batch(int(dim), rows, 0)
+
+    def minimize_batch(self, dim: int, fixed):
+        """``(values, locations)``, float64 ``(N,)``, of the minimum along ``dim`` for every row of ``fixed``
+        (extension; arguments as :meth:`roots_batch`).  NaN where a row failed."""
+        rows = self._calculus_rows(dim, fixed)
+        val, loc, _ = self._calculus_batch(int(dim), rows, 1)
+        return val, loc
+
+    def maximize_batch(self, dim: int, fixed):
+        """``(values, locations)`` of the maximum along ``dim`` for every row of ``fixed`` (extension)."""
+        rows = self._calculus_rows(dim, fixed)
+        val, loc, _ = self._calculus_batch(int(dim), rows, 2)
+        return val, loc
 
     def fast_eval(self, point, derivative_order=None, *, derivative_id=None) -> float:
         """Deprecated alias kept for drop-in compatibility (reference :789-869): same value as

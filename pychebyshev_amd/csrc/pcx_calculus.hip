@@ -1,0 +1,236 @@
+// pcx_calculus.hip -- C ABI of libpcx_hip.so (see include/pcx.h): roots, minima and maxima of an interpolant along one
+// dimension, batched over rows of fixed values of the other dimensions (reference _calculus.py:198-355).  gfx950 only.
+//
+// A handle entry expands every row into the n points (fixed..., x_j) of its fibre (k_calc_expand, x_j the handle's own
+// node values), evaluates them with the handle's existing device evaluation (the node rule of the barycentric kernels
+// makes the weight of dimension `dim` one-hot there) and solves every fibre with k_cheb1d_calculus.  Fibres and results
+// stay in HBM until the one download of the results.
+
+#include "pcx_bary_internal.h"
+#include "calculus_kernels.h"
+
+// rows per pass of the expand / evaluate / solve pipeline: at most this many fibre points in flight
+static const long kCalcChunkPoints = 1L << 21;
+
+static int calc_check(int n, int mode, int64_t N, double lo, double hi, const double *diff, double *roots_out,
+                      int32_t *counts_out, double *val_out, double *loc_out) {
+    if (n < 1 || n > PCX_CALC_MAX_N)
+        return fail(PCX_ERR_INVALID, "n=%d outside [1, %d]: the device root solver takes fibres of at most %d nodes", n,
+                    PCX_CALC_MAX_N, PCX_CALC_MAX_N);
+    if (mode < 0 || mode > 2) return fail(PCX_ERR_INVALID, "mode=%d (0 roots, 1 minimize, 2 maximize)", mode);
+    if (N < 0) return fail(PCX_ERR_INVALID, "N=%lld < 0", (long long)N);
+    if (!(lo < hi)) return fail(PCX_ERR_INVALID, "domain: lo must be < hi");
+    if (!counts_out) return fail(PCX_ERR_INVALID, "counts_out is NULL");
+    if (mode == 0 && !roots_out) return fail(PCX_ERR_INVALID, "roots_out is NULL");
+    if (mode != 0 && (!val_out || !loc_out)) return fail(PCX_ERR_INVALID, "val_out / loc_out is NULL");
+    if (mode != 0 && !diff) return fail(PCX_ERR_INVALID, "diff is NULL (modes 1 and 2 need the differentiation matrix)");
+    return PCX_OK;
+}
+
+// device outputs of a batch of N rows
+struct CalcDevOut {
+    DevBuf roots, counts, val, loc;
+    int alloc(int mode, long N, int W) {
+        int rc = counts.alloc((size_t)N * sizeof(int32_t));
+        if (!rc && mode == 0) rc = roots.alloc((size_t)N * W * sizeof(double));
+        if (!rc && mode != 0) rc = val.alloc((size_t)N * sizeof(double));
+        if (!rc && mode != 0) rc = loc.alloc((size_t)N * sizeof(double));
+        return rc;
+    }
+    int download(int mode, long N, int W, double *roots_out, int32_t *counts_out, double *val_out, double *loc_out,
+                 hipStream_t st) {
+        HIP_TRY(hipMemcpyAsync(counts_out, counts.p, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (mode == 0) {
+            HIP_TRY(hipMemcpyAsync(roots_out, roots.p, (size_t)N * W * sizeof(double), hipMemcpyDeviceToHost, st));
+        } else {
+            HIP_TRY(hipMemcpyAsync(val_out, val.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(loc_out, loc.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+        return PCX_OK;
+    }
+};
+
+// k_cheb1d_calculus over `rows` fibres (a.vals and the outputs already offset to the first row): one wave per fibre,
+// the LDS class chosen by the largest colleague matrix a fibre of n nodes can produce (n - 1)
+static int calc_launch(const CalcArgs &a, long rows, hipStream_t st) {
+    if (rows <= 0) return PCX_OK;
+    if (rows > 0x7fffffffL) return fail(PCX_ERR_UNSUPPORTED, "too many rows for one launch");
+    const int m = a.n - 1;
+    if (m <= 16) hipLaunchKernelGGL(k_cheb1d_calculus<16>, dim3((unsigned)rows), dim3(64), 0, st, a);
+    else if (m <= 32) hipLaunchKernelGGL(k_cheb1d_calculus<32>, dim3((unsigned)rows), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(k_cheb1d_calculus<64>, dim3((unsigned)rows), dim3(64), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return PCX_OK;
+}
+
+// fixed rows (N x (d - 1), the columns of every dimension but `dim` in increasing order) inside [lo, hi] of their
+// dimensions; NaN passes, as in the reference's comparisons
+static int calc_check_fixed(const double *fixed, int64_t N, int d, int dim, const double *lo, const double *hi) {
+    if (d > 1 && N > 0 && !fixed) return fail(PCX_ERR_INVALID, "fixed is NULL");
+    for (int64_t r = 0; r < N; ++r)
+        for (int c = 0, k = 0; k < d; ++k) {
+            if (k == dim) continue;
+            const double v = fixed[r * (d - 1) + c++];
+            if (v < lo[k] || v > hi[k])
+                return fail(PCX_ERR_INVALID, "Fixed value %.17g for dim %d outside domain [%.17g, %.17g] (row %lld)", v, k,
+                            lo[k], hi[k], (long long)r);
+        }
+    return PCX_OK;
+}
+
+// The pipeline of the handle entries: per pass of rows, expand -> evaluate (eval(d_pts, points, d_vals)) -> solve.
+template <typename Eval>
+static int calc_fibres(int d, int dim, int mode, const double *fixed, int64_t N, CalcArgs a, hipStream_t st, Eval eval,
+                       double *roots_out, int32_t *counts_out, double *val_out, double *loc_out) {
+    const int n = a.n;
+    const long chunk = std::max<long>(1, std::min<long>(N, kCalcChunkPoints / n));
+    DevBuf d_fixed, d_pts, d_vals;
+    CalcDevOut out;
+    int rc = d_fixed.alloc((size_t)N * (d - 1) * sizeof(double));
+    if (!rc) rc = d_pts.alloc((size_t)chunk * n * d * sizeof(double));
+    if (!rc) rc = d_vals.alloc((size_t)chunk * n * sizeof(double));
+    if (!rc) rc = out.alloc(mode, N, a.W);
+    if (rc) return rc;
+    if (d > 1) HIP_TRY(hipMemcpyAsync(d_fixed.p, fixed, (size_t)N * (d - 1) * sizeof(double), hipMemcpyHostToDevice, st));
+    for (long r0 = 0; r0 < N; r0 += chunk) {
+        const long rows = std::min<long>(chunk, N - r0);
+        const long total = rows * n * d;
+        const unsigned blocks = (unsigned)std::min<long>((total + 255) / 256, 8192);
+        hipLaunchKernelGGL(k_calc_expand, dim3(blocks), dim3(256), 0, st, d_fixed.as<double>() + (size_t)r0 * (d - 1), rows,
+                           d, dim, n, a.nodes, d_pts.as<double>());
+        HIP_TRY(hipGetLastError());
+        if ((rc = eval(d_pts.as<double>(), rows * n, d_vals.as<double>()))) return rc;
+        CalcArgs c = a;
+        c.vals = d_vals.as<double>();
+        c.counts = out.counts.as<int32_t>() + r0;
+        if (mode == 0) c.roots = out.roots.as<double>() + (size_t)r0 * a.W;
+        else { c.val = out.val.as<double>() + r0; c.loc = out.loc.as<double>() + r0; }
+        if ((rc = calc_launch(c, rows, st))) return rc;
+    }
+    return out.download(mode, N, a.W, roots_out, counts_out, val_out, loc_out, st);
+}
+
+extern "C" int pcx_cheb1d_calculus(int device, int n, double lo, double hi, const double *nodes, const double *weights,
+                                   const double *diff, const double *values, int64_t N, int mode, double *roots_out,
+                                   int32_t *counts_out, double *val_out, double *loc_out) {
+    PCX_API_BEGIN
+    int rc = calc_check(n, mode, N, lo, hi, diff, roots_out, counts_out, val_out, loc_out);
+    if (rc) return rc;
+    if (!nodes || !weights || (N > 0 && !values)) return fail(PCX_ERR_INVALID, "NULL argument");
+    if (N == 0) return PCX_OK;
+    if ((rc = use_device(device))) return rc;
+    const int W = std::max(n - 1, 1);
+    DevBuf d_grid, d_vals;                                     // nodes, weights, D in one buffer
+    CalcDevOut out;
+    rc = d_grid.alloc((size_t)(2 * n + n * n) * sizeof(double));
+    if (!rc) rc = d_vals.alloc((size_t)N * n * sizeof(double));
+    if (!rc) rc = out.alloc(mode, N, W);
+    if (rc) return rc;
+    double *g = d_grid.as<double>();
+    HIP_TRY(hipMemcpy(g, nodes, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(g + n, weights, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    if (mode != 0) HIP_TRY(hipMemcpy(g + 2 * n, diff, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_vals.p, values, (size_t)N * n * sizeof(double), hipMemcpyHostToDevice));
+    CalcArgs a{};
+    a.n = n; a.mode = mode; a.W = W; a.lo = lo; a.hi = hi;
+    a.nodes = g; a.wts = g + n; a.diff = g + 2 * n; a.vals = d_vals.as<double>();
+    a.counts = out.counts.as<int32_t>();
+    a.roots = out.roots.as<double>(); a.val = out.val.as<double>(); a.loc = out.loc.as<double>();
+    if ((rc = calc_launch(a, (long)N, nullptr))) return rc;
+    return out.download(mode, (long)N, W, roots_out, counts_out, val_out, loc_out, nullptr);
+    PCX_API_END
+}
+
+extern "C" int pcx_bary_calculus_batch(pcx_bary *h, int dim, const double *lo, const double *hi, const double *fixed,
+                                       int64_t N, int mode, double *roots_out, int32_t *counts_out, double *val_out,
+                                       double *loc_out) {
+    PCX_API_BEGIN
+    if (!h || !lo || !hi) return fail(PCX_ERR_INVALID, "NULL argument");
+    const int d = h->dims.d;
+    if (dim < 0 || dim >= d) return fail(PCX_ERR_INVALID, "dim %d out of range [0, %d]", dim, d - 1);
+    const int n = h->dims.n[dim];
+    int rc = calc_check(n, mode, N, lo[dim], hi[dim], h->d_diff, roots_out, counts_out, val_out, loc_out);
+    if (!rc) rc = calc_check_fixed(fixed, N, d, dim, lo, hi);
+    if (rc) return rc;
+    if (N == 0) return PCX_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->call_mark = h->clock;
+    DerivedTensor *dt = nullptr;
+    if ((rc = bary_get_tensor(h, nullptr, &dt))) return rc;
+    CalcArgs a{};
+    a.n = n; a.mode = mode; a.W = std::max(n - 1, 1); a.lo = lo[dim]; a.hi = hi[dim];
+    a.nodes = h->d_nodes + h->dims.off[dim];
+    a.wts = h->d_wts + h->dims.off[dim];
+    a.diff = h->d_diff + h->doff[dim];
+    auto eval = [&](const double *d_pts, long npts, double *d_vals) {
+        return bary_launch(h, &dt, 1, dt->slot, d_pts, npts, d_vals, 1, 0, h->stream, &h->s_partial);
+    };
+    return calc_fibres(d, dim, mode, fixed, N, a, h->stream, eval, roots_out, counts_out, val_out, loc_out);
+    PCX_API_END
+}
+
+extern "C" int pcx_tt_calculus_batch(pcx_tt *h, int dim, const double *fixed, int64_t N, int mode, double *roots_out,
+                                     int32_t *counts_out, double *val_out, double *loc_out) {
+    PCX_API_BEGIN
+    int device = 0;
+    TTDims dims{};
+    hipStream_t st = nullptr;
+    int rc = tt_handle_view(h, &device, &dims, &st);
+    if (rc) return rc;
+    const int d = dims.d;
+    if (dim < 0 || dim >= d) return fail(PCX_ERR_INVALID, "dim %d out of range [0, %d]", dim, d - 1);
+    // the domain in the user's frame: user dimension dims.col[k] lives at storage position k
+    double lo[PCX_MAX_DIMS], hi[PCX_MAX_DIMS];
+    int nn[PCX_MAX_DIMS];
+    for (int k = 0; k < d; ++k) {
+        lo[dims.col[k]] = dims.lo[k];
+        hi[dims.col[k]] = dims.hi[k];
+        nn[dims.col[k]] = dims.n[k];
+    }
+    const int n = nn[dim];
+    // the fibre's grid as the host builds it (barycentric.py chebyshev_nodes, compute_barycentric_weights,
+    // compute_differentiation_matrix): ascending type-I nodes, weights by a division chain, D from the weights
+    std::vector<double> grid((size_t)2 * n + (size_t)n * n);
+    double *x = grid.data(), *w = x + n, *D = w + n;
+    for (int j = 0; j < n; ++j) {
+        const double t = std::sin(0.5 * M_PI / n * (double)(2 * j - n + 1));      // chebpts1, ascending
+        x[j] = 0.5 * (lo[dim] + hi[dim]) + 0.5 * (hi[dim] - lo[dim]) * t;
+    }
+    std::sort(x, x + n);
+    for (int i = 0; i < n; ++i) {
+        w[i] = 1.0;
+        for (int j = 0; j < n; ++j)
+            if (j != i) w[i] /= (x[i] - x[j]);
+    }
+    for (int i = 0; i < n; ++i) {
+        double s = 0.0;
+        for (int j = 0; j < n; ++j) {
+            if (j == i) continue;
+            D[(size_t)i * n + j] = w[j] / ((x[i] - x[j]) * w[i]);
+            s += D[(size_t)i * n + j];
+        }
+        D[(size_t)i * n + i] = -s;
+    }
+    rc = calc_check(n, mode, N, lo[dim], hi[dim], D, roots_out, counts_out, val_out, loc_out);
+    if (!rc) rc = calc_check_fixed(fixed, N, d, dim, lo, hi);
+    if (rc) return rc;
+    if (N == 0) return PCX_OK;
+    HIP_TRY(hipSetDevice(device));
+    DevBuf d_grid;
+    if ((rc = d_grid.alloc(grid.size() * sizeof(double)))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_grid.p, grid.data(), grid.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    CalcArgs a{};
+    a.n = n; a.mode = mode; a.W = std::max(n - 1, 1); a.lo = lo[dim]; a.hi = hi[dim];
+    a.nodes = d_grid.as<double>();
+    a.wts = a.nodes + n;
+    a.diff = a.nodes + 2 * n;
+    auto eval = [&](const double *d_pts, long npts, double *d_vals) {
+        return pcx_tt_eval_batch_dev(h, d_pts, npts, d_vals, (void *)st);   // points in the user's column order
+    };
+    rc = calc_fibres(d, dim, mode, fixed, N, a, st, eval, roots_out, counts_out, val_out, loc_out);
+    (void)hipStreamSynchronize(st);                            // d_grid is freed on return
+    return rc;
+    PCX_API_END
+}

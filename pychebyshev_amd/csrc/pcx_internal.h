@@ -278,3 +278,7 @@ static int fan_out(int n_handles, int64_t N, Fn &&block_call) {
         if (rcs[g]) return fail(rcs[g], "device block %d: %s", g, errs[g].c_str());
     return PCX_OK;
 }
+
+// pcx_tt.hip: what pcx_calculus.hip reads of a tensor-train handle (its device, shape and domain by storage position,
+// and its stream)
+PCX_HIDDEN int tt_handle_view(pcx_tt *h, int *device, TTDims *dims, hipStream_t *stream);

@@ -721,6 +721,14 @@ extern "C" int pcx_tt_set_kernel(pcx_tt *h, int variant) {
     PCX_API_END
 }
 
+int tt_handle_view(pcx_tt *h, int *device, TTDims *dims, hipStream_t *stream) {
+    if (!h) return fail(PCX_ERR_INVALID, "handle is NULL");
+    *device = h->device;
+    *dims = h->dims;
+    *stream = h->stream;
+    return PCX_OK;
+}
+
 extern "C" int pcx_tt_stream(pcx_tt *h, void **stream) {
     PCX_API_BEGIN
     if (!h || !stream) return fail(PCX_ERR_INVALID, "NULL argument");

@@ -16,7 +16,8 @@ launches all run on the device (``pcx_spline_eval_batch``: ``k_spline_piece_id``
 
 Auto-N pieces (``error_threshold``) build through the pieces' own doubling loop; ``.pcb`` files
 (class tag 2) are read and written byte-compatibly.  ``sobol_indices`` aggregates the pieces' device-side indices
-on the host as the reference does.  Not provided: algebra, calculus,
+on the host as the reference does.  ``roots`` / ``minimize`` / ``maximize`` solve each piece along the
+dimension on the device and combine the pieces on the host.  Not provided: algebra, calculus batches,
 extrude/slice, auto_knots.
 """
 from __future__ import annotations
@@ -449,6 +450,63 @@ class ChebyshevSpline(ErgonomicsMixin, DerivativeIdMixin):
             idx = np.array([[res[key][k] for k in range(d)] for _, res in results])
             out[key] = {k: float(v) for k, v in enumerate(weight @ idx / variance)}
         return {"first_order": out["first_order"], "total_order": out["total_order"], "variance": variance}
+
+    # ---------------------------------------------------------------- calculus
+    def _calculus_pieces(self, dim, fixed):
+        """The validated ``dim`` and, along it, each piece selected by the fixed values (``searchsorted(knots, v,
+        side="right")`` capped at the last interval, as the reference's ``slice``) with its own ``fixed``."""
+        from ._calculus import validate_calculus_args
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        d = self.num_dimensions
+        dim, params = validate_calculus_args(d, dim, fixed, self.domain)
+        vals = dict(params)
+        ranges = []
+        for k in range(d):
+            if k == dim:
+                ranges.append(range(self._shape[k]))
+            elif len(self.knots[k]) == 0:
+                ranges.append([0])
+            else:
+                ranges.append([min(int(np.searchsorted(self.knots[k], vals[k], side="right")), self._shape[k] - 1)])
+        sub = {k: v for k, v in vals.items()} if d > 1 else None
+        pieces = [self._pieces[int(np.ravel_multi_index(multi, self._shape))] for multi in itertools.product(*ranges)]
+        return dim, pieces, sub
+
+    def roots(self, dim=None, fixed=None) -> np.ndarray:
+        """Sorted roots along ``dim`` (reference spline.py:1762-1820): every piece along ``dim`` is solved on its own
+        domain (one device call each), the roots are concatenated, sorted, and near-duplicates at the knots
+        (``1e-10 (|domain[dim]| + 1)``) dropped."""
+        dim, pieces, sub = self._calculus_pieces(dim, fixed)
+        found = [p.roots(dim, sub) for p in pieces]
+        if not found:
+            return np.array([], dtype=float)
+        out = np.sort(np.concatenate(found))
+        if len(out) > 1:
+            scale = abs(self.domain[dim][1] - self.domain[dim][0]) + 1
+            out = out[np.concatenate([[True], np.diff(out) > 1e-10 * scale])]
+        return out
+
+    def minimize(self, dim=None, fixed=None):
+        """``(value, location)`` of the minimum along ``dim`` over the pieces in order, strictly smaller wins
+        (reference spline.py:1822-1865)."""
+        dim, pieces, sub = self._calculus_pieces(dim, fixed)
+        best = (float("inf"), 0.0)
+        for p in pieces:
+            val, loc = p.minimize(dim, sub)
+            if val < best[0]:
+                best = (val, loc)
+        return best
+
+    def maximize(self, dim=None, fixed=None):
+        """``(value, location)`` of the maximum along ``dim`` (reference spline.py:1867-1910)."""
+        dim, pieces, sub = self._calculus_pieces(dim, fixed)
+        best = (float("-inf"), 0.0)
+        for p in pieces:
+            val, loc = p.maximize(dim, sub)
+            if val > best[0]:
+                best = (val, loc)
+        return best
 
     # ---------------------------------------------------------------- properties
     @property

@@ -17,9 +17,11 @@ DCT -- runs on the device (``pcx_tt_cross_step``, ``pcx_tt_grid_eval``,
 is always a ``pcx_tt_eval_batch`` launch; there is no CPU fallback.
 
 ``sobol_indices`` contracts the coefficient cores on the host (NumPy, O(d n r^2): no hot path).
+``roots`` / ``minimize`` / ``maximize`` and their batched forms evaluate the fibres and solve them on the device
+(``pcx_tt_calculus_batch``).
 
 Out of scope in this tier (raise ``NotImplementedError``): ``method='als'``
-builders, algebra, calculus, slicing, reordering.
+builders, algebra, slicing, reordering.
 """
 from __future__ import annotations
 
@@ -899,6 +901,81 @@ class ChebyshevTT(ErgonomicsMixin):
         return {"first_order": {user[s]: float(first[s]) for s in range(self.num_dimensions)},
                 "total_order": {user[s]: float(total[s]) for s in range(self.num_dimensions)},
                 "variance": variance}
+
+    # ---------------------------------------------------------------- calculus
+    def _user_frame_domain(self) -> list:
+        """``domain`` indexed by user dimension: user dimension u lives at storage position ``_dim_order.index(u)``."""
+        return [self.domain[self._dim_order.index(u)] for u in range(self.num_dimensions)]
+
+    def _calculus_batch(self, dim: int, rows: np.ndarray, mode: int):
+        from . import _calculus
+        t = self._dev()
+        rows = _lib.f64(rows)
+        N = rows.shape[0]
+
+        def call(r, c, v, loc):
+            return t.lib.pcx_tt_calculus_batch(t.handle, int(dim), _lib.p_f64(rows), N, mode, r, c, v, loc)
+        return _calculus.run_batch(call, t.lib, int(self.n_nodes[self._dim_order.index(dim)]), N, mode)
+
+    def _calculus(self, dim, fixed, mode: str):
+        from . import _calculus
+        from .barycentric import chebyshev_nodes, compute_barycentric_weights, compute_differentiation_matrix
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        d = self.num_dimensions
+        udom = self._user_frame_domain()
+        dim, params = _calculus.validate_calculus_args(d, dim, fixed, udom)
+        row = _calculus.fixed_row(d, dim, params)
+        n = int(self.n_nodes[self._dim_order.index(dim)])
+        a, b = udom[dim]
+        if n <= _calculus.MAX_DEVICE_N:
+            nodes = weights = diff = None
+        else:
+            nodes = chebyshev_nodes(a, b, n)
+            weights = compute_barycentric_weights(nodes)
+            diff = compute_differentiation_matrix(nodes, weights)
+        return _calculus.run_single(
+            lambda: self.eval_batch(_calculus.fibre_points(d, dim, row, nodes)),
+            lambda m: self._calculus_batch(dim, row, m), n, mode, nodes, weights, diff, (a, b))
+
+    def roots(self, dim=None, fixed=None) -> np.ndarray:
+        """Sorted roots along user dimension ``dim`` with the others fixed (reference tensor_train.py:1749-1790): the
+        fibre is the TT's values at the nodes of ``dim``, evaluated and solved on the device (above 64 nodes the
+        solve runs on the host).  ``dim`` and ``fixed`` are in the user's frame."""
+        return self._calculus(dim, fixed, "roots")
+
+    def minimize(self, dim=None, fixed=None):
+        """``(value, location)`` of the minimum along user dimension ``dim`` (reference tensor_train.py:1792-1831)."""
+        return self._calculus(dim, fixed, "min")
+
+    def maximize(self, dim=None, fixed=None):
+        """``(value, location)`` of the maximum along user dimension ``dim`` (reference tensor_train.py:1833-1872)."""
+        return self._calculus(dim, fixed, "max")
+
+    def _calculus_rows(self, dim, fixed) -> np.ndarray:
+        from . import _calculus
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        user_n = [self.n_nodes[self._dim_order.index(u)] for u in range(self.num_dimensions)]
+        return _calculus.validate_batch_args(self.num_dimensions, dim, fixed, self._user_frame_domain(), user_n)
+
+    def roots_batch(self, dim: int, fixed):
+        """Roots along user dimension ``dim`` for every row of ``fixed`` (extension; as
+        ``ChebyshevApproximation.roots_batch``, columns = the other user dimensions in increasing order)."""
+        rows = self._calculus_rows(dim, fixed)
+        return self._calculus_batch(int(dim), rows, 0)
+
+    def minimize_batch(self, dim: int, fixed):
+        """``(values, locations)`` of the minimum along user dimension ``dim`` for every row of ``fixed``."""
+        rows = self._calculus_rows(dim, fixed)
+        val, loc, _ = self._calculus_batch(int(dim), rows, 1)
+        return val, loc
+
+    def maximize_batch(self, dim: int, fixed):
+        """``(values, locations)`` of the maximum along user dimension ``dim`` for every row of ``fixed``."""
+        rows = self._calculus_rows(dim, fixed)
+        val, loc, _ = self._calculus_batch(int(dim), rows, 2)
+        return val, loc
 
     def error_estimate(self) -> float:
         """Sum over dimensions of the largest last Chebyshev coefficient (reference :2469-2504)."""
