@@ -345,6 +345,30 @@ int pcx_tt_svd(int device, int d, const int32_t *n_nodes, const double *tensor, 
                double tol, int32_t *ranks_out, double *cores_out, int64_t cores_cap,
                int64_t *cores_len, int32_t *sweeps_out);
 
+/* TT rounding (reference _algebra.py::_tt_round_cores), used by ChebyshevTT + and -: a right-to-left
+ * orthogonalisation sweep, then a left-to-right truncated-SVD sweep, every factorisation a one-sided
+ * Jacobi iteration on the device.  Input: d coefficient cores (r_{k-1}, n_k, r_k), C order,
+ * concatenated, ranks[d+1] with ranks[0] = ranks[d] = 1.  The rank rule is the reference's (cap at
+ * max_rank, drop singular values <= tol * sigma_max when sigma_max > 0, at least 1).  Ranks above 256
+ * or more than 256 nodes are PCX_ERR_UNSUPPORTED before anything runs.  Outputs: ranks_out[d+1]; the
+ * rounded cores, cores 0..d-2 left-orthonormal, concatenated in cores_out (capacity cores_cap
+ * doubles -- the input length always suffices -- used length in *cores_len); sweeps_out (optional)
+ * = Jacobi sweeps run.                                                                          */
+int pcx_tt_round(int device, int d, const int32_t *n_nodes, const int32_t *ranks, const double *cores,
+                 int max_rank, double tol, int32_t *ranks_out, double *cores_out, int64_t cores_cap,
+                 int64_t *cores_len, int32_t *sweeps_out);
+
+/* A sequence of adjacent swaps of storage axes (reference _algebra.py::_tt_swap_adjacent, driven by
+ * ChebyshevTT.reorder): swap s exchanges axes swaps[s] and swaps[s] + 1 by one truncated SVD of the
+ * merged pair (same rank rule).  Same input layout and limits as pcx_tt_round; a merged pair of more
+ * than 4096 rows (r_{i-1} n_{i+1}) or 2^24 elements is PCX_ERR_UNSUPPORTED.  Outputs: n_nodes_out[d]
+ * (the permuted node counts), ranks_out[d+1], the cores in cores_out as above (capacity: the caller
+ * bounds the new ranks), sweeps_out (optional).                                                 */
+int pcx_tt_reorder(int device, int d, const int32_t *n_nodes, const int32_t *ranks, const double *cores,
+                   int n_swaps, const int32_t *swaps, int max_rank, double tol, int32_t *n_nodes_out,
+                   int32_t *ranks_out, double *cores_out, int64_t cores_cap, int64_t *cores_len,
+                   int32_t *sweeps_out);
+
 /* ---- multi-GPU: the final gather of the per-rank result blocks ----------------- */
 /* The reference has no multi-device path (docs/roadmap.md:245); SURVEY.md 8(e) defines
  * it: query rows are sharded in contiguous blocks over one process per GPU, the model is

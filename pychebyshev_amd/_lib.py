@@ -119,6 +119,8 @@ SIGNATURES = {
     "pcx_tt_value_to_coeff_core": (_I, [_I, c_f64p, _I, _I, _I, c_f64p]),
     "pcx_tt_grid_eval": (_I, [_I, _I, c_i32p, c_i32p, c_f64p, c_i32p, _I, c_f64p]),
     "pcx_tt_svd": (_I, [_I, _I, c_i32p, c_f64p, _I, _D, c_i32p, c_f64p, _L, c_i64p, c_i32p]),
+    "pcx_tt_round": (_I, [_I, _I, c_i32p, c_i32p, c_f64p, _I, _D, c_i32p, c_f64p, _L, c_i64p, c_i32p]),
+    "pcx_tt_reorder": (_I, [_I, _I, c_i32p, c_i32p, c_f64p, _I, c_i32p, _I, _D, c_i32p, c_i32p, c_f64p, _L, c_i64p, c_i32p]),
     "pcx_comm_unique_id": (_I, [_V]),
     "pcx_comm_create": (_I, [_I, _I, _I, _V, c_vpp]),
     "pcx_comm_destroy": (_I, [_V]),

@@ -19,7 +19,8 @@ as the reference builds it, and copied to the device when the first evaluation h
 the reference.  ``error_threshold`` (auto-N) builds, ``error_estimate``, ``slice`` and
 ``integrate`` run their tensor contractions on the device, and so do the coefficient transform and
 energy reduction of ``sobol_indices``.  ``roots`` / ``minimize`` / ``maximize`` and their batched forms solve every
-fibre on the device (``pcx_bary_calculus_batch``).  Not provided: algebra, extrude, plotting.
+fibre on the device (``pcx_bary_calculus_batch``).  ``+``, ``-``, ``*`` and ``/`` (with scalars) combine value tensors
+on the host, as the reference does (``_algebra``).  Not provided: extrude, plotting.
 """
 from __future__ import annotations
 
@@ -34,7 +35,7 @@ from typing import Callable, List, Sequence, Tuple
 import numpy as np
 from numpy.polynomial.chebyshev import chebpts1
 
-from . import _lib
+from . import _algebra, _lib
 from ._derivative_ids import DerivativeIdMixin
 from ._ergonomics import ErgonomicsMixin
 from ._version import __version__
@@ -782,6 +783,67 @@ class ChebyshevApproximation(ErgonomicsMixin, DerivativeIdMixin):
             for lst in (nodes, weights, diffs, domain, n_nodes):
                 del lst[dim_idx]
         return self._reduced(tensor, nodes, weights, diffs, domain, n_nodes)
+
+    # ---------------------------------------------------------------- algebra
+    # Reference barycentric.py:2433-2500.  The value tensors are combined with NumPy; the result shares this
+    # object's nodes, weights and differentiation matrices, and its device model is built on first evaluation.
+    # The in-place forms rebind tensor_values to a new array: the device copy is recognised as stale by the
+    # identity of that array (_DeviceModel.tensor_ref), so it must never be modified in place.
+    def _combined(self, tensor) -> "ChebyshevApproximation":
+        return self._reduced(tensor, self.nodes, self.weights, self.diff_matrices,
+                             [list(b) for b in self.domain], list(self.n_nodes))
+
+    def __add__(self, other):
+        if type(self) is not type(other):
+            return NotImplemented
+        _algebra.check_compatible(self, other)
+        return self._combined(self.tensor_values + other.tensor_values)
+
+    def __sub__(self, other):
+        if type(self) is not type(other):
+            return NotImplemented
+        _algebra.check_compatible(self, other)
+        return self._combined(self.tensor_values - other.tensor_values)
+
+    def __mul__(self, scalar):
+        if not _algebra.is_scalar(scalar):
+            return NotImplemented
+        return self._combined(self.tensor_values * float(scalar))
+
+    def __rmul__(self, scalar):
+        return self.__mul__(scalar)
+
+    def __truediv__(self, scalar):
+        if not _algebra.is_scalar(scalar):
+            return NotImplemented
+        return self.__mul__(1.0 / float(scalar))
+
+    def __neg__(self):
+        return self.__mul__(-1.0)
+
+    def __iadd__(self, other):
+        _algebra.check_compatible(self, other)
+        self.tensor_values = self.tensor_values + other.tensor_values
+        self._cached_error_estimate = None
+        return self
+
+    def __isub__(self, other):
+        _algebra.check_compatible(self, other)
+        self.tensor_values = self.tensor_values - other.tensor_values
+        self._cached_error_estimate = None
+        return self
+
+    def __imul__(self, scalar):
+        if not _algebra.is_scalar(scalar):
+            return NotImplemented
+        self.tensor_values = self.tensor_values * float(scalar)
+        self._cached_error_estimate = None
+        return self
+
+    def __itruediv__(self, scalar):
+        if not _algebra.is_scalar(scalar):
+            return NotImplemented
+        return self.__imul__(1.0 / float(scalar))
 
     # ---------------------------------------------------------------- persistence
     def __getstate__(self) -> dict:

@@ -13,7 +13,9 @@ v0.21.1) for the evaluation path:
 group of the whole batch in one device launch and a last kernel adds the slide results in
 the reference's order.
 
-Out of scope in this tier: algebra, calculus, extrude/slice, plotting.
+``+``, ``-``, ``*`` and ``/`` combine the slides' value tensors and the pivot value on the host.
+
+Out of scope in this tier: calculus, extrude/slice, plotting.
 """
 from __future__ import annotations
 
@@ -25,7 +27,7 @@ from typing import Callable, List, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib
+from . import _algebra, _lib
 from ._version import __version__
 from ._derivative_ids import DerivativeIdMixin
 from ._ergonomics import ErgonomicsMixin
@@ -213,6 +215,104 @@ class ChebyshevSlider(ErgonomicsMixin, DerivativeIdMixin):
         _lib.check(s.lib.pcx_slider_eval_multi_batch(s.handle, _lib.p_f64(pts), pts.shape[0], _lib.p_i32(specs),
                                                      specs.shape[0], _lib.p_f64(out)), s.lib)
         return out
+
+    # ---------------------------------------------------------------- algebra
+    # Reference slider.py:1285-1390: slide by slide on the host, pivot_value combined the same way.  The in-place
+    # forms rebind every slide's tensor_values and pivot_value, which is how the device copy
+    # (_DeviceSlider.matches) sees that it is stale.
+    def _check_slider_compatible(self, other) -> None:
+        _algebra.check_compatible(self, other)
+        if self.partition != other.partition:
+            raise ValueError(f"Partition mismatch: {self.partition} vs {other.partition}")
+        if self.pivot_point != other.pivot_point:
+            raise ValueError(f"Pivot point mismatch: {self.pivot_point} vs {other.pivot_point}")
+
+    def _with_slides(self, slides, pivot_value) -> "ChebyshevSlider":
+        obj = object.__new__(ChebyshevSlider)
+        obj.function = None
+        obj.num_dimensions = self.num_dimensions
+        obj.domain = [list(b) for b in self.domain]
+        obj.n_nodes = list(self.n_nodes)
+        obj.partition = [list(g) for g in self.partition]
+        obj.pivot_point = list(self.pivot_point)
+        obj.max_derivative_order = self.max_derivative_order
+        obj.descriptor = ""
+        obj.additional_data = None
+        obj._dim_to_slide = self._dim_to_slide
+        obj.slides = slides
+        obj.pivot_value = pivot_value
+        obj._built = True
+        obj._cached_error_estimate = None
+        obj._derivative_id_registry = {}
+        obj._derivative_id_to_orders = []
+        obj._device_slider = None
+        obj._device_index = self.__dict__.get("_device_index")
+        return obj
+
+    def __add__(self, other):
+        if type(self) is not type(other):
+            return NotImplemented
+        self._check_slider_compatible(other)
+        return self._with_slides([s._combined(s.tensor_values + t.tensor_values) for s, t in zip(self.slides, other.slides)],
+                                 self.pivot_value + other.pivot_value)
+
+    def __sub__(self, other):
+        if type(self) is not type(other):
+            return NotImplemented
+        self._check_slider_compatible(other)
+        return self._with_slides([s._combined(s.tensor_values - t.tensor_values) for s, t in zip(self.slides, other.slides)],
+                                 self.pivot_value - other.pivot_value)
+
+    def __mul__(self, scalar):
+        if not _algebra.is_scalar(scalar):
+            return NotImplemented
+        f = float(scalar)
+        return self._with_slides([s._combined(s.tensor_values * f) for s in self.slides], self.pivot_value * f)
+
+    def __rmul__(self, scalar):
+        return self.__mul__(scalar)
+
+    def __truediv__(self, scalar):
+        if not _algebra.is_scalar(scalar):
+            return NotImplemented
+        return self.__mul__(1.0 / float(scalar))
+
+    def __neg__(self):
+        return self.__mul__(-1.0)
+
+    def __iadd__(self, other):
+        self._check_slider_compatible(other)
+        for s, t in zip(self.slides, other.slides):
+            s.tensor_values = s.tensor_values + t.tensor_values
+            s._cached_error_estimate = None
+        self.pivot_value = self.pivot_value + other.pivot_value
+        self._cached_error_estimate = None
+        return self
+
+    def __isub__(self, other):
+        self._check_slider_compatible(other)
+        for s, t in zip(self.slides, other.slides):
+            s.tensor_values = s.tensor_values - t.tensor_values
+            s._cached_error_estimate = None
+        self.pivot_value = self.pivot_value - other.pivot_value
+        self._cached_error_estimate = None
+        return self
+
+    def __imul__(self, scalar):
+        if not _algebra.is_scalar(scalar):
+            return NotImplemented
+        f = float(scalar)
+        for s in self.slides:
+            s.tensor_values = s.tensor_values * f
+            s._cached_error_estimate = None
+        self.pivot_value = self.pivot_value * f
+        self._cached_error_estimate = None
+        return self
+
+    def __itruediv__(self, scalar):
+        if not _algebra.is_scalar(scalar):
+            return NotImplemented
+        return self.__imul__(1.0 / float(scalar))
 
     # ---------------------------------------------------------------- misc
     @property

@@ -17,8 +17,8 @@ launches all run on the device (``pcx_spline_eval_batch``: ``k_spline_piece_id``
 Auto-N pieces (``error_threshold``) build through the pieces' own doubling loop; ``.pcb`` files
 (class tag 2) are read and written byte-compatibly.  ``sobol_indices`` aggregates the pieces' device-side indices
 on the host as the reference does.  ``roots`` / ``minimize`` / ``maximize`` solve each piece along the
-dimension on the device and combine the pieces on the host.  Not provided: algebra, calculus batches,
-extrude/slice, auto_knots.
+dimension on the device and combine the pieces on the host.  ``+``, ``-``, ``*`` and ``/`` combine the pieces' value tensors on the host.  Not provided:
+calculus batches, extrude/slice, auto_knots.
 """
 from __future__ import annotations
 
@@ -31,7 +31,7 @@ from typing import Callable, List, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib
+from . import _algebra, _lib
 from ._derivative_ids import DerivativeIdMixin
 from ._ergonomics import ErgonomicsMixin
 from ._version import __version__
@@ -507,6 +507,103 @@ class ChebyshevSpline(ErgonomicsMixin, DerivativeIdMixin):
             if val > best[0]:
                 best = (val, loc)
         return best
+
+    # ---------------------------------------------------------------- algebra
+    # Reference spline.py:1912-2010: piece by piece on the host (ChebyshevApproximation's operators), the
+    # result a new spline over the same knots.  The in-place forms rebind every piece's tensor_values, which is
+    # how the device copy (_DeviceSpline.matches) sees that it is stale.
+    def _check_spline_compatible(self, other) -> None:
+        _algebra.check_compatible(self, other)
+        if self.knots != other.knots:
+            raise ValueError(f"Knot mismatch: {self.knots} vs {other.knots}")
+
+    def _with_pieces(self, pieces) -> "ChebyshevSpline":
+        obj = object.__new__(ChebyshevSpline)
+        obj.function = None
+        obj.num_dimensions = self.num_dimensions
+        obj.domain = [list(b) for b in self.domain]
+        obj.error_threshold = None
+        obj.max_n = self.max_n
+        obj.n_workers = None
+        obj._n_nodes_nested = self._n_nodes_nested
+        obj.n_nodes = [list(v) if isinstance(v, list) else v for v in self.n_nodes]
+        obj.knots = [list(k) for k in self.knots]
+        obj.max_derivative_order = self.max_derivative_order
+        obj.additional_data = None
+        obj._derivative_id_registry = {}
+        obj._derivative_id_to_orders = []
+        obj.descriptor = ""
+        obj._intervals = self._intervals
+        obj._shape = self._shape
+        obj._pieces = pieces
+        obj._built = True
+        obj._build_time = 0.0
+        obj._cached_error_estimate = None
+        obj._device_spline = None
+        obj._device_index = self._device_index
+        return obj
+
+    def __add__(self, other):
+        if type(self) is not type(other):
+            return NotImplemented
+        self._check_spline_compatible(other)
+        return self._with_pieces([p._combined(p.tensor_values + q.tensor_values)
+                                  for p, q in zip(self._pieces, other._pieces)])
+
+    def __sub__(self, other):
+        if type(self) is not type(other):
+            return NotImplemented
+        self._check_spline_compatible(other)
+        return self._with_pieces([p._combined(p.tensor_values - q.tensor_values)
+                                  for p, q in zip(self._pieces, other._pieces)])
+
+    def __mul__(self, scalar):
+        if not _algebra.is_scalar(scalar):
+            return NotImplemented
+        s = float(scalar)
+        return self._with_pieces([p._combined(p.tensor_values * s) for p in self._pieces])
+
+    def __rmul__(self, scalar):
+        return self.__mul__(scalar)
+
+    def __truediv__(self, scalar):
+        if not _algebra.is_scalar(scalar):
+            return NotImplemented
+        return self.__mul__(1.0 / float(scalar))
+
+    def __neg__(self):
+        return self.__mul__(-1.0)
+
+    def __iadd__(self, other):
+        self._check_spline_compatible(other)
+        for p, q in zip(self._pieces, other._pieces):
+            p.tensor_values = p.tensor_values + q.tensor_values
+            p._cached_error_estimate = None
+        self._cached_error_estimate = None
+        return self
+
+    def __isub__(self, other):
+        self._check_spline_compatible(other)
+        for p, q in zip(self._pieces, other._pieces):
+            p.tensor_values = p.tensor_values - q.tensor_values
+            p._cached_error_estimate = None
+        self._cached_error_estimate = None
+        return self
+
+    def __imul__(self, scalar):
+        if not _algebra.is_scalar(scalar):
+            return NotImplemented
+        s = float(scalar)
+        for p in self._pieces:
+            p.tensor_values = p.tensor_values * s
+            p._cached_error_estimate = None
+        self._cached_error_estimate = None
+        return self
+
+    def __itruediv__(self, scalar):
+        if not _algebra.is_scalar(scalar):
+            return NotImplemented
+        return self.__imul__(1.0 / float(scalar))
 
     # ---------------------------------------------------------------- properties
     @property

@@ -20,8 +20,11 @@ is always a ``pcx_tt_eval_batch`` launch; there is no CPU fallback.
 ``roots`` / ``minimize`` / ``maximize`` and their batched forms evaluate the fibres and solve them on the device
 (``pcx_tt_calculus_batch``).
 
+``+`` / ``-`` stack the cores block-diagonally and round them back on the device (``pcx_tt_round``);
+``reorder`` runs its adjacent swaps on the device (``pcx_tt_reorder``); scalars scale core 0 on the host.
+
 Out of scope in this tier (raise ``NotImplementedError``): ``method='als'``
-builders, algebra, slicing, reordering.
+builders, slicing, extrusion.
 """
 from __future__ import annotations
 
@@ -983,6 +986,131 @@ class ChebyshevTT(ErgonomicsMixin):
         if self._cached_error_estimate is None:
             self._cached_error_estimate = float(sum(np.max(np.abs(c[:, -1, :])) for c in self._coeff_cores))
         return self._cached_error_estimate
+
+    # ---------------------------------------------------------------- algebra
+    # Reference tensor_train.py:3287-3458 and :2575-2676.  Scalars scale core 0 on the host; a sum stacks the cores
+    # block-diagonally (ranks r_a + r_b) and rounds them back on the device (pcx_tt_round); reorder runs its adjacent
+    # swaps on the device (pcx_tt_reorder).  Every result is a new object: the in-place forms rebind the name.
+    def _derived(self, cores, *, max_rank=None, domain=None, n_nodes=None, dim_order=None) -> "ChebyshevTT":
+        obj = self.__class__.__new__(self.__class__)
+        obj.function = None
+        obj.num_dimensions = self.num_dimensions
+        obj.domain = list(self.domain if domain is None else domain)
+        obj.n_nodes = list(self.n_nodes if n_nodes is None else n_nodes)
+        obj.max_rank = self.max_rank if max_rank is None else max_rank
+        obj.tolerance = self.tolerance
+        obj.max_sweeps = self.max_sweeps
+        obj.max_derivative_order = self.max_derivative_order
+        obj.additional_data = self.additional_data
+        obj.descriptor = self.descriptor
+        obj.method = self.method
+        obj._coeff_cores = cores
+        obj._tt_ranks = [c.shape[0] for c in cores] + [cores[-1].shape[2]]
+        obj._built = True
+        obj._build_time = 0.0
+        obj._total_build_evals = 0
+        obj._cached_error_estimate = None
+        obj._dim_order = list(self._dim_order if dim_order is None else dim_order)
+        obj._device_tt = None
+        obj._device_index = self._device_index
+        return obj
+
+    def _check_compatible_tt(self, other) -> None:
+        if not isinstance(other, ChebyshevTT):
+            raise TypeError(f"unsupported operand type for ChebyshevTT: {type(other).__name__}")
+        self._check_built()
+        other._check_built()
+        if self.num_dimensions != other.num_dimensions:
+            raise ValueError(f"num_dimensions mismatch: {self.num_dimensions} vs {other.num_dimensions}")
+        if list(self.n_nodes) != list(other.n_nodes):
+            raise ValueError(f"n_nodes mismatch: {self.n_nodes} vs {other.n_nodes}")
+        if not np.allclose(np.asarray(self.domain, dtype=float), np.asarray(other.domain, dtype=float)):
+            raise ValueError(f"domain mismatch: {self.domain} vs {other.domain}")
+        if self._dim_order != other._dim_order:
+            raise ValueError(f"TT dim_order mismatch: {self._dim_order} vs {other._dim_order}. "
+                             "Call other = other.reorder(self.dim_order) (or self = "
+                             "self.reorder(other.dim_order)) to align before adding/subtracting.")
+
+    def __add__(self, other: "ChebyshevTT") -> "ChebyshevTT":
+        """Sum: block-diagonal stacking, then rounding on the device to ``max(self.max_rank, other.max_rank)``
+        with ``self.tolerance`` as the relative singular-value cutoff."""
+        from . import _algebra
+        self._check_compatible_tt(other)
+        target = max(self.max_rank, other.max_rank)
+        stacked = _algebra.tt_stack(self._coeff_cores, other._coeff_cores)
+        if self.num_dimensions > 1:
+            dev = _lib.default_device() if self._device_index is None else self._device_index
+            stacked = _algebra.tt_round(stacked, target, self.tolerance, dev)
+        return self._derived(stacked, max_rank=target)
+
+    def __sub__(self, other: "ChebyshevTT") -> "ChebyshevTT":
+        return self + (-other)
+
+    def __neg__(self) -> "ChebyshevTT":
+        return self._scaled(-1.0)
+
+    def _scaled(self, s: float) -> "ChebyshevTT":
+        self._check_built()
+        cores = [c.copy() for c in self._coeff_cores]
+        cores[0] = cores[0] * s
+        return self._derived(cores)
+
+    def __mul__(self, scalar) -> "ChebyshevTT":
+        from . import _algebra
+        if not _algebra.is_scalar(scalar):
+            raise TypeError(f"ChebyshevTT * {type(scalar).__name__} is not supported "
+                            "(only scalar multiplication is defined for TT)")
+        return self._scaled(float(scalar))
+
+    def __rmul__(self, scalar) -> "ChebyshevTT":
+        return self.__mul__(scalar)
+
+    def __truediv__(self, scalar) -> "ChebyshevTT":
+        from . import _algebra
+        if not _algebra.is_scalar(scalar):
+            raise TypeError(f"ChebyshevTT / {type(scalar).__name__} is not supported")
+        if float(scalar) == 0.0:
+            raise ZeroDivisionError("division by zero")
+        return self.__mul__(1.0 / float(scalar))
+
+    def __iadd__(self, other) -> "ChebyshevTT":
+        return self + other
+
+    def __isub__(self, other) -> "ChebyshevTT":
+        return self - other
+
+    def __imul__(self, scalar) -> "ChebyshevTT":
+        return self * scalar
+
+    def __itruediv__(self, scalar) -> "ChebyshevTT":
+        return self / scalar
+
+    def reorder(self, new_order, *, max_rank=None, tolerance=None) -> "ChebyshevTT":
+        """New TT whose storage order is ``new_order`` (reference :2575-2676): the current order is bubble-sorted into
+        ``new_order`` by adjacent swaps, each one truncated SVD of the merged pair on the device, capped at
+        ``max_rank`` (default ``self.max_rank``) with relative cutoff ``tolerance`` (default ``self.tolerance``)."""
+        from . import _algebra
+        self._check_built()
+        new_order = list(new_order)
+        d = self.num_dimensions
+        if sorted(new_order) != list(range(d)):
+            raise ValueError(f"new_order must be a permutation of range({d}); got {new_order!r}")
+        if new_order == self._dim_order:
+            return self.clone()
+        eff_rank = self.max_rank if max_rank is None else max_rank
+        eff_tol = self.tolerance if tolerance is None else tolerance
+        current, n_nodes, domain = list(self._dim_order), list(self.n_nodes), list(self.domain)
+        swaps = []
+        for k in range(d):
+            j = current.index(new_order[k])
+            while j > k:
+                swaps.append(j - 1)
+                for lst in (current, n_nodes, domain):
+                    lst[j - 1], lst[j] = lst[j], lst[j - 1]
+                j -= 1
+        dev = _lib.default_device() if self._device_index is None else self._device_index
+        cores = _algebra.tt_swaps(self._coeff_cores, swaps, eff_rank, eff_tol, dev)
+        return self._derived(cores, domain=domain, n_nodes=n_nodes, dim_order=new_order)
 
     # ---------------------------------------------------------------- persistence
     def __getstate__(self) -> dict:
