@@ -84,7 +84,6 @@ extern "C" int pcx_bary_destroy(pcx_bary *h) {
     for (auto &kv : h->cache) kv.second.free_all();
     (void)hipFree(h->d_tab);
     h->s_partial.release();
-    h->pin.release();
     (void)hipFree(h->d_nodes); (void)hipFree(h->d_wts); (void)hipFree(h->d_diff);
     (void)hipFree(h->d_cheb);
     h->s_cheb[0].release(); h->s_cheb[1].release(); h->s_sobol.release();
@@ -94,10 +93,8 @@ extern "C" int pcx_bary_destroy(pcx_bary *h) {
     (void)hipFree(h->d_rowcode_hi); (void)hipFree(h->d_kcode_hi);
     (void)hipFree(h->d_rowcode_g0);
     for (pcx_bary *&r : h->rot) { if (r) pcx_bary_destroy(r); r = nullptr; }
+    h->stage.release();
     h->s_rot.release(); h->s_rot2.release();
-    h->s_pts.release(); h->s_out.release();
-    h->s_pts2.release(); h->s_out2.release();
-    if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return PCX_OK;
@@ -1194,7 +1191,7 @@ static int bary_launch_specs(pcx_bary *h, const int32_t *derivs, DerivedTensor *
     const int d = h->dims.d;
     std::vector<BaryGroup> subs;
     std::vector<char> grouped;
-    const bool own_stream = st == h->stream || (h->stream2 && st == h->stream2);
+    const bool own_stream = st == h->stream || (h->stage.second && st == h->stage.second);
     bary_plan_groups(h, derivs, m, N_call > 0 ? N_call : N, own_stream, subs, grouped);
     // runs of consecutive ungrouped specs: ordinary launches
     for (int s = 0; s < m;) {
@@ -1213,7 +1210,7 @@ static int bary_launch_specs(pcx_bary *h, const int32_t *derivs, DerivedTensor *
         for (const BaryGroup &sub : subs)
             if (sub.q > 0 && !rpts[sub.q]) { rpts[sub.q] = d_pts; ++nq; }
         if (nq) {
-            Scratch &sc = (h->stream2 && st == h->stream2) ? h->s_rot2 : h->s_rot;
+            Scratch &sc = (h->stage.second && st == h->stage.second) ? h->s_rot2 : h->s_rot;
             int rc = sc.reserve((size_t)nq * N * d * sizeof(double));
             if (rc) return rc;
             double *dst = (double *)sc.ptr;
@@ -1283,6 +1280,33 @@ extern "C" int pcx_bary_eval_batch_dev(pcx_bary *h, const double *d_pts, int64_t
     PCX_API_END
 }
 
+// The derived tensors of m specs (rows of `derivs`, m x d; NULL: the value) and the fragment table a launch of them
+// reads: the single spec's own slot, else h->d_tab.  d_tab is rewritten only when the spec set changes, and only after
+// the whole device has drained: launches still in flight on any stream may read it (device-resident calls return without
+// waiting).  Caller holds h->mu.
+PCX_HIDDEN int bary_spec_tensors(pcx_bary *h, const int32_t *derivs, int m, std::vector<DerivedTensor *> &dts,
+                                 const double *const **frag_tab) {
+    const int d = h->dims.d;
+    dts.resize(m);
+    for (int s = 0; s < m; ++s) {
+        int rc = bary_get_tensor(h, derivs ? derivs + (size_t)s * d : nullptr, &dts[s]);
+        if (rc) return rc;
+    }
+    *frag_tab = dts[0]->slot;
+    const int eff = bary_effective_variant(h);
+    if (m > 1 && (eff == 4 || eff == 5 || h->mfma_ok)) {
+        std::vector<double *> tab(m);
+        for (int s = 0; s < m; ++s) tab[s] = (eff == 4 || eff == 5) ? dts[s]->plain : dts[s]->frag;
+        if (tab != h->tab_host) {
+            HIP_TRY(hipDeviceSynchronize());
+            HIP_TRY(hipMemcpy(h->d_tab, tab.data(), m * sizeof(double *), hipMemcpyHostToDevice));
+            h->tab_host = tab;
+        }
+        *frag_tab = h->d_tab;
+    }
+    return PCX_OK;
+}
+
 // m specs at N device-resident points into d_out (N x m row-major); groups of kMaxSpecs specs per launch.
 extern "C" int pcx_bary_eval_multi_batch_dev(pcx_bary *h, const double *d_pts, int64_t N, const int32_t *derivs,
                                              int m, double *d_out, void *stream) {
@@ -1299,25 +1323,12 @@ extern "C" int pcx_bary_eval_multi_batch_dev(pcx_bary *h, const double *d_pts, i
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     for (int s0 = 0; s0 < m; s0 += kMaxSpecs) {
         const int mc = std::min(kMaxSpecs, m - s0);
-        std::vector<DerivedTensor *> dts(mc);
-        for (int s = 0; s < mc; ++s) {
-            int rc = bary_get_tensor(h, derivs + (size_t)(s0 + s) * d, &dts[s]);
-            if (rc) return rc;
-        }
-        const double *const *frag_tab = dts[0]->slot;
-        const int eff = bary_effective_variant(h);
-        if (mc > 1 && (eff == 4 || eff == 5 || h->mfma_ok)) {
-            std::vector<double *> tab(mc);
-            for (int s = 0; s < mc; ++s) tab[s] = (eff == 4 || eff == 5) ? dts[s]->plain : dts[s]->frag;
-            if (tab != h->tab_host) {
-                HIP_TRY(hipDeviceSynchronize());        // launches still in flight on any stream may read d_tab
-                HIP_TRY(hipMemcpy(h->d_tab, tab.data(), mc * sizeof(double *), hipMemcpyHostToDevice));
-                h->tab_host = tab;
-            }
-            frag_tab = h->d_tab;
-        }
-        int rc = bary_launch_specs(h, derivs + (size_t)s0 * d, dts.data(), mc, frag_tab, d_pts, (long)N, d_out, m, s0, st,
-                                   st == h->stream ? &h->s_partial : nullptr);
+        std::vector<DerivedTensor *> dts;
+        const double *const *frag_tab = nullptr;
+        int rc = bary_spec_tensors(h, derivs + (size_t)s0 * d, mc, dts, &frag_tab);
+        if (rc) return rc;
+        rc = bary_launch_specs(h, derivs + (size_t)s0 * d, dts.data(), mc, frag_tab, d_pts, (long)N, d_out, m, s0, st,
+                               st == h->stream ? &h->s_partial : nullptr);
         if (rc) return rc;
     }
     return PCX_OK;
@@ -1331,104 +1342,31 @@ static int bary_eval_host(pcx_bary *h, const double *pts, int64_t N, const int32
     if (!h) return fail(PCX_ERR_INVALID, "handle is NULL");
     if (N < 0 || m < 1) return fail(PCX_ERR_INVALID, "bad N or m");
     if (N > 0 && (!pts || !out)) return fail(PCX_ERR_INVALID, "NULL buffer");
-    if (m > kMaxSpecs) {
-        // more specs than one launch takes (the reference has no limit: a gradient plus full
-        // Hessian in 10-D is 65): groups of kMaxSpecs, each into its columns of `out`
-        if (!derivs) return fail(PCX_ERR_INVALID, "derivs is NULL");
-        const int d0 = h->dims.d;
-        std::vector<double> part;
-        for (int s0 = 0; s0 < m; s0 += kMaxSpecs) {
-            const int mc = std::min(kMaxSpecs, m - s0);
-            part.resize((size_t)N * mc);
-            int rc = bary_eval_host(h, pts, N, derivs + (size_t)s0 * d0, mc, part.data(), N_call);
-            if (rc) return rc;
-            for (int64_t i = 0; i < N; ++i)
-                memcpy(out + (size_t)i * m + s0, part.data() + (size_t)i * mc, (size_t)mc * sizeof(double));
-        }
-        return PCX_OK;
-    }
+    if (m > kMaxSpecs)
+        return eval_spec_groups(N, derivs, h->dims.d, m, out, [&](const int32_t *group, int mc, double *part) {
+            return bary_eval_host(h, pts, N, group, mc, part, N_call);
+        });
     HIP_TRY(hipSetDevice(h->device));
     std::lock_guard<std::mutex> lk(h->mu);
     h->call_mark = h->clock;
     const int d = h->dims.d;
-    std::vector<DerivedTensor *> dts(m);
-    for (int s = 0; s < m; ++s) {
-        int rc = bary_get_tensor(h, derivs ? derivs + (size_t)s * d : nullptr, &dts[s]);
-        if (rc) return rc;
-    }
-    const double *const *frag_tab = dts[0]->slot;
-    const int eff = bary_effective_variant(h);
-    if (m > 1 && (eff == 4 || eff == 5 || h->mfma_ok)) {
-        std::vector<double *> tab(m);
-        for (int s = 0; s < m; ++s) tab[s] = (eff == 4 || eff == 5) ? dts[s]->plain : dts[s]->frag;
-        if (tab != h->tab_host) {   // every earlier launch on this handle has been synchronised
-            HIP_TRY(hipMemcpy(h->d_tab, tab.data(), m * sizeof(double *), hipMemcpyHostToDevice));
-            h->tab_host = tab;
-        }
-        frag_tab = h->d_tab;
-    }
-    if (N > 0 && (size_t)N * d * sizeof(double) <= kPinnedBytes && (size_t)N * m * sizeof(double) <= kPinnedBytes &&
-        h->pin.ready()) {
-        memcpy(h->pin.in, pts, (size_t)N * d * sizeof(double));
-        int rc = bary_launch(h, dts.data(), m, frag_tab, (const double *)h->pin.in, (long)N, (double *)h->pin.out, m, 0,
-                             h->stream, &h->s_partial);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        memcpy(out, h->pin.out, (size_t)N * m * sizeof(double));
-        return PCX_OK;
-    }
-    // Two staging slots on two streams: the H2D copy of chunk i+1 and the D2H copy of chunk i-1
-    // overlap the kernel of chunk i.  A slot is reused only after its stream has drained.
+    std::vector<DerivedTensor *> dts;
+    const double *const *frag_tab = nullptr;
+    int rc = bary_spec_tensors(h, derivs, m, dts, &frag_tab);
+    if (rc) return rc;
     // pieces of 2^18 points (10 MB of 5-D coordinates); low-dimensional models take more points per piece so that a
-    // piece still moves ~10 MB (12 x 12 at 2x10^7 points: 4 MB pieces ran the path at 13 GB/s)
+    // piece still moves ~10 MB (12 x 12 at 2x10^7 points: 4 MB pieces ran the path at 13 GB/s).  Two slots from two
+    // pieces on, behind a short first piece (one round of workgroups): the first kernel starts after 2.6 MB instead of
+    // 10 MB of upload, and nothing overlaps the first upload.
     const int64_t piece = std::min<int64_t>((int64_t)1 << 21, std::max<int64_t>(kPipeChunkPoints, (((int64_t)10 << 20) / (d * 8)) & ~(int64_t)65535));
-    const bool piped = N >= 2 * piece;
-    const int64_t chunk = piped ? piece : kChunkPoints;
-    if (piped && !h->stream2)
-        HIP_TRY(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
-    // The copies queued below read and write the CALLER's arrays: whatever happens, the helper thread is joined and both
-    // streams are drained before this call returns.
-    Downloader dl(h->device);
-    auto pipeline = [&]() -> int {
-        int slot = 0;
-        // a short first piece (one round of workgroups) so that the first kernel starts after 2.6 MB instead of
-        // 10 MB of upload: nothing overlaps the first upload
-        const int64_t first_piece = piped ? (1 << 16) : chunk;
-        long piece_no = 0;
-        for (int64_t start = 0, step = first_piece; start < N; start += step, step = chunk, ++piece_no) {
-            long cnt = (long)std::min<int64_t>(step, N - start);
-            const bool second = piped && slot == 1;
-            hipStream_t st = second ? h->stream2 : h->stream;
-            Scratch &sp = second ? h->s_pts2 : h->s_pts, &so = second ? h->s_out2 : h->s_out;
-            if (piped && piece_no >= 2) dl.wait_issued(piece_no - 1);     // this slot's last download is behind its kernel
-            int rc = sp.reserve((size_t)cnt * d * sizeof(double));
-            if (rc) return rc;
-            rc = so.reserve((size_t)cnt * m * sizeof(double));
-            if (rc) return rc;
-            double *dp = (double *)sp.ptr, *dout = (double *)so.ptr;
-            HIP_TRY(hipMemcpyAsync(dp, pts + (size_t)start * d, (size_t)cnt * d * sizeof(double), hipMemcpyHostToDevice, st));
-            rc = bary_launch_specs(h, derivs, dts.data(), m, frag_tab, dp, cnt, dout, m, 0, st, second ? nullptr : &h->s_partial,
-                                   (long)N_call);
-            if (rc) return rc;
-            if (!piped) {                             // single slot: download here, drain before its buffers are reused
-                HIP_TRY(hipMemcpyAsync(out + (size_t)start * m, dout, (size_t)cnt * m * sizeof(double), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                continue;
-            }
-            dl.push(out + (size_t)start * m, dout, (size_t)cnt * m * sizeof(double), st);
-            slot ^= 1;
-        }
-        return PCX_OK;
-    };
-    const int rc_pipe = pipeline();
-    const int rc_dl = dl.finish();
-    const hipError_t e1 = hipStreamSynchronize(h->stream);
-    const hipError_t e2 = h->stream2 ? hipStreamSynchronize(h->stream2) : hipSuccess;
-    if (rc_pipe) return rc_pipe;
-    if (rc_dl) return rc_dl;
-    HIP_TRY(e1);
-    HIP_TRY(e2);
-    return PCX_OK;
+    const StagePlan plan = N >= 2 * piece ? StagePlan{1 << 16, piece, true, true} : StagePlan{kChunkPoints, kChunkPoints, false, true};
+    // every piece, the zero-copy window included, is planned with the call's N (bary_plan_groups); split launches share
+    // the handle's s_partial, so the second slot launches without it
+    return stage_host_batch(h->stage, h->device, h->stream, pts, N, d, m, out, plan,
+                            [&](int slot, hipStream_t st, const double *dp, long cnt, double *dout) {
+                                return bary_launch_specs(h, derivs, dts.data(), m, frag_tab, dp, cnt, dout, m, 0, st,
+                                                         slot ? nullptr : &h->s_partial, (long)N_call);
+                            });
 }
 
 extern "C" int pcx_bary_eval_batch(pcx_bary *h, const double *pts, int64_t N, const int32_t *deriv,
@@ -1522,8 +1460,8 @@ PCX_HIDDEN int bary_launch_small_pieces(int dout, const pcx_bary *p0, const Spli
 // is evaluated by the ordinary host-pointer path of handle g on its own host thread, its download landing in the
 // caller's `out` slice.  pin != 0 page-locks the caller's arrays for the duration of the call (hipHostRegister,
 // portable): the copies then run asynchronously at PCIe rate instead of through the driver's pageable staging.
-// A point's result does not depend on the block it lands in (for grouped multi-spec launches: as long as every
-// block stays above the 65,536-point threshold of that path).
+// A point's result does not depend on the block it lands in: every block of a grouped multi-spec launch is planned with
+// the call's N (bary_plan_groups).
 // ---------------------------------------------------------------------------------
 extern "C" int pcx_bary_group_eval_multi_batch(pcx_bary *const *handles, int n_handles, const double *pts, int64_t N,
                                                const int32_t *derivs, int m, double *out, int pin) {
@@ -1536,15 +1474,11 @@ extern "C" int pcx_bary_group_eval_multi_batch(pcx_bary *const *handles, int n_h
     }
     if (N < 0 || m < 1) return fail(PCX_ERR_INVALID, "bad N or m");
     if (N > 0 && (!pts || !out)) return fail(PCX_ERR_INVALID, "NULL buffer");
-    if (n_handles == 1 || N == 0) return bary_eval_host(handles[0], pts, N, derivs, m, out);
     const int d = handles[0]->dims.d;
-    HostPin hp;
-    HIP_TRY(hipSetDevice(handles[0]->device));
-    if (!fanout_arrays_locked(hp, pin, pts, (size_t)N * d * sizeof(double), out, (size_t)N * m * sizeof(double)))
-        return bary_eval_host(handles[0], pts, N, derivs, m, out);
-    return fan_out(n_handles, N, [&](int g, int64_t lo, int64_t cnt) {
-        return bary_eval_host(handles[g], pts + (size_t)lo * d, cnt, derivs, m, out + (size_t)lo * m, N);
-    });
+    return fan_out_host(n_handles, handles[0]->device, pin, N, pts, (size_t)N * d * sizeof(double), out,
+                        (size_t)N * m * sizeof(double), [&](int g, int64_t lo, int64_t cnt) {
+                            return bary_eval_host(handles[g], pts + (size_t)lo * d, cnt, derivs, m, out + (size_t)lo * m, N);
+                        });
     PCX_API_END
 }
 

@@ -85,16 +85,30 @@ struct pcx_bary {
     std::map<std::vector<int>, DerivedTensor> cache;
     uint64_t clock = 0;              // bumped per request; entries used since `call_mark` are never evicted
     uint64_t call_mark = 0;
-    Scratch s_pts, s_out;
-    hipStream_t stream2 = nullptr;   // second staging slot of the host-pointer pipeline (lazy)
-    Scratch s_pts2, s_out2;
+    HostStage stage;                 // host-pointer batches
     double **d_tab = nullptr;        // frag table for multi-spec launches (kMaxSpecs entries)
     std::vector<double *> tab_host;  // what d_tab currently holds
     Scratch s_partial;               // per-chunk totals of split launches
-    Pinned pin;                      // zero-copy staging for small host-pointer batches
 };
 
 static const int kMaxSpecs = 64;      // derivative specs evaluated by one launch (grid.z)
+
+// More specs than one launch takes (the reference has no limit: a gradient plus full Hessian in 10-D is 65): groups of
+// kMaxSpecs, eval(derivs of the group, mc, part) each into a host buffer of N x mc, copied into its columns of `out`.
+template <typename Fn>
+static int eval_spec_groups(int64_t N, const int32_t *derivs, int d, int m, double *out, Fn &&eval) {
+    if (!derivs) return fail(PCX_ERR_INVALID, "derivs is NULL");
+    std::vector<double> part;
+    for (int s0 = 0; s0 < m; s0 += kMaxSpecs) {
+        const int mc = std::min(kMaxSpecs, m - s0);
+        part.resize((size_t)N * mc);
+        int rc = eval(derivs + (size_t)s0 * d, mc, part.data());
+        if (rc) return rc;
+        for (int64_t i = 0; i < N; ++i)
+            memcpy(out + (size_t)i * m + s0, part.data() + (size_t)i * mc, (size_t)mc * sizeof(double));
+    }
+    return PCX_OK;
+}
 
 // pcx_bary_grid.hip
 PCX_HIDDEN bool bary_plan_grid(const BaryDims &dm, const BaryMfmaPlan &plan, BaryGridPlan &gp);
@@ -113,6 +127,8 @@ PCX_HIDDEN int bary_launch_grid(pcx_bary *h, const double *const *frag_tab, int 
 
 // pcx_bary.hip
 PCX_HIDDEN int bary_get_tensor(pcx_bary *h, const int32_t *deriv, DerivedTensor **out);
+PCX_HIDDEN int bary_spec_tensors(pcx_bary *h, const int32_t *derivs, int m, std::vector<DerivedTensor *> &dts,
+                                 const double *const **frag_tab);
 PCX_HIDDEN int bary_effective_variant(const pcx_bary *h);
 PCX_HIDDEN int bary_launch(pcx_bary *h, DerivedTensor *const *dts, int m, const double *const *frag_tab,
                            const double *d_pts, long N, double *d_out, long ostride, long ooff, hipStream_t st,

@@ -198,6 +198,90 @@ struct Downloader {
     ~Downloader() { (void)finish(); }
 };
 
+// Staging of one handle's host-pointer batches (stage_host_batch): two slots of device scratch, the second slot's stream
+// and the zero-copy window.  Guarded by the handle's mutex.
+struct HostStage {
+    hipStream_t second = nullptr;    // the second slot's stream, created on the first two-slot batch
+    Scratch pts[2], out[2];
+    Pinned pin;
+    void release() {                 // at destroy, after the handle's own stream has drained
+        if (second) { (void)hipStreamSynchronize(second); (void)hipStreamDestroy(second); second = nullptr; }
+        for (int i = 0; i < 2; ++i) { pts[i].release(); out[i].release(); }
+        pin.release();
+    }
+};
+
+// How a host-pointer batch is cut: the first piece, every later piece, whether the pieces alternate between two slots
+// (the handle's stream and HostStage::second), and whether a batch that fits kPinnedBytes takes the zero-copy window.
+struct StagePlan { int64_t first, piece; bool two_slots, zero_copy; };
+
+// N points (pts, N x d) into out (N x m) through launch(slot, stream, d_pts, cnt, d_out) -> rc, which queues the evaluation
+// of cnt device-resident points on `stream` (slot 1: the second slot's stream).  One slot: upload, launch, download and
+// drain, piece by piece.  Two slots: the upload of piece i + 1 overlaps the kernel of piece i and the download of piece
+// i - 1.  The copies read and write the CALLER's arrays: whatever happens, the Downloader is joined and both streams are
+// drained before this returns.  Caller holds the handle's mutex.
+template <typename Launch>
+static int stage_host_batch(HostStage &s, int device, hipStream_t main, const double *pts, int64_t N, int d, int m,
+                            double *out, const StagePlan &plan, Launch &&launch) {
+    const size_t in_row = (size_t)d * sizeof(double), out_row = (size_t)m * sizeof(double);
+    if (plan.zero_copy && N > 0 && N * in_row <= kPinnedBytes && N * out_row <= kPinnedBytes && s.pin.ready()) {
+        memcpy(s.pin.in, pts, N * in_row);
+        const int rc = launch(0, main, (const double *)s.pin.in, (long)N, (double *)s.pin.out);
+        const hipError_t e = hipStreamSynchronize(main);
+        if (rc) return rc;
+        HIP_TRY(e);
+        memcpy(out, s.pin.out, N * out_row);
+        return PCX_OK;
+    }
+    if (plan.two_slots && !s.second) HIP_TRY(hipStreamCreateWithFlags(&s.second, hipStreamNonBlocking));
+    Downloader dl(device);
+    auto pipeline = [&]() -> int {
+        long piece_no = 0;
+        for (int64_t start = 0, step = plan.first; start < N; start += step, step = plan.piece, ++piece_no) {
+            const long cnt = (long)std::min<int64_t>(step, N - start);
+            const int slot = plan.two_slots ? (int)(piece_no & 1) : 0;
+            hipStream_t st = slot ? s.second : main;
+            if (plan.two_slots && piece_no >= 2) dl.wait_issued(piece_no - 1);     // this slot's last download is behind its kernel
+            int rc = s.pts[slot].reserve(cnt * in_row);
+            if (rc) return rc;
+            if ((rc = s.out[slot].reserve(cnt * out_row))) return rc;
+            double *dp = (double *)s.pts[slot].ptr, *dout = (double *)s.out[slot].ptr;
+            HIP_TRY(hipMemcpyAsync(dp, pts + (size_t)start * d, cnt * in_row, hipMemcpyHostToDevice, st));
+            if ((rc = launch(slot, st, (const double *)dp, cnt, dout))) return rc;
+            if (plan.two_slots) {
+                dl.push(out + (size_t)start * m, dout, cnt * out_row, st);
+                continue;
+            }
+            HIP_TRY(hipMemcpyAsync(out + (size_t)start * m, dout, cnt * out_row, hipMemcpyDeviceToHost, st));
+            if (start + cnt < N) HIP_TRY(hipStreamSynchronize(st));    // single slot: drained before its buffers are reused
+        }
+        return PCX_OK;
+    };
+    const int rc_pipe = pipeline();
+    const int rc_dl = dl.finish();
+    const hipError_t e1 = hipStreamSynchronize(main);
+    const hipError_t e2 = s.second ? hipStreamSynchronize(s.second) : hipSuccess;
+    if (rc_pipe) return rc_pipe;
+    if (rc_dl) return rc_dl;
+    HIP_TRY(e1);
+    HIP_TRY(e2);
+    return PCX_OK;
+}
+
+// true when the runtime reports [p, p + bytes), bytes > 0, as page-locked host memory at both ends and up to 14 interior
+// points (two separate registrations could cover just the ends)
+static bool host_range_locked(const void *p, size_t bytes) {
+    bool locked = true;
+    const size_t probes = bytes > (size_t)16 ? 16 : 2;
+    for (size_t i = 0; i < probes && locked; ++i) {
+        const size_t off = i + 1 == probes ? bytes - 1 : (bytes / (probes - 1)) * i;
+        hipPointerAttribute_t at{};
+        locked = hipPointerGetAttributes(&at, (const char *)p + off) == hipSuccess && at.type == hipMemoryTypeHost;
+    }
+    (void)hipGetLastError();
+    return locked;
+}
+
 struct HostPin {
     void *a = nullptr, *b = nullptr;
     // true when [p, p + bytes) is page-locked afterwards: registered here (released by the destructor) or already
@@ -209,16 +293,7 @@ struct HostPin {
         // the GPU memory access fault of round 3 again, at a host address, in the single-handle call FOLLOWING a fan-out call
         // over the same arrays: a heap range registered, unregistered and then copied from as pageable memory.  With the
         // query in front the same soak has run clean since round 3; why that is enough is still not established.)
-        // Both ends and up to 14 interior probes (two separate registrations could cover just the ends).
-        bool locked = true;
-        const size_t probes = bytes > (size_t)16 ? 16 : 2;
-        for (size_t i = 0; i < probes && locked; ++i) {
-            const size_t off = i + 1 == probes ? bytes - 1 : (bytes / (probes - 1)) * i;
-            hipPointerAttribute_t at{};
-            locked = hipPointerGetAttributes(&at, (const char *)p + off) == hipSuccess && at.type == hipMemoryTypeHost;
-        }
-        (void)hipGetLastError();
-        if (locked) return true;
+        if (host_range_locked(p, bytes)) return true;
         if (hipHostRegister(const_cast<void *>(p), bytes, hipHostRegisterPortable) == hipSuccess) {
             *slot = const_cast<void *>(p);
             return true;
@@ -243,13 +318,7 @@ struct HostPin {
 // page-locked arrays: `pin` registers them for the call; when that is declined or fails, the whole batch goes
 // through the first handle.
 static bool fanout_arrays_locked(HostPin &hp, int pin, const void *in, size_t in_bytes, void *out, size_t out_bytes) {
-    if (!pin) {
-        hipPointerAttribute_t ai{}, ao{};
-        const bool ok = hipPointerGetAttributes(&ai, in) == hipSuccess && ai.type == hipMemoryTypeHost &&
-                        hipPointerGetAttributes(&ao, out) == hipSuccess && ao.type == hipMemoryTypeHost;
-        (void)hipGetLastError();
-        return ok;
-    }
+    if (!pin) return host_range_locked(in, in_bytes) && host_range_locked(out, out_bytes);
     const bool ok_in = hp.pin(in, in_bytes, &hp.a);
     const bool ok_out = hp.pin(out, out_bytes, &hp.b);
     static const bool log = getenv("PCX_FANOUT_LOG") != nullptr;
@@ -277,6 +346,19 @@ static int fan_out(int n_handles, int64_t N, Fn &&block_call) {
     for (int g = 0; g < n_handles; ++g)
         if (rcs[g]) return fail(rcs[g], "device block %d: %s", g, errs[g].c_str());
     return PCX_OK;
+}
+
+// The tail of the *_group_eval_* entry points, after each has validated its handles: row blocks over the handles when the
+// caller's arrays are page-locked (fanout_arrays_locked), else the whole batch through handle 0.  eval(g, lo, cnt)
+// evaluates rows [lo, lo + cnt) on handle g.
+template <typename Fn>
+static int fan_out_host(int n_handles, int device0, int pin, int64_t N, const void *in, size_t in_bytes, void *out,
+                        size_t out_bytes, Fn &&eval) {
+    if (n_handles == 1 || N == 0) return eval(0, (int64_t)0, N);
+    HostPin hp;
+    HIP_TRY(hipSetDevice(device0));
+    if (!fanout_arrays_locked(hp, pin, in, in_bytes, out, out_bytes)) return eval(0, (int64_t)0, N);
+    return fan_out(n_handles, N, eval);
 }
 
 // pcx_tt.hip: what pcx_calculus.hip reads of a tensor-train handle (its device, shape and domain by storage position,

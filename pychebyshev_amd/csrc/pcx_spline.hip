@@ -22,7 +22,8 @@ struct pcx_spline {
     hipStream_t side[kSide] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[kSide] = {nullptr, nullptr, nullptr, nullptr};
     std::mutex mu;
-    Scratch s_pts, s_out, s_piece, s_perm, s_partial;
+    HostStage stage;                     // host-pointer batches (and the points of pcx_spline_piece_ids)
+    Scratch s_piece, s_perm, s_partial;
     // one launch for all pieces (pieces of equal shape on the lane-per-point kernel): per-piece model table,
     // per-workgroup (piece, first slot) lists; staged through a pinned host buffer
     bool fused_ok = false;
@@ -38,7 +39,8 @@ extern "C" int pcx_spline_destroy(pcx_spline *h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     (void)hipFree(h->d_knots);
     (void)hipFree(h->d_counts);
-    h->s_pts.release(); h->s_out.release(); h->s_piece.release(); h->s_perm.release(); h->s_partial.release();
+    h->stage.release();
+    h->s_piece.release(); h->s_perm.release(); h->s_partial.release();
     h->s_models.release(); h->s_blk.release();
     if (h->pin_stage) (void)hipHostFree(h->pin_stage);
     for (int i = 0; i < pcx_spline::kSide; ++i) {
@@ -232,7 +234,6 @@ static int spline_launch_fused(pcx_spline *h, const double *dp, const std::vecto
 // One chunk of device-resident points through routing, bucketing and the per-piece launches, on h->stream
 // (results land in dout in point order; the launches are queued, not awaited).  Caller holds h->mu.
 static int spline_eval_chunk(pcx_spline *h, const double *dp, long cnt, const int32_t *derivs, int m, double *dout) {
-    const int d = h->sd.d;
     std::vector<int> counts, offsets;
     int rc = spline_bucket(h, dp, cnt, counts, offsets);
     if (rc) return rc;
@@ -258,23 +259,9 @@ static int spline_eval_chunk(pcx_spline *h, const double *dp, long cnt, const in
         pcx_bary *pc = h->pieces[i];
         std::lock_guard<std::mutex> plk(pc->mu);
         pc->call_mark = pc->clock;
-        std::vector<DerivedTensor *> dts(m);
-        for (int s = 0; s < m; ++s) {
-            rc = bary_get_tensor(pc, derivs ? derivs + (size_t)s * d : nullptr, &dts[s]);
-            if (rc) return rc;
-        }
-        const double *const *frag_tab = dts[0]->slot;
-        const int eff = bary_effective_variant(pc);
-        if (m > 1 && (eff == 4 || eff == 5 || pc->mfma_ok)) {
-            std::vector<double *> tab(m);
-            for (int s = 0; s < m; ++s) tab[s] = (eff == 4 || eff == 5) ? dts[s]->plain : dts[s]->frag;
-            if (tab != pc->tab_host) {
-                HIP_TRY(hipDeviceSynchronize());            // earlier launches (any stream) may still read d_tab
-                HIP_TRY(hipMemcpy(pc->d_tab, tab.data(), m * sizeof(double *), hipMemcpyHostToDevice));
-                pc->tab_host = tab;
-            }
-            frag_tab = pc->d_tab;
-        }
+        std::vector<DerivedTensor *> dts;
+        const double *const *frag_tab = nullptr;
+        if ((rc = bary_spec_tensors(pc, derivs, m, dts, &frag_tab))) return rc;
         hipStream_t st = fan ? h->side[turn % pcx_spline::kSide] : h->stream;
         ++turn;
         rc = bary_launch(pc, dts.data(), m, frag_tab, dp, counts[i], dout, m, 0, st, fan ? nullptr : &h->s_partial,
@@ -294,36 +281,17 @@ static int spline_eval_host(pcx_spline *h, const double *pts, int64_t N, const i
     if (!h) return fail(PCX_ERR_INVALID, "handle is NULL");
     if (N < 0 || m < 1) return fail(PCX_ERR_INVALID, "bad N or m");
     if (N > 0 && (!pts || !out)) return fail(PCX_ERR_INVALID, "NULL buffer");
-    if (m > kMaxSpecs) {      // groups of kMaxSpecs specs, each into its columns of `out`
-        if (!derivs) return fail(PCX_ERR_INVALID, "derivs is NULL");
-        std::vector<double> part;
-        for (int s0 = 0; s0 < m; s0 += kMaxSpecs) {
-            const int mc = std::min(kMaxSpecs, m - s0);
-            part.resize((size_t)N * mc);
-            int rc = spline_eval_host(h, pts, N, derivs + (size_t)s0 * h->sd.d, mc, part.data());
-            if (rc) return rc;
-            for (int64_t i = 0; i < N; ++i)
-                memcpy(out + (size_t)i * m + s0, part.data() + (size_t)i * mc, (size_t)mc * sizeof(double));
-        }
-        return PCX_OK;
-    }
+    if (m > kMaxSpecs)
+        return eval_spec_groups(N, derivs, h->sd.d, m, out, [&](const int32_t *group, int mc, double *part) {
+            return spline_eval_host(h, pts, N, group, mc, part);
+        });
     HIP_TRY(hipSetDevice(h->device));
     std::lock_guard<std::mutex> lk(h->mu);
-    const int d = h->sd.d;
-    for (int64_t start = 0; start < N; start += kChunkPoints) {
-        long cnt = (long)std::min<int64_t>(kChunkPoints, N - start);
-        int rc = h->s_pts.reserve((size_t)cnt * d * sizeof(double));
-        if (rc) return rc;
-        rc = h->s_out.reserve((size_t)cnt * m * sizeof(double));
-        if (rc) return rc;
-        double *dp = (double *)h->s_pts.ptr, *dout = (double *)h->s_out.ptr;
-        HIP_TRY(hipMemcpyAsync(dp, pts + (size_t)start * d, (size_t)cnt * d * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        rc = spline_eval_chunk(h, dp, cnt, derivs, m, dout);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(out + (size_t)start * m, dout, (size_t)cnt * m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    return PCX_OK;
+    return stage_host_batch(h->stage, h->device, h->stream, pts, N, h->sd.d, m, out,
+                            StagePlan{kChunkPoints, kChunkPoints, false, false},
+                            [&](int, hipStream_t, const double *dp, long cnt, double *dout) {
+                                return spline_eval_chunk(h, dp, cnt, derivs, m, dout);
+                            });
 }
 
 // Device-resident points and results (d_pts N x d, d_out N x m, both on the handle's device).  Routing needs
@@ -403,11 +371,12 @@ extern "C" int pcx_spline_piece_ids(pcx_spline *h, const double *pts, int64_t N,
     HIP_TRY(hipSetDevice(h->device));
     std::lock_guard<std::mutex> lk(h->mu);
     const int d = h->sd.d;
-    int rc = h->s_pts.reserve((size_t)N * d * sizeof(double));
+    Scratch &sp = h->stage.pts[0];
+    int rc = sp.reserve((size_t)N * d * sizeof(double));
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(h->s_pts.ptr, pts, (size_t)N * d * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(sp.ptr, pts, (size_t)N * d * sizeof(double), hipMemcpyHostToDevice, h->stream));
     std::vector<int> counts, offsets;
-    rc = spline_bucket(h, (const double *)h->s_pts.ptr, (long)N, counts, offsets);
+    rc = spline_bucket(h, (const double *)sp.ptr, (long)N, counts, offsets);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(ids_out, h->s_piece.ptr, (size_t)N * sizeof(int), hipMemcpyDeviceToHost));
     return PCX_OK;
@@ -427,7 +396,8 @@ struct pcx_slider {
     std::vector<int> owner;              // dimension -> slide
     int max_cols = 1;
     std::mutex mu;
-    Scratch s_pts, s_out, s_cols, s_vals, s_partial;
+    HostStage stage;                     // host-pointer batches
+    Scratch s_cols, s_vals, s_partial;
 };
 
 extern "C" int pcx_slider_destroy(pcx_slider *h) {
@@ -435,7 +405,8 @@ extern "C" int pcx_slider_destroy(pcx_slider *h) {
     if (!h) return PCX_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->s_pts.release(); h->s_out.release(); h->s_cols.release(); h->s_vals.release(); h->s_partial.release();
+    h->stage.release();
+    h->s_cols.release(); h->s_vals.release(); h->s_partial.release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return PCX_OK;
@@ -560,20 +531,10 @@ extern "C" int pcx_slider_eval_multi_batch(pcx_slider *h, const double *pts, int
     HIP_TRY(hipSetDevice(h->device));
     std::lock_guard<std::mutex> lk(h->mu);
     const int64_t chunk = std::max<int64_t>(1, kChunkPoints / std::max(1, m));
-    for (int64_t start = 0; start < N; start += chunk) {
-        const long cnt = (long)std::min<int64_t>(chunk, N - start);
-        int rc = h->s_pts.reserve((size_t)cnt * h->d * sizeof(double));
-        if (rc) return rc;
-        rc = h->s_out.reserve((size_t)cnt * m * sizeof(double));
-        if (rc) return rc;
-        double *dp = (double *)h->s_pts.ptr, *dout = (double *)h->s_out.ptr;
-        HIP_TRY(hipMemcpyAsync(dp, pts + (size_t)start * h->d, (size_t)cnt * h->d * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        rc = slider_eval_chunk(h, dp, cnt, derivs, m, dout);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(out + (size_t)start * m, dout, (size_t)cnt * m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    return PCX_OK;
+    return stage_host_batch(h->stage, h->device, h->stream, pts, N, h->d, m, out, StagePlan{chunk, chunk, false, false},
+                            [&](int, hipStream_t, const double *dp, long cnt, double *dout) {
+                                return slider_eval_chunk(h, dp, cnt, derivs, m, dout);
+                            });
     PCX_API_END
 }
 

@@ -41,10 +41,7 @@ struct pcx_tt {
     TTGeneric gi;
     double *d_cores = nullptr;
     std::mutex mu;
-    Scratch s_pts, s_out;
-    hipStream_t stream2 = nullptr;   // second staging slot of the host-pointer pipeline (lazy)
-    Scratch s_pts2, s_out2;
-    Pinned pin;           // zero-copy staging for small host-pointer batches
+    HostStage stage;      // host-pointer batches
     Scratch s_fd_batch, s_fd_vals;   // finite-difference stencil batch and its values (models off the lane-per-point kernel)
 };
 
@@ -60,11 +57,8 @@ extern "C" int pcx_tt_destroy(pcx_tt *h) {
     (void)hipFree(h->d_lpp_img);
     (void)hipFree(h->d_lpp_tab);
     (void)hipFree(h->d_cores);
-    h->s_pts.release(); h->s_out.release();
-    h->s_pts2.release(); h->s_out2.release();
+    h->stage.release();
     h->s_fd_batch.release(); h->s_fd_vals.release();
-    h->pin.release();
-    if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return PCX_OK;
@@ -458,17 +452,9 @@ extern "C" int pcx_tt_eval_batch(pcx_tt *h, const double *pts, int64_t N, double
     HIP_TRY(hipSetDevice(h->device));
     std::lock_guard<std::mutex> lk(h->mu);
     const int d = h->dims.d;
-    if (N > 0 && (size_t)N * d * sizeof(double) <= kPinnedBytes && h->pin.ready()) {
-        memcpy(h->pin.in, pts, (size_t)N * d * sizeof(double));
-        int rc = tt_launch(h, (const double *)h->pin.in, (long)N, (double *)h->pin.out, h->stream);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        memcpy(out, h->pin.out, (size_t)N * sizeof(double));
-        return PCX_OK;
-    }
     // The path is transfer-bound (48 .. 88 bytes per point against ~0.1 ns of kernel): pieces of ~10 MB of coordinates alternate
     // between two staging slots on two streams, so the upload of piece i+1 runs while piece i is evaluated and piece
-    // i-1 is downloaded (both PCIe directions busy; the downloads are issued by a helper thread, see Downloader).  From page-locked caller memory (pcx_host_register, or the `pin`
+    // i-1 is downloaded (both PCIe directions busy; the downloads are issued by a helper thread, see stage_host_batch).  From page-locked caller memory (pcx_host_register, or the `pin`
     // flag of pcx_tt_group_eval_batch) the copies are asynchronous DMA; from pageable memory the driver stages them.
     // ~10 MB of coordinates per piece for batches of a few pieces (N = 10^6: 1.08 -> 1.00 ms), up to ~40 MB for long ones
     // (N = 10^7: 8.9 ms with 40 MB pieces against 9.4 ms with 10 MB pieces)
@@ -476,44 +462,10 @@ extern "C" int pcx_tt_eval_batch(pcx_tt *h, const double *pts, int64_t N, double
     const int64_t kTTPipePoints = std::min<int64_t>(4 * piece_lo, std::max<int64_t>(piece_lo, (N / 8) & ~(int64_t)65535));
     const bool piped = N >= 2 * kTTPipePoints;
     const int64_t chunk = piped ? kTTPipePoints : kChunkPoints;
-    if (piped && !h->stream2) HIP_TRY(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
-    // the copies queued below read and write the CALLER's arrays: whatever happens, the helper thread (Downloader) is
-    // joined and both streams are drained before this call returns
-    Downloader dl(h->device);
-    auto pipeline = [&]() -> int {
-        int slot = 0;
-        long piece_no = 0;
-        for (int64_t start = 0; start < N; start += chunk, ++piece_no) {
-            long cnt = (long)std::min<int64_t>(chunk, N - start);
-            const bool second = piped && slot == 1;
-            hipStream_t st = second ? h->stream2 : h->stream;
-            Scratch &sp = second ? h->s_pts2 : h->s_pts, &so = second ? h->s_out2 : h->s_out;
-            if (piped && piece_no >= 2) dl.wait_issued(piece_no - 1);     // this slot's last download is behind its kernel
-            int rc = sp.reserve((size_t)cnt * d * sizeof(double));
-            if (rc) return rc;
-            if ((rc = so.reserve((size_t)cnt * sizeof(double)))) return rc;
-            HIP_TRY(hipMemcpyAsync(sp.ptr, pts + (size_t)start * d, (size_t)cnt * d * sizeof(double), hipMemcpyHostToDevice, st));
-            rc = tt_launch(h, (const double *)sp.ptr, cnt, (double *)so.ptr, st);
-            if (rc) return rc;
-            if (!piped) {                           // single slot: download here, drain before its buffers are reused
-                HIP_TRY(hipMemcpyAsync(out + start, so.ptr, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                continue;
-            }
-            dl.push(out + start, so.ptr, (size_t)cnt * sizeof(double), st);
-            slot ^= 1;
-        }
-        return PCX_OK;
-    };
-    const int rc_pipe = pipeline();
-    const int rc_dl = dl.finish();
-    const hipError_t e1 = hipStreamSynchronize(h->stream);
-    const hipError_t e2 = h->stream2 ? hipStreamSynchronize(h->stream2) : hipSuccess;
-    if (rc_pipe) return rc_pipe;
-    if (rc_dl) return rc_dl;
-    HIP_TRY(e1);
-    HIP_TRY(e2);
-    return PCX_OK;
+    return stage_host_batch(h->stage, h->device, h->stream, pts, N, d, 1, out, StagePlan{chunk, chunk, piped, true},
+                            [&](int, hipStream_t st, const double *dp, long cnt, double *dout) {
+                                return tt_launch(h, dp, cnt, dout, st);
+                            });
     PCX_API_END
 }
 
@@ -643,45 +595,14 @@ extern "C" int pcx_tt_eval_multi_batch(pcx_tt *h, const double *pts, int64_t N, 
     std::vector<TTFdSpec> specs;
     int rc = tt_fd_plan(h, derivs, m, specs);
     if (rc) return rc;
-    const int d = h->dims.d;
-    if (N > 0 && (size_t)N * d * sizeof(double) <= kPinnedBytes && (size_t)N * m * sizeof(double) <= kPinnedBytes && h->pin.ready()) {
-        memcpy(h->pin.in, pts, (size_t)N * d * sizeof(double));
-        rc = tt_fd_launch(h, (const double *)h->pin.in, (long)N, specs, (double *)h->pin.out, m, h->stream);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        memcpy(out, h->pin.out, (size_t)N * m * sizeof(double));
-        return PCX_OK;
-    }
     // pieces of 2^18 points alternate between the two staging slots: the upload of piece i + 1 overlaps the kernel of
     // piece i (8 m bytes per point come back against 8 d going in; the kernel is (stencil points) chains per point)
     const int64_t chunk = 1 << 18;
     const bool two = N > chunk && tt_runs_lpp(h);        // the generic path's scratch is single
-    if (two && !h->stream2) HIP_TRY(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
-    auto pipeline = [&]() -> int {
-        int slot = 0;
-        for (int64_t start = 0; start < N; start += chunk, slot ^= 1) {
-            const long cnt = (long)std::min<int64_t>(chunk, N - start);
-            const bool second = two && slot == 1;
-            hipStream_t st = second ? h->stream2 : h->stream;
-            Scratch &sp = second ? h->s_pts2 : h->s_pts, &so = second ? h->s_out2 : h->s_out;
-            HIP_TRY(hipStreamSynchronize(st));                       // the slot's previous download has left its buffer
-            int rc2 = sp.reserve((size_t)cnt * d * sizeof(double));
-            if (rc2) return rc2;
-            if ((rc2 = so.reserve((size_t)cnt * m * sizeof(double)))) return rc2;
-            HIP_TRY(hipMemcpyAsync(sp.ptr, pts + (size_t)start * d, (size_t)cnt * d * sizeof(double), hipMemcpyHostToDevice, st));
-            rc2 = tt_fd_launch(h, (const double *)sp.ptr, cnt, specs, (double *)so.ptr, m, st);
-            if (rc2) return rc2;
-            HIP_TRY(hipMemcpyAsync(out + (size_t)start * m, so.ptr, (size_t)cnt * m * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
-        return PCX_OK;
-    };
-    const int rc_pipe = pipeline();
-    const hipError_t e1 = hipStreamSynchronize(h->stream);
-    const hipError_t e2 = h->stream2 ? hipStreamSynchronize(h->stream2) : hipSuccess;
-    if (rc_pipe) return rc_pipe;
-    HIP_TRY(e1);
-    HIP_TRY(e2);
-    return PCX_OK;
+    return stage_host_batch(h->stage, h->device, h->stream, pts, N, h->dims.d, m, out, StagePlan{chunk, chunk, two, true},
+                            [&](int, hipStream_t st, const double *dp, long cnt, double *dout) {
+                                return tt_fd_launch(h, dp, cnt, specs, dout, m, st);
+                            });
     PCX_API_END
 }
 
@@ -695,15 +616,9 @@ extern "C" int pcx_tt_group_eval_batch(pcx_tt *const *handles, int n_handles, co
     }
     if (N < 0) return fail(PCX_ERR_INVALID, "N < 0");
     if (N > 0 && (!pts || !out)) return fail(PCX_ERR_INVALID, "NULL buffer");
-    if (n_handles == 1 || N == 0) return pcx_tt_eval_batch(handles[0], pts, N, out);
     const int d = handles[0]->dims.d;
-    HostPin hp;
-    HIP_TRY(hipSetDevice(handles[0]->device));
-    if (!fanout_arrays_locked(hp, pin, pts, (size_t)N * d * sizeof(double), out, (size_t)N * sizeof(double)))
-        return pcx_tt_eval_batch(handles[0], pts, N, out);
-    return fan_out(n_handles, N, [&](int g, int64_t lo, int64_t cnt) {
-        return pcx_tt_eval_batch(handles[g], pts + (size_t)lo * d, cnt, out + lo);
-    });
+    return fan_out_host(n_handles, handles[0]->device, pin, N, pts, (size_t)N * d * sizeof(double), out, (size_t)N * sizeof(double),
+                        [&](int g, int64_t lo, int64_t cnt) { return pcx_tt_eval_batch(handles[g], pts + (size_t)lo * d, cnt, out + lo); });
     PCX_API_END
 }
 

@@ -931,7 +931,7 @@ _PAGE_LOCKED_FOR_GOOD = []        # arrays registered with pcx_host_register and
 def test_single_process_fan_out_over_device_handles(bs5d):
     """one process, several device handles -- contiguous row blocks, one host thread per handle, every
     download into its slice of the caller's array (pcx_bary_group_eval_multi_batch).  One GPU here: device 0 listed
-    twice and three times; results equal the single-handle call bit for bit (ragged N, value and multi-spec)."""
+    twice, three and seven times; results equal the single-handle call bit for bit (ragged N, value and multi-spec)."""
     c, g = bs5d
     N = 400_003
     pts = F.bs5_query_points(N, seed=17)
@@ -958,6 +958,17 @@ def test_single_process_fan_out_over_device_handles(bs5d):
     assert m.lib.pcx_bary_group_eval_multi_batch(harr2, 2, _lib.p_f64(pl_pts), N, _lib.p_i32(_lib.i32([0] * 5)), 1,
                                                  _lib.p_f64(pl_out), 0) == 0
     assert np.array_equal(pl_out, y1)
+    # seven handles, blocks of 10,000 rows: each inside the zero-copy window, and still planned (grouped columns) with the
+    # call's 70,000 rows, as the single-handle call is
+    n7, six = 70_000, F.GREEK_SPECS_5D[:6]
+    pl_out7 = np.empty((n7, len(six)))
+    _PAGE_LOCKED_FOR_GOOD.append(pl_out7)
+    assert m.lib.pcx_host_register(m.device, pl_out7.ctypes.data_as(ctypes.c_void_p), pl_out7.nbytes) == 0
+    seven = ChebyshevApproximation.from_values(g["tensor"], 5, F.BS5_DOMAIN, F.BS5_NODES).to_device(devices=[0] * 7)
+    harr7, keep7 = _lib.handle_array([gm.handle for gm in seven._fanout])
+    assert m.lib.pcx_bary_group_eval_multi_batch(harr7, 7, _lib.p_f64(pl_pts), n7, _lib.p_i32(_lib.i32(six)), len(six),
+                                                 _lib.p_f64(pl_out7), 0) == 0
+    assert np.array_equal(pl_out7, one.vectorized_eval_multi_batch(pts[:n7], six))
     # the C ABI refuses a group of different models and reports a failing block with its index
     other = ChebyshevApproximation.from_values(np.ones((3, 3)), 2, [[0, 1], [0, 1]], [3, 3]).to_device(0)._model()
     harr, keep = _lib.handle_array([m.handle, other.handle])

@@ -56,6 +56,12 @@ def test_device_array_round_trip_and_protocol():
         d.__cuda_array_interface__
 
 
+# batch sizes at the switches of the host-pointer staging for 5-D models: empty, one row, the zero-copy window's last row
+# and the first past it (up to five result columns, six columns), the switch to two slots (2^19) and a ragged last piece
+_LAST_SWITCH = (1 << 19) + (1 << 16) + 1
+_STAGING_SWITCHES = (0, 1, 13_107, 13_108, 10_922, 10_923, (1 << 19) - 1, 1 << 19, _LAST_SWITCH)
+
+
 def test_barycentric_device_batches():
     g = golden("g2_bs5d")
     cheb = ChebyshevApproximation.from_values(g["tensor"], 5, F.BS5_DOMAIN, [11] * 5)
@@ -82,6 +88,15 @@ def test_barycentric_device_batches():
     assert cheb.vectorized_eval_batch(DeviceArray.empty((0, 5)), [0] * 5).shape == (0,)
     with pytest.raises(ValueError, match="shape"):
         cheb.vectorized_eval_batch(DeviceArray.from_host(p2), [0] * 5)
+    # at every switch of the host-pointer staging, with up to five and with six specs
+    six = F.GREEK_SPECS_5D[:6]
+    big = np.column_stack([rng.uniform(lo, hi, _LAST_SWITCH) for lo, hi in F.BS5_DOMAIN])
+    for n in _STAGING_SWITCHES:
+        dn = DeviceArray.from_host(big[:n])
+        assert np.array_equal(cheb.vectorized_eval_batch(dn, [0] * 5).to_host(), cheb.vectorized_eval_batch(big[:n], [0] * 5)), n
+        for sp in (specs, six):
+            assert np.array_equal(cheb.vectorized_eval_multi_batch(dn, sp).to_host(), cheb.vectorized_eval_multi_batch(big[:n], sp)), n
+        dn.free()
 
 
 def test_tt_spline_slider_device_batches():
@@ -114,6 +129,13 @@ def test_tt_spline_slider_device_batches():
     assert isinstance(got, DeviceArray) and got.shape == (30_001,)
     assert np.array_equal(got.to_host(), sl.eval_batch(pts, [0] * 5))
     assert np.array_equal(sl.eval_multi_batch(dpts, sc["specs"]).to_host(), sl.eval_multi_batch(pts, sc["specs"]))
+    # the 5-D models at every switch of the host-pointer staging
+    big = np.column_stack([rng.uniform(lo, hi, _LAST_SWITCH) for lo, hi in F.BS5_DOMAIN])
+    for n in _STAGING_SWITCHES:
+        dn = DeviceArray.from_host(big[:n])
+        assert np.array_equal(tt.eval_batch(dn).to_host(), tt.eval_batch(big[:n])), n
+        assert np.array_equal(sl.eval_multi_batch(dn, sc["specs"]).to_host(), sl.eval_multi_batch(big[:n], sc["specs"])), n
+        dn.free()
 
 
 def test_torch_tensors_in_and_out():

@@ -535,12 +535,12 @@ def test_eval_multi_batch_equals_eval_multi_row_by_row():
     assert np.array_equal(tt._eval_multi_batch_host(pts, specs, chunk=64), got)
     assert np.array_equal(got[:, 0], tt.eval_batch(pts))
     assert np.array_equal(tt.eval_multi_batch(DeviceArray.from_host(pts), specs).to_host(), got)
-    # 17 specs: two launches of the spec pack; a batch past the zero-copy window and past one pipeline piece
+    # 17 specs: two launches of the spec pack; batches past the zero-copy window, of exactly one pipeline piece and past it
     many = specs + specs[1:8]
-    big = np.tile(pts, (1000, 1))[: (1 << 18) + 777]
-    gm = tt.eval_multi_batch(big, many)
-    assert np.array_equal(gm[:300, :10], got) and np.array_equal(gm[:300, 10:], got[:, 1:8])
-    assert np.array_equal(gm[300:600], gm[:300])
+    for n in ((1 << 18), (1 << 18) + 777):
+        gm = tt.eval_multi_batch(np.tile(pts, (1000, 1))[:n], many)
+        assert np.array_equal(gm[:300, :10], got) and np.array_equal(gm[:300, 10:], got[:, 1:8]), n
+        assert np.array_equal(gm[300:600], gm[:300]) and np.array_equal(gm[-1], gm[(n - 1) % 300]), n
     fd = np.array([tt.eval_multi(list(s), g["fd_specs"].tolist()) for s in g["scenarios"]])
     assert np.array_equal(tt.eval_multi_batch(g["scenarios"], g["fd_specs"].tolist()), fd)
     with pytest.raises(ValueError, match="not supported"):
