@@ -280,6 +280,17 @@ int pcx_tt_eval_multi_batch(pcx_tt *h, const double *pts, int64_t N, const int32
 int pcx_tt_eval_multi_batch_dev(pcx_tt *h, const double *d_pts, int64_t N, const int32_t *derivs, int m, double *d_out,
                                 void *stream);
 int pcx_tt_stream(pcx_tt *h, void **stream);
+/* Box integrals, batched (the reference's integrate(dims, bounds) then eval(point), tensor_train.py:1505-1702, one row
+ * per call there): out[r] = integral of the model over [lo, hi] in every integrated dimension of row r, at the row's
+ * coordinates in the kept ones.  integrated = d flags (0 or 1; anything else is PCX_ERR_INVALID) in the USER's dimension
+ * order.  rows is N x (d + m) row-major, m = number of flags set: for user dimensions 0 .. d-1 in order one double (the
+ * coordinate) for a kept dimension, two (lo, hi) for an integrated one.  m = 0 is the value, as pcx_tt_eval_batch.  A row
+ * with lo == hi gives exactly 0.  The domain is not checked.  N = 0 returns PCX_OK without a launch.  Models with a
+ * lane-per-point image (ranks <= 16, n <= 16) run one row per lane, every other model one row per wave on the plain
+ * cores. */
+int pcx_tt_box_batch(pcx_tt *h, const int32_t *integrated, const double *rows, int64_t N, double *out);
+int pcx_tt_box_batch_dev(pcx_tt *h, const int32_t *integrated, const double *d_rows, int64_t N, double *d_out,
+                         void *stream);
 /* Kernel selection: 0 = auto, 1 = direct form on v_mfma_f64_16x16x4 (one GEMM over (node, left
  * rank) per dimension; ranks <= 64), 2 = small-rank "W first" form (ranks <= 12, cores in LDS),
  * 3 = small-rank direct form on v_mfma_f64_4x4x4_4b (ranks <= 12, n <= 16, cores in LDS),

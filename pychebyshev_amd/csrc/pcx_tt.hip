@@ -39,7 +39,11 @@ struct pcx_tt {
     int variant = 0;      // 0 auto, 1 direct form (16x16x4), 2 W-first form, 3 direct form (4x4x4), 4 lane per point
     bool generic = false; // ranks > 64: wave-per-point kernel on the plain cores
     TTGeneric gi;
-    double *d_cores = nullptr;
+    double *d_cores = nullptr;   // plain cores: the generic kernel's, and the box-integral kernel's of every model without a lane-per-point image
+    int ranks[PCX_MAX_DIMS + 1] = {1};
+    long coff[PCX_MAX_DIMS] = {0};
+    int nmax = 1;
+    double *d_rinv = nullptr;    // 1 / j, j = 1 .. nmax + 1, for the wave-per-row box kernel (uploaded on its first launch)
     std::mutex mu;
     HostStage stage;      // host-pointer batches
     Scratch s_fd_batch, s_fd_vals;   // finite-difference stencil batch and its values (models off the lane-per-point kernel)
@@ -57,6 +61,7 @@ extern "C" int pcx_tt_destroy(pcx_tt *h) {
     (void)hipFree(h->d_lpp_img);
     (void)hipFree(h->d_lpp_tab);
     (void)hipFree(h->d_cores);
+    (void)hipFree(h->d_rinv);
     h->stage.release();
     h->s_fd_batch.release(); h->s_fd_vals.release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -96,6 +101,10 @@ extern "C" int pcx_tt_create(int device, int d, const int32_t *n_nodes, const in
         h->dims.scale[k] = 2.0 / (hi[k] - lo[k]);
         coff[k] = core_total;
         core_total += (long)ranks[k] * n_nodes[k] * ranks[k + 1];
+        h->coff[k] = coff[k];
+        h->ranks[k] = ranks[k];
+        h->ranks[k + 1] = ranks[k + 1];
+        h->nmax = std::max(h->nmax, (int)n_nodes[k]);
         h->rmax = std::max(h->rmax, std::max(ranks[k], ranks[k + 1]));
     }
     if (h->rmax > 64) {
@@ -295,7 +304,8 @@ extern "C" int pcx_tt_create(int device, int d, const int32_t *n_nodes, const in
     }
     hipError_t e1 = hipGetLastError();
     hipError_t e2 = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_cores);
+    if (h->lppCap) (void)hipFree(d_cores);
+    else h->d_cores = d_cores;          // pcx_tt_box_batch walks the plain cores of such a model
     CREATE_TRY(e1);
     CREATE_TRY(e2);
 #undef CREATE_TRY
@@ -641,6 +651,26 @@ int tt_handle_view(pcx_tt *h, int *device, TTDims *dims, hipStream_t *stream) {
     *device = h->device;
     *dims = h->dims;
     *stream = h->stream;
+    return PCX_OK;
+}
+
+int tt_box_view(pcx_tt *h, TTBoxView *v) {
+    if (!h) return fail(PCX_ERR_INVALID, "handle is NULL");
+    v->device = h->device;
+    v->stream = h->stream;
+    v->dims = &h->dims;
+    v->ranks = h->ranks;
+    v->coff = h->coff;
+    v->rmax = h->rmax;
+    v->nmax = h->nmax;
+    v->lppCap = h->lppCap;
+    v->lpp_nodes = h->lpp_nodes;
+    v->d_lpp_img = h->d_lpp_img;
+    v->d_lpp_tab = h->d_lpp_tab;
+    v->d_cores = h->d_cores;
+    v->d_rinv = &h->d_rinv;
+    v->mu = &h->mu;
+    v->stage = &h->stage;
     return PCX_OK;
 }
 

@@ -23,8 +23,13 @@ is always a ``pcx_tt_eval_batch`` launch; there is no CPU fallback.
 ``+`` / ``-`` stack the cores block-diagonally and round them back on the device (``pcx_tt_round``);
 ``reorder`` runs its adjacent swaps on the device (``pcx_tt_reorder``); scalars scale core 0 on the host.
 
-Out of scope in this tier (raise ``NotImplementedError``): ``method='als'``
-builders, slicing, extrusion.
+``slice`` / ``extrude`` / ``integrate`` / ``inner_product`` contract the coefficient cores on the host (NumPy: a few
+``einsum`` calls over cores of a few kilobytes).  ``integrate_batch`` -- the integral over a box that differs per row, at
+the row's coordinates in the kept dimensions -- is one launch of the TT chain with the antiderivative basis in the
+integrated dimensions (``pcx_tt_box_batch``, ``csrc/tt_box_kernels.h``).
+
+Out of scope in this tier: the ``method='als'`` builder (raises ``NotImplementedError``), ``run_completion``,
+``orth_left`` / ``orth_right`` and ``with_auto_order``.
 """
 from __future__ import annotations
 
@@ -104,6 +109,81 @@ def _tt_grid_values(cores: Sequence[np.ndarray], idx: np.ndarray) -> np.ndarray:
     _lib.check(lib.pcx_tt_grid_eval(_device(), d, _lib.p_i32(n), _lib.p_i32(ranks), _lib.p_f64(cat),
                                     _lib.p_i32(ii), ii.shape[0], _lib.p_f64(out)), lib)
     return out
+
+
+def _coeff_core_to_value_core(coeff_core: np.ndarray) -> np.ndarray:
+    """Chebyshev coefficients along axis 1 -> values at the type-I nodes in ascending order: the inverse of
+    :func:`_value_core_to_coeff_core` (reference tensor_train.py:1019-1043, an inverse DCT there).  Host NumPy:
+    ``value[:, i, :] = sum_j T_j(x_i) coeff[:, j, :]`` with ``T_j(x_i) = cos(j theta_i)`` -- the cores are small."""
+    c = np.asarray(coeff_core, dtype=float)
+    n = c.shape[1]
+    theta = np.pi * (2.0 * np.arange(n - 1, -1, -1) + 1.0) / (2.0 * n)      # ascending nodes x_i = cos(theta_i)
+    basis = np.cos(np.outer(theta, np.arange(n)))
+    return np.einsum("ij,rjs->ris", basis, c)
+
+
+def _entry_list(params, arity: int) -> list:
+    """A ``slice`` (arity 2: ``(dim, value)``) or ``extrude`` (arity 3: ``(dim, (lo, hi), n_nodes)``) argument as a list
+    of tuples: one entry may come alone."""
+    alone = isinstance(params, tuple) and len(params) == arity and isinstance(params[0], (int, np.integer))
+    return [tuple(params)] if alone else [tuple(entry) for entry in params]
+
+
+def _checked_entries(entries: list, arity: int, upper: int) -> list:
+    """The entries of :func:`_entry_list`, validated.  Every entry leads with a dimension index, an integer in
+    ``[0, upper)`` that no other entry repeats; an extrude entry also needs ``lo < hi`` and an integer ``n_nodes >= 2``.
+    The checks run over all entries at once; what is reported is the first entry that fails anything and, within it,
+    type before range before repetition before bounds before node count -- the order a caller of the reference sees
+    (_extrude_slice.py:9-63), with its messages."""
+    count = len(entries)
+    if count == 0:
+        return entries
+    heads = [entry[0] for entry in entries]
+    is_index = np.fromiter((isinstance(h, (int, np.integer)) for h in heads), dtype=bool, count=count)
+    index = np.array([int(h) if ok else -1 for h, ok in zip(heads, is_index)], dtype=np.int64)
+    outside = (index < 0) | (index >= upper)
+    first_use = np.unique(index, return_index=True)[1]
+    repeats = np.ones(count, dtype=bool)
+    repeats[first_use] = False                                   # True where an earlier entry has the same index
+    failures = [(~is_index, TypeError, lambda e: f"dim_index must be int, got {type(e[0]).__name__}"),
+                (outside, ValueError, lambda e: f"dim_index {e[0]} out of range [0, {upper - 1}]"),
+                (repeats, ValueError, lambda e: f"Duplicate dim_index {e[0]}")]
+    if arity == 3:
+        empty = np.fromiter((not entry[1][0] < entry[1][1] for entry in entries), dtype=bool, count=count)
+        few = np.fromiter((not isinstance(entry[2], (int, np.integer)) or entry[2] < 2 for entry in entries),
+                          dtype=bool, count=count)
+        failures += [(empty, ValueError, lambda e: f"Domain bounds must satisfy lo < hi, got [{e[1][0]}, {e[1][1]}]"),
+                     (few, ValueError, lambda e: f"n_nodes must be int >= 2, got {e[2]}")]
+    failed = np.logical_or.reduce([mask for mask, _, _ in failures])
+    if failed.any():
+        at = int(np.argmax(failed))
+        for mask, kind, text in failures:
+            if mask[at]:
+                raise kind(text(entries[at]))
+    return [(int(entry[0]),) + entry[1:] for entry in entries]
+
+
+def _slice_params(params, ndim: int) -> list:
+    """``(dim, value)`` pairs of a ``slice`` call; at least one dimension has to stay."""
+    entries = _entry_list(params, 2)
+    if len(entries) >= ndim:
+        raise ValueError(f"Cannot slice all {ndim} dimensions (would produce 0D result)")
+    return _checked_entries(entries, 2, ndim)
+
+
+def _extrude_params(params, ndim: int) -> list:
+    """``(dim, (lo, hi), n_nodes)`` triples of an ``extrude`` call, ascending by the index each takes in the result."""
+    entries = _entry_list(params, 3)
+    entries = _checked_entries(entries, 3, ndim + len(entries))
+    return sorted(((k, (b[0], b[1]), int(n)) for k, b, n in entries), key=lambda entry: entry[0])
+
+
+def _renumbered(kept_user_dims: Sequence[int], ndim: int, removed) -> List[int]:
+    """``dim_order`` of a result that lost the user dimensions ``removed``: the surviving user dimensions, listed by
+    storage position in ``kept_user_dims``, renumbered 0 .. in increasing order (reference :1664-1679, :2093-2104)."""
+    survivors = [u for u in range(ndim) if u not in removed]
+    new_index = {u: i for i, u in enumerate(survivors)}
+    return [new_index[u] for u in kept_user_dims]
 
 
 def _sobol_from_coeff_cores(cores: Sequence[np.ndarray]):
@@ -994,7 +1074,7 @@ class ChebyshevTT(ErgonomicsMixin):
     def _derived(self, cores, *, max_rank=None, domain=None, n_nodes=None, dim_order=None) -> "ChebyshevTT":
         obj = self.__class__.__new__(self.__class__)
         obj.function = None
-        obj.num_dimensions = self.num_dimensions
+        obj.num_dimensions = len(cores)
         obj.domain = list(self.domain if domain is None else domain)
         obj.n_nodes = list(self.n_nodes if n_nodes is None else n_nodes)
         obj.max_rank = self.max_rank if max_rank is None else max_rank
@@ -1111,6 +1191,237 @@ class ChebyshevTT(ErgonomicsMixin):
         dev = _lib.default_device() if self._device_index is None else self._device_index
         cores = _algebra.tt_swaps(self._coeff_cores, swaps, eff_rank, eff_tol, dev)
         return self._derived(cores, domain=domain, n_nodes=n_nodes, dim_order=new_order)
+
+    # ---------------------------------------------------------------- slice / extrude / integrate / inner product
+    # Reference tensor_train.py:1438-1702 and :1919-2125.  Host NumPy on the coefficient cores; dimensions in the
+    # arguments are the USER's, the cores are walked by storage position.
+    def slice(self, params) -> "ChebyshevTT":
+        """Fix one or more user dimensions at given values (reference :2013-2125): ``(dim, value)`` or a list of
+        them.  The core goes to value space and is contracted with the normalised barycentric weights -- or picked
+        exactly when the value is within 1e-14 of a node -- and the matrix is absorbed into the right neighbour
+        (the left one for the last core)."""
+        from .barycentric import chebyshev_nodes, compute_barycentric_weights
+        self._check_built()
+        d = self.num_dimensions
+        params = _slice_params(params, d)
+        for dim_idx, value in params:
+            lo, hi = self.domain[self._dim_order.index(dim_idx)]
+            if value < lo or value > hi:
+                raise ValueError(f"Slice value {value} for dim {dim_idx} is outside domain [{lo}, {hi}]")
+        cores = list(self._coeff_cores)
+        domain, n_nodes, live = list(self.domain), list(self.n_nodes), list(self._dim_order)
+        placed = sorted(((self._dim_order.index(k), v) for k, v in params), reverse=True)
+        for pos, value in placed:                     # from the back: earlier positions stay valid
+            lo, hi = domain[pos]
+            nodes = chebyshev_nodes(lo, hi, n_nodes[pos])
+            values = _coeff_core_to_value_core(cores[pos])
+            gap = value - nodes
+            nearest = int(np.argmin(np.abs(gap)))
+            if abs(gap[nearest]) < 1e-14:
+                M = values[:, nearest, :]
+            else:
+                u = compute_barycentric_weights(nodes) / gap
+                M = np.einsum("rjs,j->rs", values, u / np.sum(u))
+            if pos < len(cores) - 1:
+                cores[pos + 1] = np.einsum("lr,rjs->ljs", M, cores[pos + 1])
+            else:
+                cores[pos - 1] = np.einsum("ijs,sr->ijr", cores[pos - 1], M)
+            for lst in (cores, domain, n_nodes, live):
+                del lst[pos]
+        order = _renumbered(live, d, {k for k, _ in params})
+        return self._derived(cores, domain=domain, n_nodes=n_nodes, dim_order=order)
+
+    def extrude(self, params) -> "ChebyshevTT":
+        """Add dimensions along which the function is constant (reference :1919-2011): ``(dim, (lo, hi), n_nodes)``
+        or a list of them, ``dim`` being the new dimension's index in the result.  The new core keeps the rank and
+        holds 1 in its c_0 slot only.  With the identity ``dim_order`` it is inserted at that storage position;
+        otherwise it is appended at the storage end and ``dim_order`` records where the user sees it."""
+        self._check_built()
+        params = _extrude_params(params, self.num_dimensions)
+        identity = self._dim_order == list(range(self.num_dimensions))
+        cores = list(self._coeff_cores)
+        domain, n_nodes, order = list(self.domain), list(self.n_nodes), list(self._dim_order)
+        for dim_idx, (lo, hi), n_new in params:
+            pos = dim_idx if identity else len(cores)
+            rank = 1 if pos == 0 or pos == len(cores) else cores[pos - 1].shape[2]
+            core = np.zeros((rank, n_new, rank))
+            core[np.arange(rank), 0, np.arange(rank)] = 1.0
+            cores.insert(pos, core)
+            domain.insert(pos, [lo, hi])
+            n_nodes.insert(pos, n_new)
+            if identity:
+                order = list(range(len(cores)))
+            else:
+                order = [u if u < dim_idx else u + 1 for u in order] + [dim_idx]
+        return self._derived(cores, domain=domain, n_nodes=n_nodes, dim_order=order)
+
+    def _integrated_dims(self, dims) -> List[int]:
+        if dims is None:
+            dims = list(range(self.num_dimensions))
+        elif isinstance(dims, (int, np.integer)):
+            dims = [int(dims)]
+        else:
+            dims = sorted(set(int(v) for v in dims))
+        if any(u < 0 or u >= self.num_dimensions for u in dims):
+            raise ValueError(f"dims contains out-of-range index (num_dimensions={self.num_dimensions}, dims={dims})")
+        return dims
+
+    def integrate(self, dims=None, bounds=None):
+        """Integrate over the user dimensions ``dims`` (all by default; reference :1505-1702): each integrated core
+        goes to value space and is contracted with the Fejer-1 weights -- the sub-interval weights where ``bounds``
+        gives ``(lo, hi)`` -- times ``(b - a) / 2``.  A float when no dimension is left, else a lower-dimensional
+        TT with the matrices absorbed into the next kept core (the last kept core for trailing ones)."""
+        from .barycentric import _integration_bounds, fejer1_weights, sub_interval_weights
+        self._check_built()
+        d = self.num_dimensions
+        dims = self._integrated_dims(dims)
+        per_dim = _integration_bounds(dims, bounds, self._user_frame_domain())
+        matrices = {}
+        for u, bd in zip(dims, per_dim):
+            pos = self._dim_order.index(u)
+            n = self.n_nodes[pos]
+            a, b = self.domain[pos]
+            if bd is None:
+                quad = fejer1_weights(n)
+            else:
+                quad = sub_interval_weights(n, 2.0 * (bd[0] - a) / (b - a) - 1.0, 2.0 * (bd[1] - a) / (b - a) - 1.0)
+            matrices[pos] = np.einsum("rjs,j->rs", _coeff_core_to_value_core(self._coeff_cores[pos]),
+                                      quad * ((b - a) / 2.0))
+        if len(dims) == d:
+            total = matrices[0]
+            for pos in range(1, d):
+                total = total @ matrices[pos]
+            return float(total.ravel()[0])
+        cores, pending = [], None
+        for pos in range(d):
+            if pos in matrices:
+                pending = matrices[pos] if pending is None else pending @ matrices[pos]
+                continue
+            core = self._coeff_cores[pos].copy()
+            if pending is not None:
+                core = np.einsum("lr,rjs->ljs", pending, core)
+                pending = None
+            cores.append(core)
+        if pending is not None:
+            cores[-1] = np.einsum("ljs,sr->ljr", cores[-1], pending)
+        kept = [pos for pos in range(d) if pos not in matrices]
+        return self._derived(cores, domain=[self.domain[pos] for pos in kept],
+                             n_nodes=[self.n_nodes[pos] for pos in kept],
+                             dim_order=_renumbered([self._dim_order[pos] for pos in kept], d, set(dims)))
+
+    def inner_product(self, other: "ChebyshevTT") -> float:
+        """Frobenius inner product of the two Chebyshev coefficient tensors, contracted core by core
+        (reference :1438-1503)."""
+        self._check_built()
+        if not isinstance(other, ChebyshevTT):
+            raise ValueError(f"other must be a ChebyshevTT, got {type(other).__name__}")
+        other._check_built()
+        same_box = np.allclose(np.asarray(self.domain, dtype=float), np.asarray(other.domain, dtype=float))
+        for what, same, mine, theirs in (("domains", same_box, self.domain, other.domain),
+                                         ("n_nodes", list(self.n_nodes) == list(other.n_nodes), self.n_nodes, other.n_nodes)):
+            if not same:
+                raise ValueError(f"inner_product requires matching {what}; got {mine} vs {theirs}")
+        if list(self._dim_order) != list(other._dim_order):
+            raise ValueError(f"inner_product requires matching _dim_order: {self._dim_order} vs {other._dim_order}. "
+                             "Call other = other.reorder(self._dim_order) (or self = self.reorder(other._dim_order)) "
+                             "to align before computing inner_product.")
+        # gram[a, b] pairs the left ranks of the two trains over the dimensions walked so far: fold it into this
+        # train's core, then sum that against the other's core over (its left rank, the coefficient index)
+        gram = np.ones((1, 1))
+        for mine, theirs in zip(self._coeff_cores, other._coeff_cores):
+            folded = np.tensordot(gram, mine, axes=(0, 0))                        # (r_other, n, r_self')
+            gram = np.tensordot(folded, theirs, axes=((0, 1), (0, 1)))            # (r_self', r_other')
+        return float(gram[0, 0])
+
+    def _box_rows(self, dims, bounds, points):
+        """Validated arguments of :meth:`integrate_batch` -> (flags by user dimension, rows ``(N, d + m)``)."""
+        d = self.num_dimensions
+        dims = self._integrated_dims(dims)
+        m = len(dims)
+        if m < 1:
+            raise ValueError("dims must name at least one dimension")
+        udom = np.asarray(self._user_frame_domain(), dtype=float)
+        kept = [u for u in range(d) if u not in dims]
+        n_rows = []
+        if bounds is None:
+            bnd = udom[dims][None, :, :]
+        else:
+            bnd = np.asarray(bounds, dtype=float)
+            if m == 1 and bnd.ndim == 1:
+                bnd = bnd[None, :]
+            if bnd.ndim == 2 and bnd.shape == (m, 2):
+                bnd = bnd[None, :, :]
+            elif m == 1 and bnd.ndim == 2 and bnd.shape[1] == 2:
+                bnd = bnd[:, None, :]
+            if bnd.ndim != 3 or bnd.shape[1:] != (m, 2):
+                raise ValueError(f"bounds must broadcast to (N, {m}, 2), got shape {np.shape(bounds)}")
+            if bnd.shape[0] != 1:
+                n_rows.append(("bounds", bnd.shape[0]))
+        if points is None:
+            if kept:
+                raise ValueError(f"points is required: {len(kept)} dimensions are kept")
+            pts = None
+        else:
+            pts = np.asarray(points, dtype=float)
+            if pts.ndim != 2 or pts.shape[1] != len(kept):
+                raise ValueError(f"points must have shape (N, {len(kept)}), got {pts.shape}")
+            n_rows.append(("points", pts.shape[0]))
+        if len(n_rows) == 2 and n_rows[0][1] != n_rows[1][1]:
+            raise ValueError(f"bounds has {n_rows[0][1]} rows but points has {n_rows[1][1]}")
+        N = n_rows[0][1] if n_rows else 1
+        bnd = np.broadcast_to(bnd, (N, m, 2))
+        lo, hi = bnd[:, :, 0], bnd[:, :, 1]
+        a, b = udom[dims, 0][None, :], udom[dims, 1][None, :]
+        bad = (lo > hi) | (lo < a - 1e-14) | (hi > b + 1e-14) | ~np.isfinite(lo) | ~np.isfinite(hi)
+        if bad.any():
+            r = int(np.argmax(bad.any(axis=1)))
+            j = int(np.argmax(bad[r]))
+            if lo[r, j] > hi[r, j]:
+                raise ValueError(f"bounds lo={lo[r, j]} > hi={hi[r, j]} for dim {dims[j]} (row {r})")
+            raise ValueError(f"bounds ({lo[r, j]}, {hi[r, j]}) outside domain [{udom[dims[j], 0]}, {udom[dims[j], 1]}] "
+                             f"for dim {dims[j]} (row {r})")
+        if pts is not None and pts.size:
+            pa, pb = udom[kept, 0][None, :], udom[kept, 1][None, :]
+            bad = ~((pts >= pa) & (pts <= pb))
+            if bad.any():
+                r = int(np.argmax(bad.any(axis=1)))
+                j = int(np.argmax(bad[r]))
+                raise ValueError(f"point value {pts[r, j]} for dim {kept[j]} is outside domain "
+                                 f"[{udom[kept[j], 0]}, {udom[kept[j], 1]}] (row {r})")
+        flags = np.zeros(d, dtype=np.int32)
+        flags[dims] = 1
+        rows = np.empty((N, d + m))
+        col = 0
+        for u in range(d):
+            if flags[u]:
+                j = dims.index(u)
+                rows[:, col] = np.maximum(lo[:, j], a[0, j])         # clipped to the domain, as integrate() does
+                rows[:, col + 1] = np.minimum(hi[:, j], b[0, j])
+                col += 2
+            else:
+                rows[:, col] = pts[:, kept.index(u)]
+                col += 1
+        return flags, rows
+
+    def integrate_batch(self, dims, bounds=None, points=None) -> np.ndarray:
+        """Box integrals for a batch of rows (extension; the reference computes one with ``integrate(dims, bounds)``
+        and then ``eval(point)``): ``out[r]`` is the integral over ``bounds[r]`` in the user dimensions ``dims`` at
+        ``points[r]`` in the others.  ``bounds`` broadcasts to ``(N, m, 2)`` with the integrated dimensions in
+        increasing order (``(m, 2)``, or ``(2,)`` for one dimension, serves every row; ``None`` is the whole domain);
+        ``points`` is ``(N, d - m)``, the kept dimensions in increasing order as in :meth:`roots_batch`, and may be
+        ``None`` only when every dimension is integrated.  One launch on the device (``pcx_tt_box_batch``): the TT
+        chain with the antiderivatives of the Chebyshev polynomials as the basis in the integrated dimensions.
+        Host arrays only."""
+        self._check_built()
+        flags, rows = self._box_rows(dims, bounds, points)
+        t = self._dev()
+        rows = _lib.f64(rows)
+        out = np.empty(rows.shape[0])
+        if rows.shape[0]:
+            _lib.check(t.lib.pcx_tt_box_batch(t.handle, _lib.p_i32(flags), _lib.p_f64(rows), rows.shape[0],
+                                              _lib.p_f64(out)), t.lib)
+        return out
+
 
     # ---------------------------------------------------------------- persistence
     def __getstate__(self) -> dict:
