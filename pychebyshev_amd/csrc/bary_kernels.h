@@ -10,6 +10,7 @@
 //                         contraction as a (M x K) . (K x points) GEMM on
 //                         v_mfma_f64_16x16x4_f64 plus a VALU epilogue over the head dims
 //   k_bary_rows       K1+K2 for any shape: LPP lanes per point walk the tensor rows
+// The kernels that are no templates are static: several translation units include this file (bary_mfma_launch.h).
 #pragma once
 
 #include "pcx_common.h"
@@ -17,7 +18,7 @@
 // ---------------------------------------------------------------------------------
 // K3: one pass of _apply_derivative_passes: out[o,i,q] = sum_j in[o,j,q] * D[i,j].
 // ---------------------------------------------------------------------------------
-__global__ void k_mode_product(const double *__restrict__ in, double *__restrict__ out,
+static __global__ void k_mode_product(const double *__restrict__ in, double *__restrict__ out,
                                const double *__restrict__ D, long outer, int na, long inner) {
     long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     long total = outer * na * inner;
@@ -38,7 +39,7 @@ __global__ void k_mode_product(const double *__restrict__ in, double *__restrict
 // (ChebyshevApproximation.slice: vec = normalised barycentric weights or a one-hot row,
 // reference _extrude_slice.py:79-92; the same kernel serves quadrature weights).
 // ---------------------------------------------------------------------------------
-__global__ void k_contract_axis(const double *__restrict__ in, double *__restrict__ out,
+static __global__ void k_contract_axis(const double *__restrict__ in, double *__restrict__ out,
                                 const double *__restrict__ vec, long outer, int na, long inner) {
     long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= outer * inner) return;
@@ -51,12 +52,14 @@ __global__ void k_contract_axis(const double *__restrict__ in, double *__restric
 }
 
 // ---------------------------------------------------------------------------------
-// A-fragment packing: frag[t][s][l] = T2[16 t + (l & 15)][4 s + (l >> 4)], zero padded,
+// A-fragment packing: frag[t][s][l] = T2[16 t + (l & 15)][R + 4 s + (l >> 4)], zero padded,
 // where T2 is the C-order tensor viewed as (M x K).  One coalesced 512-byte read then
 // feeds one v_mfma_f64_16x16x4_f64 (A operand: lane l holds A[l & 15][l >> 4]).
+// R (0, 1 or 2; BaryMfmaPlan::R) columns in front of the image are not part of it: they are the
+// accumulators' seed, packed by k_pack_seed behind the image.
 // ---------------------------------------------------------------------------------
-__global__ void k_pack_fragments(const double *__restrict__ T2, double *__restrict__ frag, int M,
-                                 int K, int MT, int KS) {
+static __global__ void k_pack_fragments(const double *__restrict__ T2, double *__restrict__ frag, int M,
+                                 int K, int MT, int KS, int R) {
     long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     long total = (long)MT * KS * 64;
     if (idx >= total) return;
@@ -65,14 +68,31 @@ __global__ void k_pack_fragments(const double *__restrict__ T2, double *__restri
     int s = (int)(ts % KS);
     int t = (int)(ts / KS);
     int m = 16 * t + (l & 15);
-    int k = 4 * s + (l >> 4);
+    int k = R + 4 * s + (l >> 4);
     frag[idx] = (m < M && k < K) ? T2[(long)m * K + k] : 0.0;
+}
+
+// Seed packing: seed[t][g][r][j] = T2[16 t + g + 4 j][r] for the R seed columns r (rows >= M: 0.0) -- the four
+// rows lane group g holds in its accumulator registers j = 0..3, side by side: one 32-byte load per column,
+// the same address for the 16 lanes of a group (like load_row_codes).  tps > 0: slab packing, tile t is tile
+// t % tps of slab t / tps and M the rows of one slab (k_pack_fragments_slabs).
+static __global__ void k_pack_seed(const double *__restrict__ T2, double *__restrict__ seed, int M, int K, int MT, int R, int tps) {
+    long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)MT * 16 * R) return;
+    const int j = (int)(idx & 3);
+    const int r = (int)((idx >> 2) % R);
+    const long tg = (idx >> 2) / R;
+    const int g = (int)(tg & 3);
+    const long t = tg >> 2;
+    const long slab = tps > 0 ? t / tps : 0;
+    const int m = 16 * (int)(tps > 0 ? t % tps : t) + g + 4 * j;
+    seed[idx] = m < M ? T2[(slab * M + m) * K + r] : 0.0;
 }
 
 // Slab packing for dim-0 groups (BaryG0): the tensor viewed as (n0 x M1 x K); slab i0 is packed like a
 // tensor of its own into `tps` row tiles (M1 rows padded to 16 tps), so no row tile straddles two i0.
-__global__ void k_pack_fragments_slabs(const double *__restrict__ T3, double *__restrict__ frag, int n0, int M1,
-                                       int K, int tps, int KS) {
+static __global__ void k_pack_fragments_slabs(const double *__restrict__ T3, double *__restrict__ frag, int n0, int M1,
+                                       int K, int tps, int KS, int R) {
     long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long per_slab = (long)tps * KS * 64;
     if (idx >= per_slab * n0) return;
@@ -83,7 +103,7 @@ __global__ void k_pack_fragments_slabs(const double *__restrict__ T3, double *__
     int s = (int)(ts % KS);
     int t = (int)(ts / KS);
     int m = 16 * t + (l & 15);
-    int k = 4 * s + (l >> 4);
+    int k = R + 4 * s + (l >> 4);
     frag[idx] = (m < M1 && k < K) ? T3[((long)i0 * M1 + m) * K + k] : 0.0;
 }
 
@@ -162,6 +182,18 @@ __device__ __forceinline__ pcx_u4 load_row_codes(const unsigned *__restrict__ co
     return pcx_u4{{q.x, q.y, q.z, q.w}};
 }
 
+// The seed of tile t for lane group g (k_pack_seed): R columns x the four rows g, g + 4, g + 8, g + 12.
+typedef const pcx_d4 __attribute__((address_space(1))) *pcx_seed_ptr;
+template <int R>
+struct pcx_seed { pcx_d4 v[R > 0 ? R : 1]; };
+template <int R>
+__device__ __forceinline__ pcx_seed<R> load_seed(pcx_seed_ptr seed, long t, int g) {
+    pcx_seed<R> q;
+#pragma unroll
+    for (int r = 0; r < R; ++r) q.v[r] = seed[(4 * t + g) * R + r];
+    return q;
+}
+
 template <int NF>
 __device__ __forceinline__ double code_weight_t(unsigned code, const double *bw_col, int PW) {
     if constexpr (NF >= 4) return code_weight(code, bw_col, PW);
@@ -178,10 +210,14 @@ __device__ __forceinline__ double code_weight_t(unsigned code, const double *bw_
 //
 //   prologue  weights of every dimension for the wave's points -> LDS table
 //             bw[row][point], rows = concatenated dims + one row of ones;
-//             B operands  B[nt][s] (lane l: k = 4s + (l>>4), point 16nt + (l&15))
-//             = product of the tail-dim weights named by kcode[k], kept in VGPRs.
+//             B operands  B[nt][s] (lane l: k = R + 4s + (l>>4), point 16nt + (l&15))
+//             = product of the tail-dim weights named by kcode[k - R], kept in VGPRs;
+//             R > 0: seed weights ws[nt][r] = wK[r, point] (kcode[4 KS + r]).
 //   main      row tiles are walked in CHUNKS of PCX_CHUNK_TILES; for each tile t:
-//             acc[nt] = sum_s mfma(A = frag[t][s], B[nt][s]);
+//             acc[nt] = seed + sum_s mfma(A = frag[t][s], B[nt][s]);
+//             seed = 0 (R = 0), else the K-remainder columns 0 .. R-1 as R vector FMAs per register onto +0.0:
+//             the f64 MFMA is a k-ordered FMA chain starting from C, so columns 0 .. R-1 as C followed by
+//             R .. K-1 in whole k-steps are the operations of 0 .. K-1 in padded k-steps, in the same order;
 //             D layout: lane l, reg j holds row (l>>4) + 4j, column (point) l & 15;
 //             cs[nt] += acc[nt][j] * (head-dim weight product named by rowcode[...]).
 //   every PCX_CHUNK_TILES tiles the per-lane chunk sum is added to the per-lane total.
@@ -205,7 +241,9 @@ __device__ __forceinline__ double code_weight_t(unsigned code, const double *bw_
 // the row codes name the head dimensions 1 .. split-1 only, at the end of every slab the wave's partial sum
 // P[i0] is reduced over the four lane groups into the (by then dead) tail part of its LDS table, and the
 // epilogue finishes all members of the group from P (bary_g0_finish).  grid.y = grid.z = 1.
-template <int KS, int NT, bool WIDE, int NF = 4, bool G0 = false>
+// R: K-remainder columns that enter as the accumulators' seed (BaryMfmaPlan::R; the seed array lies behind the
+// fragment image, k_pack_seed).
+template <int KS, int NT, bool WIDE, int NF = 4, bool G0 = false, int R = 0>
 __global__ void __launch_bounds__(256, 2)
 k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
             const double *__restrict__ wts, const double *const *__restrict__ frag_tab,
@@ -231,6 +269,7 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
     // vmcnt/lgkmcnt waits); it is known to be global memory, say so
     typedef const double __attribute__((address_space(1))) *gptr_t;
     const gptr_t frag = (gptr_t)frag_tab[blockIdx.z];
+    const pcx_seed_ptr seed = (pcx_seed_ptr)(frag + (size_t)plan.MT * KS * 64);
     const int nchunks = (plan.MT + PCX_CHUNK_TILES - 1) / PCX_CHUNK_TILES;
     const int ch0 = blockIdx.y * chunks_per_split;
     const int ch1 = (ch0 + chunks_per_split < nchunks) ? ch0 + chunks_per_split : nchunks;
@@ -268,6 +307,18 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
             for (int nt = 0; nt < NT; ++nt) B[nt][s] *= code_weight(hi, bwt + 16 * nt + c, PW);
         }
     }
+    double ws[NT][R > 0 ? R : 1];      // seed weights: wK[r, point] of the lane's column(s)
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        unsigned code = kcode[4 * KS + r];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) ws[nt][r] = code_weight(code, bwt + 16 * nt + c, PW);
+        if (WIDE) {
+            unsigned hi = kcode_hi[4 * KS + r];
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) ws[nt][r] *= code_weight(hi, bwt + 16 * nt + c, PW);
+        }
+    }
 
     // ---- main loop over row tiles; every PCX_CHUNK_TILES tiles the per-lane chunk sum cs
     //      is folded into the per-lane total (or stored, in a split launch)
@@ -278,20 +329,37 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
     const int t_begin = ch0 * PCX_CHUNK_TILES;
     const int t_end = (ch1 * PCX_CHUNK_TILES < plan.MT) ? ch1 * PCX_CHUNK_TILES : plan.MT;
     const bool split = gridDim.y > 1;
-    // Long narrow plans (the 11^5 headline: 31 k-steps) run a hand-pipelined tile loop: fragment
+    // Long narrow plans (the 11^5 headline: 30 k-steps) run a hand-pipelined tile loop: fragment
     // loads stay DEPTH k-steps ahead ACROSS tile boundaries (the first DEPTH fragments of tile t+1
     // are fetched during the tail of tile t), the row codes of tile t+1 are fetched at the top of
     // tile t (loads return in order: waiting for codes issued behind a tile's own fragment loads
     // drained them all, once per tile), and the head-weight look-ups of row j are issued at k-step
-    // 2j and multiplied two k-steps later.  Fences keep hipcc from sinking the loads back to
-    // their uses.  Same arithmetic in the same order as the plain loop below: identical results.
+    // 2j and multiplied two k-steps later.  The seed of tile t+1 (R > 0) is fetched with its first fragments.
+    // Fences keep hipcc from sinking the loads back to their uses.  Same arithmetic in the same
+    // order as the plain loop below: identical results.
     constexpr bool PIPELINED = (KS >= 12);
     constexpr int DEPTH = 6;           // <= 12 <= KS: the ring never wraps a tile (A/B on one box: 4 -0.6 %, 8 -0.3 %)
     unsigned cn[4] = {0u, 0u, 0u, 0u}, cnh[4] = {0u, 0u, 0u, 0u};
     double head[DEPTH];
+    // The accumulators start a tile at its seed: +0.0 (R = 0), else column 0 (then 1) as FMAs onto +0.0.  The pipelined
+    // loop fetches the seed of tile t+1 with that tile's first fragments and forms it when tile t's epilogue has read
+    // the accumulators, so the seed occupies registers of its own for DEPTH k-steps only.
+    pcx_d4 acc[NT];
+    auto seed_acc = [&](const pcx_seed<R> &sd) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[nt] = (pcx_d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[nt][j] = __builtin_fma(sd.v[r][j], ws[nt][r], acc[nt][j]);
+    };
+    constexpr bool CARRY = PIPELINED && R > 0;      // acc is seeded for the next tile at the end of each tile
 #pragma unroll
     for (int i = 0; i < DEPTH; ++i) head[i] = 0.0;
     if (PIPELINED && t_begin < t_end) {
+        if constexpr (R > 0) seed_acc(load_seed<R>(seed, t_begin, g));
         {
             const pcx_u4 q = load_row_codes(rowcode, t_begin, g);
             pcx_u4 qh = q;
@@ -307,9 +375,11 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
     }
     for (int t = t_begin; t < t_end; ++t) {
         double w[NT][4];
-        pcx_d4 acc[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[nt] = (pcx_d4){0.0, 0.0, 0.0, 0.0};
+        pcx_seed<R> sdn;
+        if constexpr (!CARRY) {
+            if constexpr (R > 0) sdn = load_seed<R>(seed, t, g);
+            seed_acc(sdn);
+        }
         const gptr_t tt = tf + (size_t)t * KS * 64;
         if constexpr (PIPELINED) {
             const int t_next = (t + 1 < t_end) ? t + 1 : t;
@@ -336,6 +406,9 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
                 const double a = ring[s % DEPTH];
                 if (s + DEPTH < KS) ring[s % DEPTH] = tt[(s + DEPTH) * 64];
                 else head[s + DEPTH - KS] = tn[(s + DEPTH - KS) * 64];
+                if constexpr (R > 0) {          // with tile t+1's first fragments: live for DEPTH k-steps only
+                    if (s == KS - DEPTH) sdn = load_seed<R>(seed, t_next, g);
+                }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     if (s == 2 * j) {
@@ -398,6 +471,7 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
             for (int j = 0; j < 4; ++j) cs[nt] = __builtin_fma(acc[nt][j], w[nt][j], cs[nt]);
+        if constexpr (CARRY) seed_acc(sdn);
         if constexpr (G0) {
             if ((t + 1) % gs.tps == 0) {            // end of slab i0: P[i0] = (s0 + s1) + (s2 + s3) -> LDS
                 const int i0 = t / gs.tps;
@@ -473,8 +547,10 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
 //   ds_read_b64 (16 distinct addresses per wave-instruction, conflict-free).
 // 512 threads = 8 waves share each staged tile; every wave owns 32 points (NT = 2).
 // dynamic LDS = 8 * (sum_n + 2) * 32 * 8 + 2 * KS * 64 * 8 bytes.
+// R > 0: the same seed as k_bary_mfma, from the same array -- accumulator (row group rg) of lane group g is
+// register j = rg of the 16x16x4 kernel's D layout.
 // ---------------------------------------------------------------------------------
-template <int KS>
+template <int KS, int R = 0>
 __global__ void __launch_bounds__(512, 2)
 k_bary_mfma4(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
              const double *__restrict__ wts, const double *const *__restrict__ frag_tab,
@@ -496,6 +572,7 @@ k_bary_mfma4(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
     const long base = ((long)blockIdx.x * 8 + wave) * PW;
     typedef const double __attribute__((address_space(1))) *gptr_t;
     const gptr_t frag = (gptr_t)frag_tab[blockIdx.z];
+    const pcx_seed_ptr seed = (pcx_seed_ptr)(frag + (size_t)plan.MT * SLAB);
 
     // ---- prologue 1: barycentric weights (lane -> point lane % 32, dims strided by 2)
     {
@@ -544,6 +621,13 @@ k_bary_mfma4(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) B[nt][s] = code_weight(code, bwt + 16 * nt + c, PW);
     }
+    double ws[NT][R > 0 ? R : 1];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        unsigned code = kcode[4 * KS + r];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) ws[nt][r] = code_weight(code, bwt + 16 * nt + c, PW);
+    }
 
     double total[NT], cs[NT];
 #pragma unroll
@@ -572,6 +656,8 @@ k_bary_mfma4(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
         // the tile's four row codes of this lane group, fetched before the MFMA chains
         const pcx_u4 q4 = load_row_codes(rowcode, t, g);
         const unsigned code0 = q4.v[0], code1 = q4.v[1], code2 = q4.v[2], code3 = q4.v[3];
+        pcx_seed<R> sd;
+        if constexpr (R > 0) sd = load_seed<R>(seed, t, g);
         // two row groups at a time: four independent accumulator chains, and the broadcast
         // LDS reads of the next DEPTH k-steps are in flight while the current one multiplies
 #pragma unroll
@@ -581,7 +667,11 @@ k_bary_mfma4(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
 #pragma unroll
             for (int r = 0; r < 2; ++r)
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[r][nt] = 0.0;
+                for (int nt = 0; nt < NT; ++nt) {
+                    acc[r][nt] = 0.0;
+#pragma unroll
+                    for (int rr = 0; rr < R; ++rr) acc[r][nt] = __builtin_fma(sd.v[rr][2 * half + r], ws[nt][rr], acc[r][nt]);
+                }
             typedef double d2_t __attribute__((ext_vector_type(2)));
             const d2_t *ar = reinterpret_cast<const d2_t *>(cur + aoff + 32 * half);   // 32 pairs per k-step
             d2_t ring[DEPTH];
@@ -632,7 +722,7 @@ k_bary_mfma4(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
 // Finishes a split launch with exactly the additions of a non-split one: per lane group g
 // the chunk sums in chunk order, s_g = ((cs_0 + cs_1) + cs_2) + ..., then (s0 + s1) + (s2 + s3).
 // partial layout: [spec][chunk][group][point].
-__global__ void k_bary_reduce(const double *__restrict__ partial, double *__restrict__ out, long N,
+static __global__ void k_bary_reduce(const double *__restrict__ partial, double *__restrict__ out, long N,
                               int nchunks, int nspec, long ostride, long ooff,
                               const int *__restrict__ perm) {
     long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -656,7 +746,7 @@ __global__ void k_bary_reduce(const double *__restrict__ partial, double *__rest
 // with K = n[d-1], accumulating wM(row) * sum_k T[row,k] b_last[k]; shuffle-reduce.
 // dynamic LDS = (256 / LPP) * sum_n * 8 bytes.
 // ---------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256)
+static __global__ void __launch_bounds__(256)
 k_bary_rows(BaryDims dims, int LPP, const double *__restrict__ nodes,
             const double *__restrict__ wts, const double *__restrict__ T,
             const double *__restrict__ pts, double *__restrict__ out, long N, long ostride,

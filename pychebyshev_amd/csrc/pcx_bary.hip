@@ -5,6 +5,7 @@
 
 #include "pcx_bary_internal.h"
 #include "bary_kernels.h"
+#include "bary_mfma_launch.h"
 #include "gather_kernels.h"
 #include "sobol_kernels.h"
 
@@ -29,21 +30,32 @@ static const int kCacheSpecs = 96;    // derivative tensors kept per handle besi
 
 // every k-step count up to 32 is instantiated: no padding of the folded K axis beyond 4;
 // 36..64 (one column tile per wave only: the B operands alone are up to 128 VGPRs) let two
-// tail dimensions of 12..16 nodes fold into K
+// tail dimensions of 12..16 nodes fold into K; 42 exists in the seeded sets only (13 x 13 = 1 + 4 x 42)
 static const int kKsList[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22,
-                              23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 36, 40, 44, 48, 52, 56, 60, 64};
+                              23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 36, 40, 42, 44, 48, 52, 56, 60, 64};
 
-static int pick_ks(int K) {
-    int need = (K + 3) / 4;
+// K columns of which the first R are the accumulators' seed: the instantiated k-step count that runs the rest
+static int pick_ks(int K, int R = 0) {
+    int need = (K - R + 3) / 4;
     for (int ks : kKsList)
-        if (ks >= need) return ks;
+        if (ks >= need && (ks != 42 || R > 0)) return ks;
     return -1;
+}
+
+// K mod 4 = 1 or 2: those columns become the seed of the accumulators (R vector FMAs per accumulator register)
+// and the k-loop runs (K - R) / 4 whole k-steps -- against a k-step of its own that multiplies mostly padding.
+// A remainder of 3 stays a k-step (12 NT vector FMAs against NT matrix instructions).  PCX_BARY_SEED=0, read per
+// handle (a process may build both forms: tests, tools/seed_ab.py), keeps every plan unseeded.
+static int seed_columns(long K, bool seed) {
+    const int r = (int)(K % 4);
+    return (seed && K > 4 && (r == 1 || r == 2)) ? r : 0;
 }
 
 // choose the head/tail split minimising the estimated time: MT row tiles, each KS MFMAs plus
 // an epilogue (head-weight look-ups and products) worth about 5 MFMAs (measured on 15^4,
 // tools/bary_rate_probe.py); the single-column-tile kernels re-read A twice as often
-static bool plan_mfma(const BaryDims &dm, BaryMfmaPlan &best) {
+// (costs in half MFMAs: a seeded tile pays about half a matrix instruction for its R x 4 NT vector FMAs)
+static bool plan_mfma(const BaryDims &dm, BaryMfmaPlan &best, bool seed) {
     bool found = false;
     long best_cost = 0;
     for (int split = std::max(0, dm.d - 2 * PCX_CODE_FIELDS); split < dm.d; ++split) {
@@ -53,27 +65,20 @@ static bool plan_mfma(const BaryDims &dm, BaryMfmaPlan &best) {
         for (int k = split; k < dm.d; ++k) { K *= dm.n[k]; tail_rows += dm.n[k]; }
         if (K > 256 || M > (1 << 24)) continue;
         if (head_rows > PCX_MAX_PART_ROWS || tail_rows > PCX_MAX_PART_ROWS) continue;   // 8-bit code fields per table part
-        int ks = pick_ks((int)K);
+        const int R = seed_columns(K, seed);
+        int ks = pick_ks((int)K, R);
         if (ks < 0) continue;
         long mt = (M + 15) / 16;
-        long cost = mt * (ks + 5) * (ks > 32 ? 23 : 20);
+        long cost = mt * (2 * ks + 10 + (R > 0 ? 1 : 0)) * (ks > 32 ? 23 : 20);
         if (!found || cost < best_cost || (cost == best_cost && K > best.K)) {
             found = true;
             best_cost = cost;
-            best.split = split; best.M = (int)M; best.K = (int)K; best.MT = (int)mt; best.KS = ks;
+            best.split = split; best.M = (int)M; best.K = (int)K; best.MT = (int)mt; best.KS = ks; best.R = R;
             best.tail_base = (int)head_rows + 1;
             best.rows = dm.sum_n + 2;
         }
     }
     return found;
-}
-
-static size_t mfma4_lds_bytes(const BaryDims &dm, int ks) {
-    return ((size_t)8 * (dm.sum_n + 2) * 32 + (size_t)2 * ks * 64) * sizeof(double);
-}
-
-static size_t mfma_lds_bytes(const BaryDims &dm, int nt) {
-    return (size_t)4 * (dm.sum_n + 2) * 16 * nt * sizeof(double);
 }
 
 extern "C" int pcx_bary_destroy(pcx_bary *h) {
@@ -106,8 +111,9 @@ static int bary_pack(pcx_bary *h, DerivedTensor &dt) {
     if (!h->mfma_ok) return PCX_OK;
     const BaryMfmaPlan &p = h->plan;
     size_t cnt = h->kfold_ok ? bary_kfold_frag_count(h->kf) : (size_t)(h->grid_ok ? h->gp.MT : p.MT) * p.KS * 64;
+    const size_t nseed = (size_t)p.MT * 16 * p.R;                 // the seed columns, behind the image (R = 0: none)
     DevBuf frag, slot;
-    int rc = frag.alloc(cnt * sizeof(double));
+    int rc = frag.alloc((cnt + nseed) * sizeof(double));
     if (rc) return rc;
     if (h->kfold_ok) {
         if ((rc = bary_pack_kfold(h, dt.plain, frag.as<double>()))) return rc;
@@ -116,8 +122,13 @@ static int bary_pack(pcx_bary *h, DerivedTensor &dt) {
     } else {
         int blocks = (int)((cnt + 255) / 256);
         hipLaunchKernelGGL(k_pack_fragments, dim3(blocks), dim3(256), 0, h->stream, dt.plain, frag.as<double>(),
-                           p.M, p.K, p.MT, p.KS);
+                           p.M, p.K, p.MT, p.KS, p.R);
         HIP_TRY(hipGetLastError());
+        if (nseed) {
+            hipLaunchKernelGGL(k_pack_seed, dim3((unsigned)((nseed + 255) / 256)), dim3(256), 0, h->stream, dt.plain,
+                               frag.as<double>() + cnt, p.M, p.K, p.MT, p.R, 0);
+            HIP_TRY(hipGetLastError());
+        }
     }
     if ((rc = slot.alloc(sizeof(double *)))) return rc;
     double *fp = frag.as<double>();
@@ -186,7 +197,8 @@ extern "C" int pcx_bary_create(int device, int d, const int32_t *n_nodes, const 
     h->lpp = lpp;
 
     // MFMA plan + row/k codes
-    h->mfma_ok = plan_mfma(h->dims, h->plan);
+    { const char *e = getenv("PCX_BARY_SEED"); h->seed = !(e && e[0] == '0'); }
+    h->mfma_ok = plan_mfma(h->dims, h->plan, h->seed);
     if (h->mfma_ok) {
         // two column tiles per wave while the B operands fit the register file beside them: up to 32 k-steps, 36 and 40 with
         // narrow codes (232 ... 256 VGPRs at two waves per SIMD; round 4, one against two column tiles: 12^4 0.642 -> 0.683,
@@ -255,10 +267,9 @@ extern "C" int pcx_bary_create(int device, int d, const int32_t *n_nodes, const 
     }
     if (h->mfma_ok) {
         const BaryMfmaPlan &p = h->plan;
-        // all-ones rows: the last row of the head part (row codes) and of the tail part (k codes)
-        const unsigned ones_h = (unsigned)(p.tail_base - 1), ones_t = (unsigned)(p.rows - 1 - p.tail_base);
-        std::vector<unsigned> rowcode((size_t)p.MT * 16), kcode((size_t)p.KS * 4);
-        std::vector<unsigned> rowcode_hi(rowcode.size()), kcode_hi(kcode.size());
+        // all-ones rows: the last row of the head part (row codes) and of the tail part (k codes, below)
+        const unsigned ones_h = (unsigned)(p.tail_base - 1);
+        std::vector<unsigned> rowcode((size_t)p.MT * 16), rowcode_hi((size_t)p.MT * 16);
         h->wide = p.split > PCX_CODE_FIELDS || d - p.split > PCX_CODE_FIELDS;
         for (long m = 0; m < (long)p.MT * 16; ++m) {
             unsigned f[2 * PCX_CODE_FIELDS] = {ones_h, ones_h, ones_h, ones_h, ones_h, ones_h, ones_h, ones_h};
@@ -273,19 +284,6 @@ extern "C" int pcx_bary_create(int device, int d, const int32_t *n_nodes, const 
             rowcode[m] = f[0] | (f[1] << 8) | (f[2] << 16) | (f[3] << 24);
             rowcode_hi[m] = f[4] | (f[5] << 8) | (f[6] << 16) | (f[7] << 24);
         }
-        for (long kk = 0; kk < (long)p.KS * 4; ++kk) {
-            unsigned f[2 * PCX_CODE_FIELDS] = {ones_t, ones_t, ones_t, ones_t, ones_t, ones_t, ones_t, ones_t};
-            if (kk < p.K) {
-                long rem = kk;
-                for (int k = d - 1; k >= p.split; --k) {
-                    int i = (int)(rem % h->dims.n[k]);
-                    rem /= h->dims.n[k];
-                    f[k - p.split] = (unsigned)(h->dims.off[k] - h->dims.off[p.split] + i);   // relative to the tail part
-                }
-            }
-            kcode[kk] = f[0] | (f[1] << 8) | (f[2] << 16) | (f[3] << 24);
-            kcode_hi[kk] = f[4] | (f[5] << 8) | (f[6] << 16) | (f[7] << 24);
-        }
         // device layout of the row codes: the four codes a lane needs for a tile (rows g, g+4, g+8, g+12 of
         // tile t) side by side, [t][g][j], so that one 16-byte load fetches them
         auto lane_order = [&](std::vector<unsigned> &v) {
@@ -299,14 +297,10 @@ extern "C" int pcx_bary_create(int device, int d, const int32_t *n_nodes, const 
         lane_order(rowcode_hi);
         if (h->wide) {
             CREATE_TRY(hipMalloc((void **)&h->d_rowcode_hi, rowcode_hi.size() * sizeof(unsigned)));
-            CREATE_TRY(hipMalloc((void **)&h->d_kcode_hi, kcode_hi.size() * sizeof(unsigned)));
             CREATE_TRY(hipMemcpy(h->d_rowcode_hi, rowcode_hi.data(), rowcode_hi.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-            CREATE_TRY(hipMemcpy(h->d_kcode_hi, kcode_hi.data(), kcode_hi.size() * sizeof(unsigned), hipMemcpyHostToDevice));
         }
         CREATE_TRY(hipMalloc((void **)&h->d_rowcode, rowcode.size() * sizeof(unsigned)));
-        CREATE_TRY(hipMalloc((void **)&h->d_kcode, kcode.size() * sizeof(unsigned)));
         CREATE_TRY(hipMemcpy(h->d_rowcode, rowcode.data(), rowcode.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-        CREATE_TRY(hipMemcpy(h->d_kcode, kcode.data(), kcode.size() * sizeof(unsigned), hipMemcpyHostToDevice));
         // dim-0 groups: head = dimension 0 x (dimensions 1 .. split-1); the rows of one i0 form a slab padded to whole
         // tiles.  Needs two column tiles per wave (large batches only), narrow codes, and room for two n0-vectors
         // per point in the tail part of the LDS table (dead once the B operands are in registers); n0 <= 16 bounds the
@@ -349,6 +343,11 @@ extern "C" int pcx_bary_create(int device, int d, const int32_t *n_nodes, const 
 
     // short plans: the grid form (bary_grid_kernels.h) -- unless the shape can share GEMMs between specs one order apart
     // (dim-0 groups above), which needs the slab packing of the row-code form
+    // Their planners and packers know no seed: they are priced, and where one of them is taken run, on the plan with
+    // every column in the k-loop
+    BaryMfmaPlan uplan = h->plan;
+    uplan.R = 0;
+    if (h->mfma_ok) uplan.KS = pick_ks(uplan.K);
     if (h->mfma_ok && !(h->plan.split > PCX_CODE_FIELDS || d - h->plan.split > PCX_CODE_FIELDS)) {
         // 3-D tensors one of whose dimensions fills whole row tiles: the k-fold form (bary_kfold_kernels.h) ahead of the grid
         // form -- and of the dim-0 groups: 9 x 48 x 30 runs at 0.30 of the peak on the row-code form a group would share, the
@@ -363,11 +362,11 @@ extern "C" int pcx_bary_create(int device, int d, const int32_t *n_nodes, const 
             if (keff > 0 && !h->g0_ok) {
                 // the alternative is the grid form -- or the row-code form where the grid planner declines, which it does when it
                 // expects no more of its own form: priced as a grid plan either way (25 x 25 x 40: row codes 0.44, k-fold 0.6)
-                (void)bary_plan_grid(h->dims, h->plan, gtry);
+                (void)bary_plan_grid(h->dims, uplan, gtry);
                 if (gtry.MT > 0)
-                    geff = (long)((double)h->plan.M * h->plan.K * 10000.0 / ((double)gtry.MT * 16.0 * h->plan.KS * 4.0));
+                    geff = (long)((double)uplan.M * uplan.K * 10000.0 / ((double)gtry.MT * 16.0 * uplan.KS * 4.0));
             }
-            h->kfold_ok = bary_kfold_take(h->kf, keff, geff, h->plan.KS);
+            h->kfold_ok = bary_kfold_take(h->kf, keff, geff, uplan.KS);
         }
         if (h->kfold_ok) {
             const int nt_rc = h->nt;
@@ -385,9 +384,9 @@ extern "C" int pcx_bary_create(int device, int d, const int32_t *n_nodes, const 
             (void)hipFree(h->d_rowcode_g0);
             h->d_rowcode_g0 = nullptr;
         }
-        if (!h->kfold_ok && !h->g0_ok) h->grid_ok = bary_plan_grid(h->dims, h->plan, h->gp);
+        if (!h->kfold_ok && !h->g0_ok) h->grid_ok = bary_plan_grid(h->dims, uplan, h->gp);
         if (h->grid_ok) {
-            h->nt = h->plan.KS > 32 ? 1 : 2;                       // the table is per wave and holds one part at a time
+            h->nt = uplan.KS > 32 ? 1 : 2;                       // the table is per wave and holds one part at a time
             const size_t cap = (size_t)(h->gp.wpb == 4 ? 150 : 64) * 1024;
             if (bary_grid_lds_bytes(h, h->nt) > cap) h->nt = 1;
             if (bary_grid_lds_bytes(h, h->nt) > cap) h->grid_ok = false;
@@ -413,6 +412,34 @@ extern "C" int pcx_bary_create(int device, int d, const int32_t *n_nodes, const 
         CREATE_TRY(hipMemcpy(h->d_gsnodes, sn.data(), sn.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     if (h->grid_ok || h->kfold_ok) h->mfma4_ok = false;
+    if (h->grid_ok || h->kfold_ok) h->plan = uplan;
+    if (h->mfma_ok) {
+        // k codes: entry kk names column R + kk (the fragment image starts behind the seed columns); the R seed
+        // columns 0 .. R-1 follow at 4 KS + r
+        const BaryMfmaPlan &p = h->plan;
+        const unsigned ones_t = (unsigned)(p.rows - 1 - p.tail_base);
+        std::vector<unsigned> kcode((size_t)p.KS * 4 + p.R), kcode_hi((size_t)p.KS * 4 + p.R);
+        for (long kk = 0; kk < (long)kcode.size(); ++kk) {
+            unsigned f[2 * PCX_CODE_FIELDS] = {ones_t, ones_t, ones_t, ones_t, ones_t, ones_t, ones_t, ones_t};
+            const long col = kk < (long)p.KS * 4 ? p.R + kk : kk - (long)p.KS * 4;
+            if (col < p.K) {
+                long rem = col;
+                for (int k = d - 1; k >= p.split; --k) {
+                    int i = (int)(rem % h->dims.n[k]);
+                    rem /= h->dims.n[k];
+                    f[k - p.split] = (unsigned)(h->dims.off[k] - h->dims.off[p.split] + i);   // relative to the tail part
+                }
+            }
+            kcode[kk] = f[0] | (f[1] << 8) | (f[2] << 16) | (f[3] << 24);
+            kcode_hi[kk] = f[4] | (f[5] << 8) | (f[6] << 16) | (f[7] << 24);
+        }
+        if (h->wide) {
+            CREATE_TRY(hipMalloc((void **)&h->d_kcode_hi, kcode_hi.size() * sizeof(unsigned)));
+            CREATE_TRY(hipMemcpy(h->d_kcode_hi, kcode_hi.data(), kcode_hi.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+        }
+        CREATE_TRY(hipMalloc((void **)&h->d_kcode, kcode.size() * sizeof(unsigned)));
+        CREATE_TRY(hipMemcpy(h->d_kcode, kcode.data(), kcode.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+    }
 
     // value tensor (derivative spec all-zero) enters the cache at create
     DerivedTensor dt;
@@ -621,122 +648,6 @@ PCX_HIDDEN int bary_get_tensor(pcx_bary *h, const int32_t *deriv, DerivedTensor 
     return PCX_OK;
 }
 
-// One MFMA launch for m specs (frag_tab: device table of m fragment pointers).  Small
-// batches are split over grid.y (chunks of row tiles) so that a handful of points still
-// uses the whole chip; the per-chunk totals are then added by k_bary_reduce in the fixed
-// chunk order, which makes every result independent of the batch size.
-template <int KS, int NT, bool WIDE, int NF = 4>
-static int launch_mfma_t(pcx_bary *h, const double *const *frag_tab, int m, const double *d_pts, long N,
-                         double *d_out, long ostride, long ooff, hipStream_t st, Scratch *split_scratch,
-                         const int *perm) {
-    const bool allow_split = split_scratch != nullptr;
-    size_t lds = mfma_lds_bytes(h->dims, NT);
-    auto kern = k_bary_mfma<KS, NT, WIDE, NF>;
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    long per_wg = 4L * 16 * NT;
-    long blocks = (N + per_wg - 1) / per_wg;
-    if (blocks > 0x7fffffffL) return fail(PCX_ERR_UNSUPPORTED, "batch too large for one launch");
-    int nchunks = (h->plan.MT + PCX_CHUNK_TILES - 1) / PCX_CHUNK_TILES;
-    int nsplit = 1, cps = nchunks;
-    const long want = 512;   // workgroups that fill 256 CUs at two per CU
-    if (allow_split && blocks * m < want && nchunks > 1) {
-        nsplit = (int)std::min<long>(nchunks, (want + blocks * m - 1) / (blocks * m));
-        cps = (nchunks + nsplit - 1) / nsplit;
-        nsplit = (nchunks + cps - 1) / cps;
-    }
-    double *partial = nullptr;
-    if (nsplit > 1) {
-        int rc = split_scratch->reserve((size_t)m * nchunks * 4 * (size_t)N * sizeof(double));
-        if (rc) return rc;
-        partial = (double *)split_scratch->ptr;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)nsplit, (unsigned)m), dim3(256), lds, st,
-                       h->dims, h->plan, h->d_nodes, h->d_wts, frag_tab, h->d_rowcode, h->d_kcode,
-                       h->d_rowcode_hi, h->d_kcode_hi, d_pts, d_out, N, ostride, ooff, cps, partial, perm, BaryG0{}, nullptr);
-    HIP_TRY(hipGetLastError());
-    if (nsplit > 1) {
-        long cnt = N * m;
-        hipLaunchKernelGGL(k_bary_reduce, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, partial, d_out,
-                           N, nchunks, m, ostride, ooff, perm);
-        HIP_TRY(hipGetLastError());
-    }
-    return PCX_OK;
-}
-
-// 4x4x4_4b form: 512-thread workgroups (8 waves x 32 points), row tiles staged through LDS.
-template <int KS>
-static int launch_mfma4_t(pcx_bary *h, const double *const *frag_tab, int m, const double *d_pts, long N,
-                          double *d_out, long ostride, long ooff, hipStream_t st, const int *perm) {
-    size_t lds = mfma4_lds_bytes(h->dims, KS);
-    auto kern = k_bary_mfma4<KS>;
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    long blocks = (N + 255) / 256;
-    if (blocks > 0x7fffffffL) return fail(PCX_ERR_UNSUPPORTED, "batch too large for one launch");
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, 1, (unsigned)m), dim3(512), lds, st, h->dims, h->plan,
-                       h->d_nodes, h->d_wts, frag_tab, h->d_rowcode, h->d_kcode, d_pts, d_out, N, ostride, ooff, perm);
-    HIP_TRY(hipGetLastError());
-    return PCX_OK;
-}
-
-static int launch_mfma4(pcx_bary *h, const double *const *frag_tab, int m, const double *d_pts, long N,
-                        double *d_out, long ostride, long ooff, hipStream_t st, const int *perm) {
-    switch (h->plan.KS) {
-#define CASE_KS(v) case v: return launch_mfma4_t<v>(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, perm);
-        CASE_KS(1) CASE_KS(2) CASE_KS(3) CASE_KS(4) CASE_KS(5) CASE_KS(6) CASE_KS(7) CASE_KS(8)
-        CASE_KS(9) CASE_KS(10) CASE_KS(11) CASE_KS(12) CASE_KS(13) CASE_KS(14) CASE_KS(15) CASE_KS(16)
-        CASE_KS(17) CASE_KS(18) CASE_KS(19) CASE_KS(20) CASE_KS(21) CASE_KS(22) CASE_KS(23) CASE_KS(24)
-        CASE_KS(25) CASE_KS(26) CASE_KS(27) CASE_KS(28) CASE_KS(29) CASE_KS(30) CASE_KS(31) CASE_KS(32)
-#undef CASE_KS
-    }
-    return fail(PCX_ERR_UNSUPPORTED, "no MFMA instantiation for KS=%d", h->plan.KS);
-}
-
-// NF: live fields of a row code = head dimensions (1..4), known per handle: the kernel reads only those
-// (16 LDS reads and multiplies fewer per row tile with a two-dimensional head; 11^5, head of three: +1.4 %).
-template <int NT, bool WIDE, int NF>
-static int launch_mfma_nf(pcx_bary *h, const double *const *frag_tab, int m, const double *d_pts, long N,
-                          double *d_out, long ostride, long ooff, hipStream_t st, Scratch *split_scratch,
-                          const int *perm) {
-    switch (h->plan.KS) {
-#define CASE_KS(v) case v: return launch_mfma_t<v, NT, WIDE, NF>(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, split_scratch, perm);
-        CASE_KS(1) CASE_KS(2) CASE_KS(3) CASE_KS(4) CASE_KS(5) CASE_KS(6) CASE_KS(7) CASE_KS(8)
-        CASE_KS(9) CASE_KS(10) CASE_KS(11) CASE_KS(12) CASE_KS(13) CASE_KS(14) CASE_KS(15) CASE_KS(16)
-        CASE_KS(17) CASE_KS(18) CASE_KS(19) CASE_KS(20) CASE_KS(21) CASE_KS(22) CASE_KS(23) CASE_KS(24)
-        CASE_KS(25) CASE_KS(26) CASE_KS(27) CASE_KS(28) CASE_KS(29) CASE_KS(30) CASE_KS(31) CASE_KS(32)
-#undef CASE_KS
-    }
-    if constexpr (NT == 1) {
-        switch (h->plan.KS) {
-#define CASE_KS(v) case v: return launch_mfma_t<v, 1, WIDE, NF>(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, split_scratch, perm);
-            CASE_KS(36) CASE_KS(40) CASE_KS(44) CASE_KS(48) CASE_KS(52) CASE_KS(56) CASE_KS(60) CASE_KS(64)
-#undef CASE_KS
-        }
-    }
-    if constexpr (NT == 2 && !WIDE) {
-        switch (h->plan.KS) {
-#define CASE_KS(v) case v: return launch_mfma_t<v, 2, WIDE, NF>(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, split_scratch, perm);
-            CASE_KS(36) CASE_KS(40)
-#undef CASE_KS
-        }
-    }
-    return fail(PCX_ERR_UNSUPPORTED, "no MFMA instantiation for KS=%d, NT=%d", h->plan.KS, NT);
-}
-
-template <int NT, bool WIDE>
-static int launch_mfma_nt(pcx_bary *h, const double *const *frag_tab, int m, const double *d_pts, long N,
-                          double *d_out, long ostride, long ooff, hipStream_t st, Scratch *split_scratch,
-                          const int *perm) {
-    if constexpr (!WIDE) {
-        if (h->plan.split <= 2)
-            return launch_mfma_nf<NT, false, 2>(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, split_scratch, perm);
-        if (h->plan.split == 3)
-            return launch_mfma_nf<NT, false, 3>(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, split_scratch, perm);
-    }
-    return launch_mfma_nf<NT, WIDE, 4>(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, split_scratch, perm);
-}
-
 static int launch_rows(pcx_bary *h, const DerivedTensor &dt, const double *d_pts, long N,
                        double *d_out, long ostride, long ooff, hipStream_t st, const int *perm) {
     int ppw = 256 / h->lpp;
@@ -831,12 +742,18 @@ static int bary_pack_g0(pcx_bary *h, DerivedTensor &dt) {
     const BaryMfmaPlan &p = h->plan;
     const int n0 = h->dims.n[0];
     const size_t cnt = (size_t)n0 * h->g0_tps * p.KS * 64;
+    const size_t nseed = (size_t)n0 * h->g0_tps * 16 * p.R;       // the slabs' seed columns, behind the image
     DevBuf frag, slot;
-    int rc = frag.alloc(cnt * sizeof(double));
+    int rc = frag.alloc((cnt + nseed) * sizeof(double));
     if (rc) return rc;
     hipLaunchKernelGGL(k_pack_fragments_slabs, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, dt.plain,
-                       frag.as<double>(), n0, p.M / n0, p.K, h->g0_tps, p.KS);
+                       frag.as<double>(), n0, p.M / n0, p.K, h->g0_tps, p.KS, p.R);
     HIP_TRY(hipGetLastError());
+    if (nseed) {
+        hipLaunchKernelGGL(k_pack_seed, dim3((unsigned)((nseed + 255) / 256)), dim3(256), 0, h->stream, dt.plain,
+                           frag.as<double>() + cnt, p.M / n0, p.K, n0 * h->g0_tps, p.R, h->g0_tps);
+        HIP_TRY(hipGetLastError());
+    }
     if ((rc = slot.alloc(sizeof(double *)))) return rc;
     double *fp = frag.as<double>();
     HIP_TRY(hipMemcpy(slot.p, &fp, sizeof(double *), hipMemcpyHostToDevice));
@@ -844,39 +761,6 @@ static int bary_pack_g0(pcx_bary *h, DerivedTensor &dt) {
     dt.frag_g0 = frag.release<double>();
     dt.slot_g0 = slot.release<double *>();
     return PCX_OK;
-}
-
-template <int KS, int NF>
-static int launch_g0_t(pcx_bary *h, const DerivedTensor &base, const BaryG0 &gs, const double *d_pts, long N, double *d_out,
-                       long ostride, long ooff, hipStream_t st) {
-    auto kern = k_bary_mfma<KS, 2, false, NF, true>;
-    const size_t lds = mfma_lds_bytes(h->dims, 2);
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const long blocks = (N + 127) / 128;
-    if (blocks > 0x7fffffffL) return fail(PCX_ERR_UNSUPPORTED, "batch too large for one launch");
-    BaryMfmaPlan plan = h->plan;
-    plan.MT = gs.tps * gs.n0;
-    const int nchunks = (plan.MT + PCX_CHUNK_TILES - 1) / PCX_CHUNK_TILES;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, 1, 1), dim3(256), lds, st, h->dims, plan, h->d_nodes, h->d_wts,
-                       (const double *const *)base.slot_g0, h->d_rowcode_g0, h->d_kcode, nullptr, nullptr, d_pts, d_out, N,
-                       ostride, ooff, nchunks, nullptr, nullptr, gs, h->d_diff + h->doff[0]);
-    HIP_TRY(hipGetLastError());
-    return PCX_OK;
-}
-
-template <int NF>
-static int launch_g0_nf(pcx_bary *h, const DerivedTensor &base, const BaryG0 &gs, const double *d_pts, long N, double *d_out,
-                        long ostride, long ooff, hipStream_t st) {
-    switch (h->plan.KS) {
-#define CASE_KS(v) case v: return launch_g0_t<v, NF>(h, base, gs, d_pts, N, d_out, ostride, ooff, st);
-        CASE_KS(1) CASE_KS(2) CASE_KS(3) CASE_KS(4) CASE_KS(5) CASE_KS(6) CASE_KS(7) CASE_KS(8)
-        CASE_KS(9) CASE_KS(10) CASE_KS(11) CASE_KS(12) CASE_KS(13) CASE_KS(14) CASE_KS(15) CASE_KS(16)
-        CASE_KS(17) CASE_KS(18) CASE_KS(19) CASE_KS(20) CASE_KS(21) CASE_KS(22) CASE_KS(23) CASE_KS(24)
-        CASE_KS(25) CASE_KS(26) CASE_KS(27) CASE_KS(28) CASE_KS(29) CASE_KS(30) CASE_KS(31) CASE_KS(32)
-#undef CASE_KS
-    }
-    return fail(PCX_ERR_UNSUPPORTED, "no dim-0 group instantiation for KS=%d", h->plan.KS);
 }
 
 static const long kG0MinPoints = 65536;      // below: per-spec launches (they split over row tiles and need no second pass)
@@ -908,19 +792,21 @@ PCX_HIDDEN int bary_launch(pcx_bary *h, DerivedTensor *const *dts, int m, const 
     }
     if (variant == 3) {
         if (!h->mfma4_ok) return fail(PCX_ERR_UNSUPPORTED, "4x4x4 MFMA kernel does not cover this shape");
-        return launch_mfma4(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, perm);
+        switch (h->plan.R) {
+        case 1: return bary_launch_mfma4_seed1(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, perm);
+        case 2: return bary_launch_mfma4_seed2(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, perm);
+        }
+        return launch_mfma4<0>(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, perm);
     }
     if (variant == 2) {
         if (!h->mfma_ok) return fail(PCX_ERR_UNSUPPORTED, "MFMA kernel does not cover this shape");
         if (h->kfold_ok) return bary_launch_kfold(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, perm);
         if (h->grid_ok) return bary_launch_grid(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, split_scratch, perm);
-        // two column tiles per wave for throughput; one when the batch cannot fill the chip
-        int nt = (N >= 65536) ? h->nt : 1;
-        if (h->wide)
-            return nt == 2 ? launch_mfma_nt<2, true>(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, split_scratch, perm)
-                           : launch_mfma_nt<1, true>(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, split_scratch, perm);
-        return nt == 2 ? launch_mfma_nt<2, false>(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, split_scratch, perm)
-                       : launch_mfma_nt<1, false>(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, split_scratch, perm);
+        switch (h->plan.R) {
+        case 1: return bary_launch_rowcode_seed1(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, split_scratch, perm);
+        case 2: return bary_launch_rowcode_seed2(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, split_scratch, perm);
+        }
+        return launch_rowcode<0>(h, frag_tab, m, d_pts, N, d_out, ostride, ooff, st, split_scratch, perm);
     }
     for (int s = 0; s < m; ++s) {
         int rc = launch_rows(h, *dts[s], d_pts, N, d_out, ostride, ooff + s, st, perm);
@@ -1010,8 +896,11 @@ static int bary_launch_group(pcx_bary *h, int q, const int32_t *lower, const int
         gs.col[i] = col[i];
         gs.maxorder = std::max(gs.maxorder, rel[i]);
     }
-    return (g->g0_nf == 2) ? launch_g0_nf<2>(g, *base, gs, pp, N, d_out, ostride, ooff, st)
-                           : launch_g0_nf<3>(g, *base, gs, pp, N, d_out, ostride, ooff, st);
+    switch (g->plan.R) {
+    case 1: return bary_launch_g0_seed1(g, *base, gs, pp, N, d_out, ostride, ooff, st);
+    case 2: return bary_launch_g0_seed2(g, *base, gs, pp, N, d_out, ostride, ooff, st);
+    }
+    return launch_g0<0>(g, *base, gs, pp, N, d_out, ostride, ooff, st);
 }
 
 // How far does the spec lower + e_q come out of lower's GEMM from where its own GEMM puts it?  Differentiating after

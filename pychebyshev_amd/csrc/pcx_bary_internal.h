@@ -15,9 +15,9 @@ static int alloc_plain(DevBuf &b, long total) {
 
 struct DerivedTensor {
     double *plain = nullptr;  // C-order tensor after the derivative passes (prod n doubles)
-    double *frag = nullptr;   // MFMA A-fragment packing of `plain` (MT*KS*64 doubles) or NULL
+    double *frag = nullptr;   // MFMA A-fragment packing of `plain` (MT*KS*64 doubles, then MT*16*R seed doubles) or NULL
     double **slot = nullptr;  // device table with the single entry `frag` (kernel's frag_tab)
-    double *frag_g0 = nullptr;   // slab packing for dim-0 group launches (n0 * tps * KS * 64 doubles), built on first use
+    double *frag_g0 = nullptr;   // slab packing for dim-0 group launches (n0 * tps * (KS * 64 + 16 R) doubles), built on first use
     double **slot_g0 = nullptr;  // device table with the single entry `frag_g0`
     uint64_t last_use = 0;    // handle clock at the last request (least-recently-used eviction)
     void free_all() {
@@ -43,6 +43,7 @@ struct pcx_bary {
     Scratch s_sobol;                 // k_sobol_energy's slab + k_sobol_finish's result
     // launch plan
     bool mfma_ok = false;
+    bool seed = true;                // K-remainder columns seed the accumulators (PCX_BARY_SEED=0 at create: never)
     BaryMfmaPlan plan;
     int nt = 2;                      // point tiles per wave in the MFMA kernel
     unsigned *d_rowcode = nullptr, *d_kcode = nullptr;
@@ -124,6 +125,19 @@ PCX_HIDDEN int bary_launch_kfold(pcx_bary *h, const double *const *frag_tab, int
                                  long ostride, long ooff, hipStream_t st, const int *perm);
 PCX_HIDDEN int bary_launch_grid(pcx_bary *h, const double *const *frag_tab, int m, const double *d_pts, long N, double *d_out,
                                 long ostride, long ooff, hipStream_t st, Scratch *split_scratch, const int *perm);
+
+// pcx_bary_seed1.hip, pcx_bary_seed2.hip: the row-code MFMA launch tables for plans with R = 1 and R = 2 seed columns
+// (bary_mfma_launch.h; R = 0 lives in pcx_bary.hip)
+#define PCX_DECLARE_SEED_LAUNCHERS(R)                                                                                            \
+    PCX_HIDDEN int bary_launch_rowcode_seed##R(pcx_bary *h, const double *const *frag_tab, int m, const double *d_pts, long N,   \
+                                               double *d_out, long ostride, long ooff, hipStream_t st, Scratch *split_scratch,   \
+                                               const int *perm);                                                                 \
+    PCX_HIDDEN int bary_launch_mfma4_seed##R(pcx_bary *h, const double *const *frag_tab, int m, const double *d_pts, long N,     \
+                                             double *d_out, long ostride, long ooff, hipStream_t st, const int *perm);           \
+    PCX_HIDDEN int bary_launch_g0_seed##R(pcx_bary *h, const DerivedTensor &base, const BaryG0 &gs, const double *d_pts, long N, \
+                                          double *d_out, long ostride, long ooff, hipStream_t st);
+PCX_DECLARE_SEED_LAUNCHERS(1)
+PCX_DECLARE_SEED_LAUNCHERS(2)
 
 // pcx_bary.hip
 PCX_HIDDEN int bary_get_tensor(pcx_bary *h, const int32_t *deriv, DerivedTensor **out);

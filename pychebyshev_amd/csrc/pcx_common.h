@@ -33,7 +33,8 @@ struct BaryMfmaPlan {
     int M;    // prod n[0:split]  (1 when split == 0)
     int K;    // prod n[split:d]
     int MT;   // row tiles of 16 covering M
-    int KS;   // k-steps of 4 run by the kernel instantiation (KS*4 >= K)
+    int KS;   // k-steps of 4 run by the kernel instantiation (KS*4 >= K - R)
+    int R;    // K mod 4 when that is 1 or 2 (else 0): columns 0 .. R-1 are no k-step, they seed the accumulators
     int tail_base;  // first table row of the tail part (= sum of head n + 1)
     int rows;       // table rows (= sum_n + 2)
 };
