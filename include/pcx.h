@@ -369,6 +369,37 @@ int pcx_tt_round(int device, int d, const int32_t *n_nodes, const int32_t *ranks
                  int max_rank, double tol, int32_t *ranks_out, double *cores_out, int64_t cores_cap,
                  int64_t *cores_len, int32_t *sweeps_out);
 
+/* Core orthogonalisation in place of ChebyshevTT.orth_left / orth_right (reference tensor_train.py:1296-1356,
+ * helpers :697-735).  side 0: cores 0 .. position-1 become left-orthonormal (position in [1, d-1]), each R factor
+ * multiplied into the next core; side 1: cores position+1 .. d-1 become row-orthonormal (position in [0, d-2]), each
+ * factor multiplied into the core before.  Every factorisation is a Householder QR of one unfolding in one workgroup,
+ * columns in their own order; a column that is zero below its diagonal takes the identity reflector, so the factor is
+ * orthonormal on rank-deficient input too.  An unfolding wider than tall gives the smaller bond, min(r_l n, r_r), as
+ * numpy.linalg.qr does.  Layout and limits of pcx_tt_round: cores concatenated in C order, ranks[0] = ranks[d] = 1,
+ * ranks or node counts above 256 are PCX_ERR_UNSUPPORTED before anything runs.  The input length always suffices as
+ * cores_cap.  The cores on the far side of `position` come back bit for bit.                                      */
+int pcx_tt_orth(int device, int d, const int32_t *n_nodes, const int32_t *ranks, const double *cores, int side,
+                int position, int32_t *ranks_out, double *cores_out, int64_t cores_cap, int64_t *cores_len);
+
+/* Fixed-rank completion by alternating least squares against the values on the whole tensor grid
+ * (ChebyshevTT.run_completion, reference tensor_train.py:1358-1436 and _als_fixed_rank_sweeps :738-876).  value_cores:
+ * the VALUE cores in pcx_tt_round's layout; target: host, prod(n) doubles, C order.  With the neighbouring cores in
+ * orthonormal form the solve of core k is the projection C_k = L^T T R^T; one outer iteration is a left-to-right and
+ * a right-to-left half sweep that carry the projected target along and read it about four times.  After each outer
+ * iteration the dense tensor of the cores is formed on the device and rel_change = ||T_new - T_prev||_F /
+ * (||T_prev||_F + 1e-30) goes to rel_change_out[i]; the loop stops when it falls below `tolerance` (the reference's
+ * rule) or after max_iter iterations; *iters_out = iterations run.  max_iter <= 0 runs none and returns the cores as
+ * given (rel_change_out may be NULL).  *grid_residual_out = ||TT - target||_F / ||target||_F of the returned cores.
+ * Bonds shrink where an unfolding cannot hold them (ranks_out).  Every sum runs in a fixed order: equal input gives
+ * equal bits.  Limits: those of pcx_tt_round, and a grid of at most PCX_TT_ALS_MAX_GRID points (the device holds the
+ * target, two reconstructions and the projection buffers, about 4 prod(n) doubles), else PCX_ERR_UNSUPPORTED before
+ * anything runs.                                                                                                    */
+#define PCX_TT_ALS_MAX_GRID (1LL << 28)
+int pcx_tt_als(int device, int d, const int32_t *n_nodes, const int32_t *ranks, const double *value_cores,
+               const double *target, double tolerance, int max_iter, int32_t *ranks_out, double *cores_out,
+               int64_t cores_cap, int64_t *cores_len, int32_t *iters_out, double *rel_change_out,
+               double *grid_residual_out);
+
 /* A sequence of adjacent swaps of storage axes (reference _algebra.py::_tt_swap_adjacent, driven by
  * ChebyshevTT.reorder): swap s exchanges axes swaps[s] and swaps[s] + 1 by one truncated SVD of the
  * merged pair (same rank rule).  Same input layout and limits as pcx_tt_round; a merged pair of more

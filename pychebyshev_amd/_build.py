@@ -30,6 +30,7 @@ SOURCES = {
     "pcx_tt.hip": HOST_H + ["tt_kernels.h", "tt_lpp_kernels.h", "tt_fd_kernels.h"],
     "pcx_tt_box.hip": HOST_H + ["tt_lpp_kernels.h", "tt_box_kernels.h"],
     "pcx_ttbuild.hip": HOST_H + ["ttcross_kernels.h", "ttsvd_kernels.h", "tt_round_kernels.h"],
+    "pcx_tt_als.hip": HOST_H + ["tt_als_kernels.h"],
     "pcx_calculus.hip": HOST_H + ["pcx_bary_internal.h", "calculus_kernels.h"],
     "pcx_comm.hip": [PCX_H],
 }

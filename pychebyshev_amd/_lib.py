@@ -123,6 +123,8 @@ SIGNATURES = {
     "pcx_tt_svd": (_I, [_I, _I, c_i32p, c_f64p, _I, _D, c_i32p, c_f64p, _L, c_i64p, c_i32p]),
     "pcx_tt_round": (_I, [_I, _I, c_i32p, c_i32p, c_f64p, _I, _D, c_i32p, c_f64p, _L, c_i64p, c_i32p]),
     "pcx_tt_reorder": (_I, [_I, _I, c_i32p, c_i32p, c_f64p, _I, c_i32p, _I, _D, c_i32p, c_i32p, c_f64p, _L, c_i64p, c_i32p]),
+    "pcx_tt_orth": (_I, [_I, _I, c_i32p, c_i32p, c_f64p, _I, _I, c_i32p, c_f64p, _L, c_i64p]),
+    "pcx_tt_als": (_I, [_I, _I, c_i32p, c_i32p, c_f64p, c_f64p, _D, _I, c_i32p, c_f64p, _L, c_i64p, c_i32p, c_f64p, c_f64p]),
     "pcx_comm_unique_id": (_I, [_V]),
     "pcx_comm_create": (_I, [_I, _I, _I, _V, c_vpp]),
     "pcx_comm_destroy": (_I, [_V]),

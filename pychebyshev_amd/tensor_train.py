@@ -28,8 +28,13 @@ is always a ``pcx_tt_eval_batch`` launch; there is no CPU fallback.
 the row's coordinates in the kept dimensions -- is one launch of the TT chain with the antiderivative basis in the
 integrated dimensions (``pcx_tt_box_batch``, ``csrc/tt_box_kernels.h``).
 
-Out of scope in this tier: the ``method='als'`` builder (raises ``NotImplementedError``), ``run_completion``,
-``orth_left`` / ``orth_right`` and ``with_auto_order``.
+``orth_left`` / ``orth_right`` run their Householder QR sweep on the device (``pcx_tt_orth``).  ``run_completion`` --
+fixed-rank alternating least squares against the values on the whole grid -- runs all its outer iterations in one
+device call (``pcx_tt_als``, ``csrc/tt_als_kernels.h``): with the neighbouring cores orthonormal each core's solve is
+the projection ``C_k = L^T T R^T``, two chains of tall-skinny contractions over the target tensor, in place of the
+reference's dense ``lstsq``.  Its ``values=`` keyword passes the target as a tensor instead of through the callback.
+
+Out of scope in this tier: the ``method='als'`` builder (raises ``NotImplementedError``) and ``with_auto_order``.
 """
 from __future__ import annotations
 
@@ -1066,6 +1071,102 @@ class ChebyshevTT(ErgonomicsMixin):
         if self._cached_error_estimate is None:
             self._cached_error_estimate = float(sum(np.max(np.abs(c[:, -1, :])) for c in self._coeff_cores))
         return self._cached_error_estimate
+
+    # ---------------------------------------------------------------- orthogonalisation and completion
+    # Reference tensor_train.py:1296-1436.  Both act in place; every argument check runs before the library is loaded.
+    def _set_cores(self, cores) -> None:
+        """New cores in place: the ranks follow the cores' bonds, the device handle and the cached error estimate go."""
+        self._coeff_cores = cores
+        self._tt_ranks = [c.shape[0] for c in cores] + [cores[-1].shape[2]]
+        self._cached_error_estimate = None
+        self.invalidate_device_cache()
+
+    def _orth(self, side: int, position: int) -> None:
+        from . import _algebra
+        lib = _lib.load()
+        n, ranks, cat = _algebra._shape_args(self._coeff_cores)
+        out = np.empty(cat.size)
+        ranks_out = np.empty(self.num_dimensions + 1, dtype=np.int32)
+        length = ctypes.c_int64(0)
+        dev = _lib.default_device() if self._device_index is None else self._device_index
+        _lib.check(lib.pcx_tt_orth(int(dev), self.num_dimensions, _lib.p_i32(n), _lib.p_i32(ranks), _lib.p_f64(cat),
+                                   int(side), int(position), _lib.p_i32(ranks_out), _lib.p_f64(out), out.size,
+                                   ctypes.byref(length)), lib)
+        self._set_cores(_algebra._split(out, n, ranks_out))
+
+    def orth_left(self, position: int) -> None:
+        """Left-orthogonalise cores ``[0 .. position-1]`` in place (reference :1296-1325): each, unfolded as
+        ``(r_k n_k, r_{k+1})``, gets orthonormal columns, the R factors move right into ``core[position]``; the tensor
+        is unchanged.  Householder QR on the device (``pcx_tt_orth``).  An unfolding wider than tall comes back with
+        the smaller bond, and ``tt_ranks`` follows."""
+        self._check_built()
+        d = self.num_dimensions
+        if not (1 <= position < d):
+            raise ValueError(f"position must be in [1, {d - 1}] for orth_left, got {position}")
+        self._orth(0, position)
+
+    def orth_right(self, position: int) -> None:
+        """Right-orthogonalise cores ``[position+1 .. d-1]`` in place (reference :1327-1356): each, unfolded as
+        ``(r_k, n_k r_{k+1})``, gets orthonormal rows, the factors move left; the tensor is unchanged."""
+        self._check_built()
+        d = self.num_dimensions
+        if not (0 <= position < d - 1):
+            raise ValueError(f"position must be in [0, {d - 2}] for orth_right, got {position}")
+        self._orth(1, position)
+
+    completion_info = None      # set by run_completion: {"iterations", "rel_change", "grid_residual"}
+
+    def run_completion(self, tolerance: float = 1e-8, max_iter: int = 50, verbose: bool = False, *, values=None) -> None:
+        """Refine the TT at its current rank by alternating least squares against the function's values on the whole
+        tensor grid (reference :1358-1436).  All outer iterations run in one device call (``pcx_tt_als``): with the
+        neighbouring cores orthonormal each core's solve is a projection of the target, see DESIGN.md.
+
+        ``values`` (extension, keyword only): the target as a dense tensor of shape ``tuple(self.n_nodes)`` in the
+        storage frame, in ``from_values``' node order, instead of the callback -- so a TT without ``function``
+        (``from_values``, ``reorder``, algebra results, loaded models) can be completed.  Without it the grid is filled
+        through ``self.function(point, additional_data)`` as ``build(method="svd")`` fills it.
+
+        Stops when ``||T_new - T_old||_F / ||T_old||_F < tolerance`` after an outer iteration, or after ``max_iter``
+        of them (``max_iter <= 0``: none).  ``self.completion_info`` records the iterations run, the ``rel_change``
+        history and ``grid_residual = ||TT - T||_F / ||T||_F`` of the final cores."""
+        self._check_built()
+        n = [int(v) for v in self.n_nodes]
+        d = self.num_dimensions
+        if values is None:
+            if self.function is None:
+                raise RuntimeError("run_completion requires self.function to be callable; "
+                                   "the TT was loaded from a source without the original function.")
+            grids = [np.sort(0.5 * (a + b) + 0.5 * (b - a) * chebpts1(nk)) for (a, b), nk in zip(self.domain, n)]
+            data, raw = self.additional_data, self.function
+            target = np.empty(n)
+            for idx in np.ndindex(*n):
+                target[idx] = raw([float(grids[k][idx[k]]) for k in range(d)], data)
+        else:
+            target = np.asarray(values, dtype=np.float64)
+            if target.shape != tuple(n):
+                raise ValueError(f"values shape {target.shape} does not match expected {tuple(n)}")
+            if not np.isfinite(target).all():
+                raise ValueError("values contains NaN or Inf — all values must be finite")
+        from . import _algebra
+        lib = _lib.load()
+        value_cores = [_coeff_core_to_value_core(c) for c in self._coeff_cores]
+        nn, ranks, cat = _algebra._shape_args(value_cores)
+        target = _lib.f64(target)
+        out = np.empty(cat.size)
+        ranks_out = np.empty(d + 1, dtype=np.int32)
+        length, iters, resid = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_double(0.0)
+        history = np.zeros(max(int(max_iter), 1))
+        dev = _lib.default_device() if self._device_index is None else self._device_index
+        _lib.check(lib.pcx_tt_als(int(dev), d, _lib.p_i32(nn), _lib.p_i32(ranks), _lib.p_f64(cat), _lib.p_f64(target.ravel()),
+                                  float(tolerance), int(max_iter), _lib.p_i32(ranks_out), _lib.p_f64(out), out.size,
+                                  ctypes.byref(length), ctypes.byref(iters), _lib.p_f64(history), ctypes.byref(resid)), lib)
+        refined = _algebra._split(out, nn, ranks_out)
+        self._set_cores([_value_core_to_coeff_core(c) for c in refined])
+        rel = [float(v) for v in history[: int(iters.value)]]
+        if verbose:
+            for i, x in enumerate(rel):
+                print(f"  ALS iter {i + 1}: rel_change = {x:.3e}")
+        self.completion_info = {"iterations": int(iters.value), "rel_change": rel, "grid_residual": float(resid.value)}
 
     # ---------------------------------------------------------------- algebra
     # Reference tensor_train.py:3287-3458 and :2575-2676.  Scalars scale core 0 on the host; a sum stacks the cores
