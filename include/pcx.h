@@ -204,6 +204,12 @@ int pcx_bary_kernel_info(pcx_bary *h, int32_t *info_out /* 6 ints; [2] = k-steps
  * dimension}.  PCX_BARY_KFOLD=0 switches
  * that form off. */
 int pcx_bary_grid_info(pcx_bary *h, int32_t *info_out /* 4 ints */);
+/* The row-code MFMA form's launch geometry for large batches: [0] workgroups the device holds at once, [1] points per
+ * workgroup, [2] chunks of row tiles, [3] whether a launch whose last round of workgroups is at most half full splits
+ * that round over the idle ones (1: where the row-tile walk is long enough to pay for the finishing kernel, the default;
+ * PCX_BARY_TAIL=0 at create: 0, never; =2: 2, wherever the geometry allows), [4] workgroups per tail block in the latest such
+ * launch (0: it kept one workgroup per block), [5] its tail blocks.  All zero when launches take another form. */
+int pcx_bary_tail_info(pcx_bary *h, int32_t *info_out /* 6 ints */);
 int pcx_bary_stream(pcx_bary *h, void **stream);
 
 /* ---- piecewise (spline) interpolant ---------------------------------------- */

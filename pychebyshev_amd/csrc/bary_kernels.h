@@ -13,6 +13,8 @@
 // The kernels that are no templates are static: several translation units include this file (bary_mfma_launch.h).
 #pragma once
 
+#include <type_traits>
+
 #include "pcx_common.h"
 
 // ---------------------------------------------------------------------------------
@@ -194,6 +196,16 @@ __device__ __forceinline__ pcx_seed<R> load_seed(pcx_seed_ptr seed, long t, int 
     return q;
 }
 
+// Row OFFSETS (pipelined loop of the narrow instantiations): the same fields as a row code, each already scaled to the
+// LDS byte offset row * PW * 8 of its table row (16 bits: rows <= 255, PW <= 32), so that a look-up address is the
+// lane's table base plus a half-word -- one vector instruction per field instead of extract + shift-add.  Per tile t
+// and lane group g two 16-byte words, [t][g][w][j]: word 0 holds fields 0 | 1 << 16 of rows j = 0..3, word 1 fields
+// 2 | 3 << 16 (read only when NF >= 3).  One table per PW (pcx_bary_create).
+__device__ __forceinline__ pcx_u4 load_row_offs(const unsigned *__restrict__ offs, long t, int g, int w) {
+    const uint4 q = reinterpret_cast<const uint4 *>(offs)[8 * t + 2 * g + w];
+    return pcx_u4{{q.x, q.y, q.z, q.w}};
+}
+
 template <int NF>
 __device__ __forceinline__ double code_weight_t(unsigned code, const double *bw_col, int PW) {
     if constexpr (NF >= 4) return code_weight(code, bw_col, PW);
@@ -229,6 +241,10 @@ __device__ __forceinline__ double code_weight_t(unsigned code, const double *bw_
 //   [y*cps, (y+1)*cps) and stores each per-lane chunk sum to partial[z][chunk][g][p];
 //   k_bary_reduce then performs the same additions in the same order -> results are
 //   bit-identical for every batch size.
+// tail.P > 0 ("tail split", large batches whose last round of resident workgroups is at most half full): the
+//   workgroups from blockIdx.x = tail.first on are P pieces per point block; piece q of tail block b walks the
+//   chunks [q*tail.cpp, (q+1)*tail.cpp) of point block tail.first + b and stores its chunk sums to partial like a
+//   split launch, indexed by point relative to the first tail point; k_bary_reduce finishes those points.
 // grid.z = number of derivative specs evaluated in this launch (frag_tab[z]).
 //
 // 256 threads = 4 waves; dynamic LDS = 4 * (sum_n + 2) * PW * 8 bytes.
@@ -251,7 +267,8 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
             const unsigned *__restrict__ rowcode_hi, const unsigned *__restrict__ kcode_hi,
             const double *__restrict__ pts, double *__restrict__ out, long N, long ostride,
             long ooff, int chunks_per_split, double *__restrict__ partial,
-            const int *__restrict__ perm, BaryG0 gs, const double *__restrict__ diff0) {
+            const int *__restrict__ perm, BaryG0 gs, const double *__restrict__ diff0,
+            const unsigned *__restrict__ rowoff, BaryTail tail) {
     // perm (optional): the launch covers the N rows perm[0..N) of pts/out (a bucket of a
     // piecewise interpolant) instead of rows 0..N.
     static_assert(NT == 1 || NT == 2 || NT == 4, "PW must divide the wave");
@@ -264,15 +281,30 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
     const int c = lane & 15;
     double *bw = lds + (size_t)wave * plan.rows * PW;
     const double *bwt = bw + (size_t)plan.tail_base * PW;      // tail part: what the k codes index
-    const long base = ((long)blockIdx.x * 4 + wave) * PW;
+    // point block and chunk range of this workgroup: its own, or (tail split) a piece of a tail block
+    int bx = blockIdx.x;
+    const int nchunks = (plan.MT + PCX_CHUNK_TILES - 1) / PCX_CHUNK_TILES;
+    int ch0 = blockIdx.y * chunks_per_split, ch_len = chunks_per_split;
+    bool split = gridDim.y > 1;
+    long part_p0 = 0;                  // first point of `partial`, and the points it holds per (chunk, lane group)
+    long part_n = N;
+    if (!G0 && tail.P > 0 && bx >= tail.first) {
+        const int e = bx - tail.first;
+        const int tb = e / tail.P;
+        bx = tail.first + tb;
+        ch0 = (e - tb * tail.P) * tail.cpp;
+        ch_len = tail.cpp;
+        split = true;
+        part_p0 = (long)tail.first * 4 * PW;
+        part_n = N - part_p0;
+    }
+    const int ch1 = (ch0 + ch_len < nchunks) ? ch0 + ch_len : nchunks;
+    const long base = ((long)bx * 4 + wave) * PW;
     // a pointer loaded from memory is "generic" to the compiler (flat_load + combined
     // vmcnt/lgkmcnt waits); it is known to be global memory, say so
     typedef const double __attribute__((address_space(1))) *gptr_t;
     const gptr_t frag = (gptr_t)frag_tab[blockIdx.z];
     const pcx_seed_ptr seed = (pcx_seed_ptr)(frag + (size_t)plan.MT * KS * 64);
-    const int nchunks = (plan.MT + PCX_CHUNK_TILES - 1) / PCX_CHUNK_TILES;
-    const int ch0 = blockIdx.y * chunks_per_split;
-    const int ch1 = (ch0 + chunks_per_split < nchunks) ? ch0 + chunks_per_split : nchunks;
 
     // ---- prologue 1: barycentric weights (lane -> point lane % PW, dims strided by PH)
     {
@@ -295,30 +327,37 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
     __syncthreads();
 
     // ---- prologue 2: B operands in registers
+    // A narrow tail of at most two dimensions (wave-uniform, a plan field) reads its two live fields only: the others
+    // name the ones row and a product with exactly 1.0 changes no bit (as NF for the row codes).
     double B[NT][KS];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        unsigned code = kcode[4 * s + g];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) B[nt][s] = code_weight(code, bwt + 16 * nt + c, PW);
-        if (WIDE) {
-            unsigned hi = kcode_hi[4 * s + g];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) B[nt][s] *= code_weight(hi, bwt + 16 * nt + c, PW);
-        }
-    }
     double ws[NT][R > 0 ? R : 1];      // seed weights: wK[r, point] of the lane's column(s)
+    auto tail_weights = [&](auto nft) {
+        constexpr int NFT = decltype(nft)::value;
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-        unsigned code = kcode[4 * KS + r];
+        for (int s = 0; s < KS; ++s) {
+            unsigned code = kcode[4 * s + g];
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) ws[nt][r] = code_weight(code, bwt + 16 * nt + c, PW);
-        if (WIDE) {
-            unsigned hi = kcode_hi[4 * KS + r];
+            for (int nt = 0; nt < NT; ++nt) B[nt][s] = code_weight_t<NFT>(code, bwt + 16 * nt + c, PW);
+            if (WIDE) {
+                unsigned hi = kcode_hi[4 * s + g];
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) ws[nt][r] *= code_weight(hi, bwt + 16 * nt + c, PW);
+                for (int nt = 0; nt < NT; ++nt) B[nt][s] *= code_weight(hi, bwt + 16 * nt + c, PW);
+            }
         }
-    }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            unsigned code = kcode[4 * KS + r];
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) ws[nt][r] = code_weight_t<NFT>(code, bwt + 16 * nt + c, PW);
+            if (WIDE) {
+                unsigned hi = kcode_hi[4 * KS + r];
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) ws[nt][r] *= code_weight(hi, bwt + 16 * nt + c, PW);
+            }
+        }
+    };
+    if (!WIDE && dims.d - plan.split <= 2) tail_weights(std::integral_constant<int, 2>{});
+    else tail_weights(std::integral_constant<int, 4>{});
 
     // ---- main loop over row tiles; every PCX_CHUNK_TILES tiles the per-lane chunk sum cs
     //      is folded into the per-lane total (or stored, in a split launch)
@@ -328,18 +367,44 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
     const gptr_t tf = frag + lane;
     const int t_begin = ch0 * PCX_CHUNK_TILES;
     const int t_end = (ch1 * PCX_CHUNK_TILES < plan.MT) ? ch1 * PCX_CHUNK_TILES : plan.MT;
-    const bool split = gridDim.y > 1;
     // Long narrow plans (the 11^5 headline: 30 k-steps) run a hand-pipelined tile loop: fragment
     // loads stay DEPTH k-steps ahead ACROSS tile boundaries (the first DEPTH fragments of tile t+1
-    // are fetched during the tail of tile t), the row codes of tile t+1 are fetched at the top of
-    // tile t (loads return in order: waiting for codes issued behind a tile's own fragment loads
-    // drained them all, once per tile), and the head-weight look-ups of row j are issued at k-step
-    // 2j and multiplied two k-steps later.  The seed of tile t+1 (R > 0) is fetched with its first fragments.
+    // are fetched during the tail of tile t), the head-weight look-ups of row j are issued at k-step
+    // 2j (2j + 1 for a wide plan's second word) and multiplied two k-steps later, and the row codes
+    // of tile t+1 are fetched at k-step CODE_STEP of tile t, behind the last look-up, straight into
+    // the registers the look-ups read: no second set and no copies, and (loads return in order) by
+    // the top of tile t+1 they are the oldest loads in flight, so waiting for them drains nothing.
+    // The narrow instantiations read pre-scaled row offsets instead of row codes (load_row_offs).
+    // The seed of tile t+1 (R > 0) is fetched with its first fragments.
     // Fences keep hipcc from sinking the loads back to their uses.  Same arithmetic in the same
     // order as the plain loop below: identical results.
     constexpr bool PIPELINED = (KS >= 12);
     constexpr int DEPTH = 6;           // <= 12 <= KS: the ring never wraps a tile (A/B on one box: 4 -0.6 %, 8 -0.3 %)
-    unsigned cn[4] = {0u, 0u, 0u, 0u}, cnh[4] = {0u, 0u, 0u, 0u};
+    constexpr bool OFFS = PIPELINED && !WIDE && !G0;     // row offsets (two fields per word) instead of row codes
+    constexpr bool CODE2 = WIDE || (OFFS && NF >= 3);    // a second word per row
+    constexpr int CODE_STEP = 8;       // the last look-up is at k-step 6 (7: wide); < 12 <= KS
+    unsigned cc[4] = {0u, 0u, 0u, 0u}, cch[4] = {0u, 0u, 0u, 0u};
+    auto load_codes = [&](long t) {
+        const pcx_u4 q = OFFS ? load_row_offs(rowoff, t, g, 0) : load_row_codes(rowcode, t, g);
+        pcx_u4 qh = q;
+        if constexpr (WIDE) qh = load_row_codes(rowcode_hi, t, g);
+        else if constexpr (CODE2) qh = load_row_offs(rowoff, t, g, 1);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            cc[j] = q.v[j];
+            if (CODE2) cch[j] = qh.v[j];
+        }
+    };
+    // table entry of field f of row j for column tile nt
+    auto head_entry = [&](int j, int nt, int f) -> double {
+        if constexpr (OFFS) {
+            const unsigned word = f < 2 ? cc[j] : cch[j];
+            const unsigned off = (f & 1) ? (word >> 16) : (word & 0xffffu);
+            return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(bw + 16 * nt + c) + off);
+        } else {
+            return bw[(size_t)((cc[j] >> (8 * f)) & 255u) * PW + 16 * nt + c];
+        }
+    };
     double head[DEPTH];
     // The accumulators start a tile at its seed: +0.0 (R = 0), else column 0 (then 1) as FMAs onto +0.0.  The pipelined
     // loop fetches the seed of tile t+1 with that tile's first fragments and forms it when tile t's epilogue has read
@@ -360,16 +425,7 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
     for (int i = 0; i < DEPTH; ++i) head[i] = 0.0;
     if (PIPELINED && t_begin < t_end) {
         if constexpr (R > 0) seed_acc(load_seed<R>(seed, t_begin, g));
-        {
-            const pcx_u4 q = load_row_codes(rowcode, t_begin, g);
-            pcx_u4 qh = q;
-            if (WIDE) qh = load_row_codes(rowcode_hi, t_begin, g);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                cn[j] = q.v[j];
-                if (WIDE) cnh[j] = qh.v[j];
-            }
-        }
+        load_codes(t_begin);
 #pragma unroll
         for (int i = 0; i < DEPTH; ++i) head[i] = tf[((size_t)t_begin * KS + i) * 64];
     }
@@ -385,20 +441,8 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
             const int t_next = (t + 1 < t_end) ? t + 1 : t;
             const gptr_t tn = tf + (size_t)t_next * KS * 64;
             double ring[DEPTH];
-            unsigned cc[4], cch[4];
 #pragma unroll
             for (int i = 0; i < DEPTH; ++i) ring[i] = head[i];
-            {
-                const pcx_u4 q = load_row_codes(rowcode, t_next, g);
-                pcx_u4 qh = q;
-                if (WIDE) qh = load_row_codes(rowcode_hi, t_next, g);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    cc[j] = cn[j];
-                    cn[j] = q.v[j];
-                    if (WIDE) { cch[j] = cnh[j]; cnh[j] = qh.v[j]; }
-                }
-            }
             double wr[4][NT][4];          // raw table entries of row j, looked up at k-step 2j
             double wh[4][NT][4];          // ... and of its second code word (wide plans), at k-step 2j + 1
 #pragma unroll
@@ -409,6 +453,7 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
                 if constexpr (R > 0) {          // with tile t+1's first fragments: live for DEPTH k-steps only
                     if (s == KS - DEPTH) sdn = load_seed<R>(seed, t_next, g);
                 }
+                if (s == CODE_STEP) load_codes(t_next);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     if (s == 2 * j) {
@@ -416,7 +461,7 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
                         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
                             for (int f = 0; f < (NF < 4 ? NF : 4); ++f)          // dead fields name the ones row: not read
-                                wr[j][nt][f] = bw[(size_t)((cc[j] >> (8 * f)) & 255u) * PW + 16 * nt + c];
+                                wr[j][nt][f] = head_entry(j, nt, f);
                     }
                     if (s == 2 * j + 2) {
 #pragma unroll
@@ -495,7 +540,7 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
                 for (int nt = 0; nt < NT; ++nt) {
                     long pidx = base + 16 * nt + c;
                     if (pidx < N)
-                        partial[(((size_t)blockIdx.z * nchunks + ch) * 4 + g) * (size_t)N + pidx] = cs[nt];
+                        partial[(((size_t)blockIdx.z * nchunks + ch) * 4 + g) * (size_t)part_n + (pidx - part_p0)] = cs[nt];
                 }
             }
 #pragma unroll
@@ -721,23 +766,38 @@ k_bary_mfma4(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
 
 // Finishes a split launch with exactly the additions of a non-split one: per lane group g
 // the chunk sums in chunk order, s_g = ((cs_0 + cs_1) + cs_2) + ..., then (s0 + s1) + (s2 + s3).
-// partial layout: [spec][chunk][group][point].
-static __global__ void k_bary_reduce(const double *__restrict__ partial, double *__restrict__ out, long N,
-                              int nchunks, int nspec, long ostride, long ooff,
-                              const int *__restrict__ perm) {
-    long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= N * nspec) return;
-    long p = idx % N;
-    int z = (int)(idx / N);
-    const double *src = partial + (size_t)z * nchunks * 4 * (size_t)N + p;
-    double sg[4];
-    for (int g = 0; g < 4; ++g) {
-        double t = 0.0;
-        for (int ch = 0; ch < nchunks; ++ch) t += src[((size_t)ch * 4 + g) * (size_t)N];
-        sg[g] = t;
+// partial layout: [spec][chunk][group][point]; its N points are the launch's points p0 .. p0 + N (p0 > 0: the
+// tail blocks of a tail split).  A workgroup takes 64 (point, spec) pairs, wave g the chain of lane group g -- the
+// four chains of a point side by side and eight loads of each in flight (one thread per point walking all 4 nchunks
+// values took 22 us for the 17,024 tail points of the headline batch, as long as the split saved).
+static __global__ void __launch_bounds__(256)
+k_bary_reduce(const double *__restrict__ partial, double *__restrict__ out, long N, int nchunks, int nspec,
+              long ostride, long ooff, const int *__restrict__ perm, long p0) {
+    __shared__ double sg[4][64];
+    const int lane = threadIdx.x & 63;
+    const int g = threadIdx.x >> 6;
+    const long idx = (long)blockIdx.x * 64 + lane;
+    const bool valid = idx < N * nspec;
+    const long p = valid ? idx % N : 0;
+    const int z = valid ? (int)(idx / N) : 0;
+    const double *src = partial + ((size_t)z * nchunks * 4 + g) * (size_t)N + p;
+    const size_t step = (size_t)4 * (size_t)N;          // one chunk on
+    double t = 0.0;
+    int ch = 0;
+    for (; ch + 8 <= nchunks; ch += 8) {
+        double v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = src[(size_t)(ch + i) * step];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) t += v[i];
     }
-    long row = perm ? (long)perm[p] : p;
-    out[row * ostride + ooff + z] = (sg[0] + sg[1]) + (sg[2] + sg[3]);
+    for (; ch < nchunks; ++ch) t += src[(size_t)ch * step];
+    sg[g][lane] = t;
+    __syncthreads();
+    if (g == 0 && valid) {
+        long row = perm ? (long)perm[p0 + p] : p0 + p;
+        out[row * ostride + ooff + z] = (sg[0][lane] + sg[1][lane]) + (sg[2][lane] + sg[3][lane]);
+    }
 }
 
 // ---------------------------------------------------------------------------------

@@ -17,10 +17,30 @@ static size_t mfma_lds_bytes(const BaryDims &dm, int nt) {
     return (size_t)4 * (dm.sum_n + 2) * 16 * nt * sizeof(double);
 }
 
+// Workgroups of `kern` the device holds at once (256 threads, `lds` bytes each): the occupancy query times the
+// compute units, at most the 512 (256 CUs at two per CU) every launch was sized for before the query existed.
+static int resident_slots(const void *kern, size_t lds, int device, int *slots) {
+    int per_cu = 0, cus = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds));
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    *slots = (int)std::max<long>(1, std::min<long>(512, (long)per_cu * cus));
+    return PCX_OK;
+}
+
 // One MFMA launch for m specs (frag_tab: device table of m fragment pointers).  Small
 // batches are split over grid.y (chunks of row tiles) so that a handful of points still
 // uses the whole chip; the per-chunk totals are then added by k_bary_reduce in the fixed
 // chunk order, which makes every result independent of the batch size.
+// Large batches end in a ragged round: `blocks` workgroups over `slots` resident ones leave tail = blocks mod slots
+// for the last round.  When that round is at most half full (and m = 1: launches of several specs keep their
+// geometry), each tail block is walked by P = min(nchunks, slots / tail) workgroups of the SAME grid, a contiguous
+// range of chunks each, and k_bary_reduce finishes the tail points -- the additions of a split launch, so the same
+// bits.  The finishing kernel costs about 7 us in the stream (9^4: 0.326 -> 0.334 ms per 10^6 points with the split, 7^5
+// level, 11^5 -0.8 %), so the split is taken where a workgroup's walk -- MT (KS + 5) NT matrix-instruction slots, the
+// planner's price of a tile -- is long enough that a third of it outweighs that: from kTailMinWork on (about 0.1 ms; 11^5
+// is 5,880, 7^5 748, 9^4 300).  PCX_BARY_TAIL=0 at create keeps the one-workgroup-per-block geometry, =2 splits wherever the
+// geometry allows (tests).
+static const long kTailMinWork = 2048;
 template <int KS, int NT, bool WIDE, int NF, int R>
 static int launch_mfma_t(pcx_bary *h, const double *const *frag_tab, int m, const double *d_pts, long N,
                          double *d_out, long ostride, long ooff, hipStream_t st, Scratch *split_scratch,
@@ -35,26 +55,51 @@ static int launch_mfma_t(pcx_bary *h, const double *const *frag_tab, int m, cons
     if (blocks > 0x7fffffffL) return fail(PCX_ERR_UNSUPPORTED, "batch too large for one launch");
     int nchunks = (h->plan.MT + PCX_CHUNK_TILES - 1) / PCX_CHUNK_TILES;
     int nsplit = 1, cps = nchunks;
-    const long want = 512;   // workgroups that fill 256 CUs at two per CU
+    if (KS >= 12 && !WIDE && !h->d_rowoff[NT - 1]) return fail(PCX_ERR_UNSUPPORTED, "row offsets of the pipelined loop were not built");
+    if (!h->slots[NT - 1]) {
+        int rc = resident_slots((const void *)kern, lds, h->device, &h->slots[NT - 1]);
+        if (rc) return rc;
+    }
+    if (h->slots_query) return PCX_OK;
+    const long want = h->slots[NT - 1];   // workgroups that fill the device
     if (allow_split && blocks * m < want && nchunks > 1) {
         nsplit = (int)std::min<long>(nchunks, (want + blocks * m - 1) / (blocks * m));
         cps = (nchunks + nsplit - 1) / nsplit;
         nsplit = (nchunks + cps - 1) / cps;
     }
+    BaryTail tail{0, 0, 0};
+    long grid_x = blocks;
+    const long tail_blocks = blocks % want;
+    const bool tail_pays = h->tail_mode == 2 || (h->tail_mode == 1 && (long)h->plan.MT * (KS + 5) * NT >= kTailMinWork);
+    if (tail_pays && allow_split && m == 1 && nsplit == 1 && nchunks > 1 && blocks > want && tail_blocks > 0 &&
+        2 * tail_blocks <= want) {
+        int P = (int)std::min<long>(nchunks, want / tail_blocks);
+        tail.cpp = (nchunks + P - 1) / P;
+        P = (nchunks + tail.cpp - 1) / tail.cpp;       // no empty pieces
+        if (P > 1 && blocks + want <= 0x7fffffffL) {
+            tail.first = (int)(blocks - tail_blocks);
+            tail.P = P;
+            grid_x = tail.first + tail_blocks * P;     // <= blocks + slots
+        }
+    }
+    h->last_tail_P = tail.P;
+    h->last_tail_blocks = tail.P ? (int)tail_blocks : 0;
+    const long part_p0 = tail.P ? (long)tail.first * per_wg : 0;    // first point `partial` holds
     double *partial = nullptr;
-    if (nsplit > 1) {
-        int rc = split_scratch->reserve((size_t)m * nchunks * 4 * (size_t)N * sizeof(double));
+    if (nsplit > 1 || tail.P) {
+        int rc = split_scratch->reserve((size_t)m * nchunks * 4 * (size_t)(N - part_p0) * sizeof(double));
         if (rc) return rc;
         partial = (double *)split_scratch->ptr;
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)nsplit, (unsigned)m), dim3(256), lds, st,
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid_x, (unsigned)nsplit, (unsigned)m), dim3(256), lds, st,
                        h->dims, h->plan, h->d_nodes, h->d_wts, frag_tab, h->d_rowcode, h->d_kcode,
-                       h->d_rowcode_hi, h->d_kcode_hi, d_pts, d_out, N, ostride, ooff, cps, partial, perm, BaryG0{}, nullptr);
+                       h->d_rowcode_hi, h->d_kcode_hi, d_pts, d_out, N, ostride, ooff, cps, partial, perm, BaryG0{}, nullptr,
+                       h->d_rowoff[NT - 1], tail);
     HIP_TRY(hipGetLastError());
-    if (nsplit > 1) {
-        long cnt = N * m;
-        hipLaunchKernelGGL(k_bary_reduce, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, partial, d_out,
-                           N, nchunks, m, ostride, ooff, perm);
+    if (nsplit > 1 || tail.P) {
+        long cnt = (N - part_p0) * m;
+        hipLaunchKernelGGL(k_bary_reduce, dim3((unsigned)((cnt + 63) / 64)), dim3(256), 0, st, partial, d_out,
+                           N - part_p0, nchunks, m, ostride, ooff, perm, part_p0);
         HIP_TRY(hipGetLastError());
     }
     return PCX_OK;
@@ -165,7 +210,7 @@ static int launch_g0_t(pcx_bary *h, const DerivedTensor &base, const BaryG0 &gs,
     const int nchunks = (plan.MT + PCX_CHUNK_TILES - 1) / PCX_CHUNK_TILES;
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks, 1, 1), dim3(256), lds, st, h->dims, plan, h->d_nodes, h->d_wts,
                        (const double *const *)base.slot_g0, h->d_rowcode_g0, h->d_kcode, nullptr, nullptr, d_pts, d_out, N,
-                       ostride, ooff, nchunks, nullptr, nullptr, gs, h->d_diff + h->doff[0]);
+                       ostride, ooff, nchunks, nullptr, nullptr, gs, h->d_diff + h->doff[0], nullptr, BaryTail{0, 0, 0});
     HIP_TRY(hipGetLastError());
     return PCX_OK;
 }

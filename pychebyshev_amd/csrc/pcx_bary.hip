@@ -97,6 +97,7 @@ extern "C" int pcx_bary_destroy(pcx_bary *h) {
     (void)hipFree(h->d_rowcode); (void)hipFree(h->d_kcode);
     (void)hipFree(h->d_rowcode_hi); (void)hipFree(h->d_kcode_hi);
     (void)hipFree(h->d_rowcode_g0);
+    (void)hipFree(h->d_rowoff[0]); (void)hipFree(h->d_rowoff[1]);
     for (pcx_bary *&r : h->rot) { if (r) pcx_bary_destroy(r); r = nullptr; }
     h->stage.release();
     h->s_rot.release(); h->s_rot2.release();
@@ -198,6 +199,7 @@ extern "C" int pcx_bary_create(int device, int d, const int32_t *n_nodes, const 
 
     // MFMA plan + row/k codes
     { const char *e = getenv("PCX_BARY_SEED"); h->seed = !(e && e[0] == '0'); }
+    { const char *e = getenv("PCX_BARY_TAIL"); h->tail_mode = (e && e[0] == '0') ? 0 : ((e && e[0] == '2') ? 2 : 1); }
     h->mfma_ok = plan_mfma(h->dims, h->plan, h->seed);
     if (h->mfma_ok) {
         // two column tiles per wave while the B operands fit the register file beside them: up to 32 k-steps, 36 and 40 with
@@ -301,6 +303,23 @@ extern "C" int pcx_bary_create(int device, int d, const int32_t *n_nodes, const 
         }
         CREATE_TRY(hipMalloc((void **)&h->d_rowcode, rowcode.size() * sizeof(unsigned)));
         CREATE_TRY(hipMemcpy(h->d_rowcode, rowcode.data(), rowcode.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+        // the pipelined loop of the narrow instantiations (k_bary_mfma, KS >= 12) reads row OFFSETS: every field as
+        // the LDS byte offset row * PW * 8 of its table row, 16 bits each (rows <= 255, PW <= 32), two 16-byte words
+        // per (tile, lane group): [t][g][fields 0 | 1 << 16, fields 2 | 3 << 16][j].  One table per PW = 16 NT.
+        if (!h->wide && p.KS >= 12) {
+            std::vector<unsigned> offs((size_t)p.MT * 32);
+            for (int nt = 1; nt <= 2; ++nt) {
+                const unsigned sc = 16u * nt * sizeof(double);
+                for (size_t q = 0; q < (size_t)p.MT * 4; ++q)              // q = 4 t + g
+                    for (int j = 0; j < 4; ++j) {
+                        const unsigned code = rowcode[4 * q + j];
+                        offs[8 * q + j] = ((code & 255u) * sc) | ((((code >> 8) & 255u) * sc) << 16);
+                        offs[8 * q + 4 + j] = (((code >> 16) & 255u) * sc) | (((code >> 24) * sc) << 16);
+                    }
+                CREATE_TRY(hipMalloc((void **)&h->d_rowoff[nt - 1], offs.size() * sizeof(unsigned)));
+                CREATE_TRY(hipMemcpy(h->d_rowoff[nt - 1], offs.data(), offs.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+            }
+        }
         // dim-0 groups: head = dimension 0 x (dimensions 1 .. split-1); the rows of one i0 form a slab padded to whole
         // tiles.  Needs two column tiles per wave (large batches only), narrow codes, and room for two n0-vectors
         // per point in the tail part of the LDS table (dead once the B operands are in registers); n0 <= 16 bounds the
@@ -1594,6 +1613,38 @@ extern "C" int pcx_bary_kernel_info(pcx_bary *h, int32_t *info) {
                          : (256 / h->lpp) * h->dims.sum_n * 8;
     info[4] = h->mfma_ok ? 64 * h->nt : 256 / h->lpp;
     info[5] = h->mfma_ok ? h->plan.split : h->dims.d - 1;
+    return PCX_OK;
+    PCX_API_END
+}
+
+// [0] workgroups of the row-code MFMA kernel the device holds at once (launch_mfma_t's `slots`, for batches of 65,536
+// points or more), [1] points per workgroup there, [2] chunks of row tiles, [3] the tail-split mode (PCX_BARY_TAIL:
+// 0 never, 1 where it pays, 2 wherever the geometry allows), [4] workgroups per tail block in the latest row-code launch (0: it was not split) and
+// [5] its tail blocks.  All zero when launches do not take the row-code form.
+extern "C" int pcx_bary_tail_info(pcx_bary *h, int32_t *info) {
+    PCX_API_BEGIN
+    if (!h || !info) return fail(PCX_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < 6; ++i) info[i] = 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->mfma_ok || h->kfold_ok || h->grid_ok) return PCX_OK;
+    if (!h->slots[h->nt - 1]) {
+        int rc = use_device(h->device);
+        if (rc) return rc;
+        h->slots_query = true;           // the launch tables know the instantiation: they fill h->slots and return
+        switch (h->plan.R) {
+        case 1: rc = bary_launch_rowcode_seed1(h, nullptr, 1, nullptr, 65536, nullptr, 1, 0, h->stream, nullptr, nullptr); break;
+        case 2: rc = bary_launch_rowcode_seed2(h, nullptr, 1, nullptr, 65536, nullptr, 1, 0, h->stream, nullptr, nullptr); break;
+        default: rc = launch_rowcode<0>(h, nullptr, 1, nullptr, 65536, nullptr, 1, 0, h->stream, nullptr, nullptr);
+        }
+        h->slots_query = false;
+        if (rc) return rc;
+    }
+    info[0] = h->slots[h->nt - 1];
+    info[1] = 64 * h->nt;
+    info[2] = (h->plan.MT + PCX_CHUNK_TILES - 1) / PCX_CHUNK_TILES;
+    info[3] = h->tail_mode;
+    info[4] = h->last_tail_P;
+    info[5] = h->last_tail_blocks;
     return PCX_OK;
     PCX_API_END
 }

@@ -49,6 +49,13 @@ struct pcx_bary {
     unsigned *d_rowcode = nullptr, *d_kcode = nullptr;
     unsigned *d_rowcode_hi = nullptr, *d_kcode_hi = nullptr;   // fields 4..7 (wide plans only)
     bool wide = false;      // more than four head or tail dimensions
+    // pipelined narrow plans (KS >= 12): the row codes as pre-scaled LDS byte offsets, one table per PW = 16, 32 (load_row_offs)
+    unsigned *d_rowoff[2] = {nullptr, nullptr};
+    int tail_mode = 1;               // tail split of large launches (launch_mfma_t): 1 where the row-tile walk is long enough to pay
+                                     // for the second kernel; PCX_BARY_TAIL=0 at create: never, =2: wherever the geometry allows
+    int slots[2] = {0, 0};           // resident workgroups of the row-code kernel per NT = 1, 2; queried at the first launch
+    int last_tail_P = 0, last_tail_blocks = 0;   // geometry of the latest launch_mfma_t (pcx_bary_tail_info: the tests' witness)
+    bool slots_query = false;        // the launch tables only fill `slots` (pcx_bary_tail_info)
     // short plans: row tiles = RA x RB blocks of the last two head dimensions, no row codes (bary_grid_kernels.h);
     // the fragment image of every derivative tensor is then packed in that order
     bool grid_ok = false;

@@ -87,6 +87,14 @@ struct BaryG0 {
     int col[PCX_G0_MAX];     // output column of member s
 };
 
+// Tail split of a k_bary_mfma launch (bary_mfma_launch.h): the point blocks from `first` on are walked by P workgroups
+// each, `cpp` chunks of row tiles per workgroup.  P = 0: none.
+struct BaryTail {
+    int first;
+    int P;
+    int cpp;
+};
+
 // "Plain" (C-order) tensors carry PCX_PLAIN_PAD zeroed doubles behind their end: the lane-per-point kernels read a
 // row with a fixed-width run of scalar loads that may reach past the last row.
 #define PCX_PLAIN_PAD 64
