@@ -211,6 +211,26 @@ int pcx_bary_grid_info(pcx_bary *h, int32_t *info_out /* 4 ints */);
  * launch (0: it kept one workgroup per block), [5] its tail blocks.  All zero when launches take another form. */
 int pcx_bary_tail_info(pcx_bary *h, int32_t *info_out /* 6 ints */);
 int pcx_bary_stream(pcx_bary *h, void **stream);
+/* Box integrals, batched (the reference's integrate(dims, bounds) then vectorized_eval(point), one row per call there):
+ * out[r] = integral of the interpolant over [lo, hi] in every integrated dimension of row r, at the row's coordinates in
+ * the kept ones.  flags = d entries (0 kept, 1 integrated; anything else is PCX_ERR_INVALID); lo / hi = the model's domain,
+ * d each (a handle does not know it; lo < hi, else PCX_ERR_INVALID).  rows is N x (d + m) row-major, m = number of flags
+ * set: for dimensions 0 .. d-1 in order one double (the coordinate) for a kept dimension, two (lo, hi) for an integrated
+ * one.  m = 0 is the value.  A kept coordinate within 1e-14 of a node takes that node's slice, as an evaluation does; an
+ * integrated dimension takes the sub-interval Fejer-1 weights of its (lo, hi), and a row with lo == hi gives exactly 0.
+ * Rows are not checked against the domain.  N = 0 returns PCX_OK without a launch.  One launch per piece of the batch and
+ * one workgroup per block of rows: a result does not depend on the batch size.  Handles whose fragment image is the
+ * row-code packing run v_mfma_f64_16x16x4_f64 on that image (k_bary_box_mfma); every other handle, a handle whose
+ * evaluation prefers a lane-per-point kernel while no variant is set, and every handle after pcx_bary_set_kernel(h, 1)
+ * run the any-shape form on the plain tensor (k_bary_box_rows).  The _dev form takes device
+ * rows and results and queues on `stream` (NULL: the handle's); it returns without waiting. */
+int pcx_bary_box_batch(pcx_bary *h, const int32_t *flags, const double *lo, const double *hi, const double *rows,
+                       int64_t N, double *out);
+int pcx_bary_box_batch_dev(pcx_bary *h, const int32_t *flags, const double *lo, const double *hi, const double *d_rows,
+                           int64_t N, double *d_out, void *stream);
+/* The form a box call takes now: [0] 1 = MFMA form, 0 = rows form; [1] k-steps per row tile; [2] seed columns R;
+ * [3] 1 = wide codes (more than four head or tail dimensions).  [1] .. [3] are 0 for the rows form. */
+int pcx_bary_box_info(pcx_bary *h, int32_t *info_out /* 4 ints */);
 
 /* ---- piecewise (spline) interpolant ---------------------------------------- */
 /* ChebyshevSpline (spline.py:35-700): per-dimension sorted interior knots (concatenated)

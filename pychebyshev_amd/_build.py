@@ -24,6 +24,7 @@ SOURCES = {
     "pcx_bary.hip": HOST_H + ["pcx_bary_internal.h", "bary_kernels.h", "bary_mfma_launch.h", "gather_kernels.h", "sobol_kernels.h"],
     "pcx_bary_seed1.hip": HOST_H + ["pcx_bary_internal.h", "bary_kernels.h", "bary_mfma_launch.h"],
     "pcx_bary_seed2.hip": HOST_H + ["pcx_bary_internal.h", "bary_kernels.h", "bary_mfma_launch.h"],
+    "pcx_bary_box.hip": HOST_H + ["pcx_bary_internal.h", "bary_kernels.h", "bary_box_kernels.h"],
     "pcx_bary_grid.hip": HOST_H + ["pcx_bary_internal.h", "bary_grid_kernels.h", "bary_weights.h"],
     "pcx_bary_kfold.hip": HOST_H + ["pcx_bary_internal.h", "bary_kfold_kernels.h"],
     "pcx_spline.hip": HOST_H + ["pcx_bary_internal.h", "gather_kernels.h", "route_kernels.h"],

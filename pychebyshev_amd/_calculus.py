@@ -179,3 +179,122 @@ def run_single(fibre_fn, batch_fn, n: int, mode: str, nodes, weights, diff, doma
         return roots_1d(values, domain)
     return optimize_1d(values, nodes, weights, diff, domain, mode)
 
+
+# ---------------------------------------------------------------------------------------------- box integrals
+def box_rows(d: int, domain, dims, bounds, points):
+    """Validated arguments of an ``integrate_batch`` call on a ``d``-dimensional model over ``domain`` -> (flags by
+    dimension, rows ``(N, d + m)``): ``bounds`` broadcast to ``(N, m, 2)`` and clipped to the domain, ``points``
+    ``(N, d - m)``, both in increasing dimension order.  A row holds, per dimension, the coordinate of a kept
+    dimension or ``lo, hi`` of an integrated one (``pcx_bary_box_batch`` / ``pcx_tt_box_batch``).  Raises before any
+    device call."""
+    if dims is None:
+        dims = list(range(d))
+    elif isinstance(dims, (int, np.integer)):
+        dims = [int(dims)]
+    else:
+        dims = sorted(set(int(v) for v in dims))
+    if any(u < 0 or u >= d for u in dims):
+        raise ValueError(f"dims contains out-of-range index (num_dimensions={d}, dims={dims})")
+    m = len(dims)
+    if m < 1:
+        raise ValueError("dims must name at least one dimension")
+    udom = np.asarray(domain, dtype=float)
+    kept = [u for u in range(d) if u not in dims]
+    n_rows = []
+    if bounds is None:
+        bnd = udom[dims][None, :, :]
+    else:
+        bnd = np.asarray(bounds, dtype=float)
+        if m == 1 and bnd.ndim == 1:
+            bnd = bnd[None, :]
+        if bnd.ndim == 2 and bnd.shape == (m, 2):
+            bnd = bnd[None, :, :]
+        elif m == 1 and bnd.ndim == 2 and bnd.shape[1] == 2:
+            bnd = bnd[:, None, :]
+        if bnd.ndim != 3 or bnd.shape[1:] != (m, 2):
+            raise ValueError(f"bounds must broadcast to (N, {m}, 2), got shape {np.shape(bounds)}")
+        if bnd.shape[0] != 1:
+            n_rows.append(("bounds", bnd.shape[0]))
+    if points is None:
+        if kept:
+            raise ValueError(f"points is required: {len(kept)} dimensions are kept")
+        pts = None
+    else:
+        pts = np.asarray(points, dtype=float)
+        if pts.ndim != 2 or pts.shape[1] != len(kept):
+            raise ValueError(f"points must have shape (N, {len(kept)}), got {pts.shape}")
+        n_rows.append(("points", pts.shape[0]))
+    if len(n_rows) == 2 and n_rows[0][1] != n_rows[1][1]:
+        raise ValueError(f"bounds has {n_rows[0][1]} rows but points has {n_rows[1][1]}")
+    N = n_rows[0][1] if n_rows else 1
+    bnd = np.broadcast_to(bnd, (N, m, 2))
+    lo, hi = bnd[:, :, 0], bnd[:, :, 1]
+    a, b = udom[dims, 0][None, :], udom[dims, 1][None, :]
+    bad = (lo > hi) | (lo < a - 1e-14) | (hi > b + 1e-14) | ~np.isfinite(lo) | ~np.isfinite(hi)
+    if bad.any():
+        r = int(np.argmax(bad.any(axis=1)))
+        j = int(np.argmax(bad[r]))
+        if lo[r, j] > hi[r, j]:
+            raise ValueError(f"bounds lo={lo[r, j]} > hi={hi[r, j]} for dim {dims[j]} (row {r})")
+        raise ValueError(f"bounds ({lo[r, j]}, {hi[r, j]}) outside domain [{udom[dims[j], 0]}, {udom[dims[j], 1]}] "
+                         f"for dim {dims[j]} (row {r})")
+    if pts is not None and pts.size:
+        pa, pb = udom[kept, 0][None, :], udom[kept, 1][None, :]
+        bad = ~((pts >= pa) & (pts <= pb))
+        if bad.any():
+            r = int(np.argmax(bad.any(axis=1)))
+            j = int(np.argmax(bad[r]))
+            raise ValueError(f"point value {pts[r, j]} for dim {kept[j]} is outside domain "
+                             f"[{udom[kept[j], 0]}, {udom[kept[j], 1]}] (row {r})")
+    flags = np.zeros(d, dtype=np.int32)
+    flags[dims] = 1
+    rows = np.empty((N, d + m))
+    col = 0
+    for u in range(d):
+        if flags[u]:
+            j = dims.index(u)
+            rows[:, col] = np.maximum(lo[:, j], a[0, j])         # clipped to the domain, as integrate() does
+            rows[:, col + 1] = np.minimum(hi[:, j], b[0, j])
+            col += 2
+        else:
+            rows[:, col] = pts[:, kept.index(u)]
+            col += 1
+    return flags, rows
+
+
+def box_quadrature_matrix(n: int) -> np.ndarray:
+    """``Q_n`` of the device box integrals (``csrc/bary_box_kernels.h``): ``Q_n @ mu`` are the sub-interval Fejer-1
+    weights at the ``n`` ascending type-I nodes for the moments ``mu_q`` of ``T_q`` over the sub-interval --
+    ``Q[j, 0] = 1 / n``, ``Q[j, q] = (2 / n) cos(pi q (2 (n - 1 - j) + 1) / (2 n))`` (the reference's DCT-III,
+    reversed)."""
+    j = np.arange(n)[:, None]
+    q = np.arange(n)[None, :]
+    Q = (2.0 / n) * np.cos(np.pi * q * (2 * (n - 1 - j) + 1) / (2.0 * n))
+    Q[:, 0] = 1.0 / n
+    return Q
+
+
+def box_moments(n: int, t_lo: float, t_hi: float) -> np.ndarray:
+    """``mu_q = F_q(t_hi) - F_q(t_lo)`` for ``q < n`` with the antiderivatives ``F_0 = t``, ``F_1 = t^2 / 2``,
+    ``F_q = (T_{q+1} / (q + 1) - T_{q-1} / (q - 1)) / 2``: every ``F_q`` by the same operations at both ends, as the
+    device forms them, so ``t_lo == t_hi`` gives exactly zeros."""
+    mu = np.zeros(n)
+    mu[0] = t_hi - t_lo
+    if n > 1:
+        mu[1] = 0.5 * (t_hi * t_hi) - 0.5 * (t_lo * t_lo)
+    am, ac = t_lo, 2.0 * t_lo * t_lo - 1.0
+    bm, bc = t_hi, 2.0 * t_hi * t_hi - 1.0
+    for q in range(2, n):
+        ap, bp = 2.0 * t_lo * ac - am, 2.0 * t_hi * bc - bm
+        c1, c2 = 1.0 / (q + 1), 1.0 / (q - 1)
+        mu[q] = 0.5 * (bp * c1 - bm * c2) - 0.5 * (ap * c1 - am * c2)
+        am, ac = ac, ap
+        bm, bc = bc, bp
+    return mu
+
+
+def box_weights(n: int, a: float, b: float, lo: float, hi: float) -> np.ndarray:
+    """Host restatement of ``box_weights_1d``: the weight vector of an integrated dimension with ``n`` nodes on
+    ``[a, b]`` for the sub-interval ``[lo, hi]``, ``(b - a) / 2 . Q_n mu``."""
+    scale = 2.0 / (b - a)
+    return 0.5 * (b - a) * (box_quadrature_matrix(n) @ box_moments(n, (lo - a) * scale - 1.0, (hi - a) * scale - 1.0))

@@ -94,6 +94,9 @@ SIGNATURES = {
     "pcx_bary_grid_info": (_I, [_V, c_i32p]),
     "pcx_bary_tail_info": (_I, [_V, c_i32p]),
     "pcx_bary_stream": (_I, [_V, c_vpp]),
+    "pcx_bary_box_batch": (_I, [_V, c_i32p, c_f64p, c_f64p, c_f64p, _L, c_f64p]),
+    "pcx_bary_box_batch_dev": (_I, [_V, c_i32p, c_f64p, c_f64p, _V, _L, _V, _V]),
+    "pcx_bary_box_info": (_I, [_V, c_i32p]),
     "pcx_spline_create": (_I, [_I, _I, c_i32p, c_f64p, c_vpp, _I, c_vpp]),
     "pcx_spline_destroy": (_I, [_V]),
     "pcx_spline_eval_batch": (_I, [_V, c_f64p, _L, c_i32p, c_f64p]),

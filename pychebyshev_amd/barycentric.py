@@ -742,6 +742,33 @@ class ChebyshevApproximation(ErgonomicsMixin, DerivativeIdMixin):
             return float(tensor)
         return self._reduced(tensor, nodes, weights, diffs, domain, n_nodes)
 
+    def integrate_batch(self, dims, bounds=None, points=None) -> np.ndarray:
+        """Box integrals for a batch of rows (extension; the reference computes one with ``integrate(dims, bounds)``
+        and then ``vectorized_eval(point)``): ``out[r]`` is the integral over ``bounds[r]`` in the dimensions ``dims``
+        at ``points[r]`` in the others.  Arguments as :meth:`ChebyshevTT.integrate_batch`: ``bounds`` broadcasts to
+        ``(N, m, 2)`` with the integrated dimensions in increasing order (``(m, 2)``, or ``(2,)`` for one dimension,
+        serves every row; ``None`` is the whole domain); ``points`` is ``(N, d - m)``, the kept dimensions in
+        increasing order, and may be ``None`` only when every dimension is integrated.  One launch on the device
+        (``pcx_bary_box_batch``): the contraction of an evaluation with the sub-interval Fejer-1 weights of the row's
+        ``(lo, hi)`` in the integrated dimensions.  Host arrays only; the first device handle takes the batch."""
+        from ._calculus import box_rows
+        if self.tensor_values is None:
+            raise RuntimeError("Call build() first")
+        flags, rows = box_rows(self.num_dimensions, self.domain, dims, bounds, points)
+        return self._box_batch(flags, rows)
+
+    def _box_batch(self, flags: np.ndarray, rows: np.ndarray) -> np.ndarray:
+        """``pcx_bary_box_batch`` over validated rows (see :func:`pychebyshev_amd._calculus.box_rows`)."""
+        rows = _lib.f64(rows)
+        out = np.empty(rows.shape[0])
+        if rows.shape[0]:
+            m = self._model()
+            dom = np.asarray(self.domain, dtype=float)
+            lo, hi = _lib.f64(dom[:, 0]), _lib.f64(dom[:, 1])
+            _lib.check(m.lib.pcx_bary_box_batch(m.handle, _lib.p_i32(_lib.i32(flags)), _lib.p_f64(lo), _lib.p_f64(hi),
+                                                _lib.p_f64(rows), rows.shape[0], _lib.p_f64(out)), m.lib)
+        return out
+
     def slice(self, params) -> "ChebyshevApproximation":
         """Fix one or more dimensions at given values (reference barycentric.py:2064-2154):
         each sliced axis is contracted with its normalised barycentric weight vector -- or a

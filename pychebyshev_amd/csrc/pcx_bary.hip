@@ -91,6 +91,7 @@ extern "C" int pcx_bary_destroy(pcx_bary *h) {
     h->s_partial.release();
     (void)hipFree(h->d_nodes); (void)hipFree(h->d_wts); (void)hipFree(h->d_diff);
     (void)hipFree(h->d_cheb);
+    (void)hipFree(h->d_boxq);
     h->s_cheb[0].release(); h->s_cheb[1].release(); h->s_sobol.release();
     (void)hipFree(h->d_snodes);
     (void)hipFree(h->d_gsnodes);

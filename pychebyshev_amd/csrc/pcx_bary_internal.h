@@ -38,6 +38,7 @@ struct pcx_bary {
     long total = 0;
     std::vector<int> doff;           // offsets of D_k in diff_cat
     double *d_nodes = nullptr, *d_wts = nullptr, *d_diff = nullptr;
+    double *d_boxq = nullptr;        // box integrals (pcx_bary_box.hip; lazy): Q_n per dimension at doff[k], then 1 / j for j <= max n + 1
     double *d_cheb = nullptr;        // values -> Chebyshev coefficients matrix per dimension, at doff[k] (pcx_bary_sobol; lazy)
     Scratch s_cheb[2];               // the coefficient passes ping-pong between these (prod n doubles each, kept after first use)
     Scratch s_sobol;                 // k_sobol_energy's slab + k_sobol_finish's result

@@ -17,8 +17,10 @@ launches all run on the device (``pcx_spline_eval_batch``: ``k_spline_piece_id``
 Auto-N pieces (``error_threshold``) build through the pieces' own doubling loop; ``.pcb`` files
 (class tag 2) are read and written byte-compatibly.  ``sobol_indices`` aggregates the pieces' device-side indices
 on the host as the reference does.  ``roots`` / ``minimize`` / ``maximize`` solve each piece along the
-dimension on the device and combine the pieces on the host.  ``+``, ``-``, ``*`` and ``/`` combine the pieces' value tensors on the host.  Not provided:
-calculus batches, extrude/slice, auto_knots.
+dimension on the device and combine the pieces on the host.  ``+``, ``-``, ``*`` and ``/`` combine the pieces' value tensors on the host.
+``integrate`` contracts each piece on the device and sums the pieces along the integrated dimensions;
+``integrate_batch`` is the box integral with another box per row: one ``pcx_bary_box_batch`` launch per piece on the
+rows whose box reaches it.  Not provided: roots / minimize / maximize batches, extrude/slice, auto_knots.
 """
 from __future__ import annotations
 
@@ -507,6 +509,123 @@ class ChebyshevSpline(ErgonomicsMixin, DerivativeIdMixin):
             if val > best[0]:
                 best = (val, loc)
         return best
+
+    # ---------------------------------------------------------------- integration
+    def integrate(self, dims=None, bounds=None):
+        """Integrate over ``dims`` (all by default; reference spline.py:1581-1760).  Over all dimensions: the sum
+        of the pieces' integrals over their part of ``bounds``, a float.  Otherwise every piece is integrated along
+        the dimension (on the device, ``ChebyshevApproximation.integrate``) over its part of the bounds, the pieces
+        along that axis are summed, and the result is a lower-dimensional spline.  Bounds that equal a piece's
+        interval within 1e-14 integrate the whole piece."""
+        from .barycentric import _integration_bounds
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        if dims is None:
+            dims = list(range(self.num_dimensions))
+        elif isinstance(dims, (int, np.integer)):
+            dims = [int(dims)]
+        dims = sorted(set(dims))
+        for d in dims:
+            if d < 0 or d >= self.num_dimensions:
+                raise ValueError(f"dim {d} out of range [0, {self.num_dimensions - 1}]")
+        per_dim = dict(zip(dims, _integration_bounds(dims, bounds, self.domain)))
+
+        def part(bd, interval):
+            """What a piece over ``interval`` integrates of ``bd``: "skip", None (the whole piece) or (lo, hi)."""
+            if bd is None:
+                return None
+            lo, hi = max(bd[0], interval[0]), min(bd[1], interval[1])
+            if lo >= hi:
+                return "skip"
+            if abs(lo - interval[0]) < 1e-14 and abs(hi - interval[1]) < 1e-14:
+                return None
+            return (lo, hi)
+
+        pieces = np.empty(self._shape, dtype=object)
+        for multi, piece in zip(itertools.product(*[range(n) for n in self._shape]), self._pieces):
+            pieces[multi] = piece
+        if len(dims) == self.num_dimensions:
+            total = 0.0
+            for multi in np.ndindex(*self._shape):
+                parts = [part(per_dim[d], self._intervals[d][multi[d]]) for d in range(self.num_dimensions)]
+                if any(isinstance(b, str) for b in parts):
+                    continue
+                if all(b is None for b in parts):
+                    total += pieces[multi].integrate()
+                else:
+                    total += pieces[multi].integrate(bounds=parts)
+            return total
+
+        knots = [list(k) for k in self.knots]
+        intervals = [list(iv) for iv in self._intervals]
+        domain = [list(b) for b in self.domain]
+        for d in sorted(dims, reverse=True):
+            rest = tuple(n for i, n in enumerate(pieces.shape) if i != d)
+            summed = np.empty(rest, dtype=object)
+            for idx in np.ndindex(*rest):
+                along = pieces[idx[:d] + (slice(None),) + idx[d:]]
+                terms = []
+                for i, p in enumerate(along):
+                    b = part(per_dim[d], intervals[d][i])
+                    if isinstance(b, str):
+                        continue
+                    terms.append(p.integrate(dims=[d]) if b is None else p.integrate(dims=[d], bounds=[b]))
+                if not terms:                       # the bounds reach no piece: a zero piece
+                    terms.append(along[0].integrate(dims=[d]) * 0.0)
+                acc = terms[0]
+                for other in terms[1:]:
+                    acc = acc + other
+                summed[idx] = acc
+            pieces = summed
+            del knots[d], intervals[d], domain[d]
+        out = ChebyshevSpline.from_pieces(list(pieces.ravel()), self.num_dimensions - len(dims), domain, knots,
+                                          max_derivative_order=self.max_derivative_order)
+        out._device_index = self._device_index
+        return out
+
+    def integrate_batch(self, dims, bounds=None, points=None) -> np.ndarray:
+        """Box integrals for a batch of rows (extension; arguments as ``ChebyshevApproximation.integrate_batch``):
+        ``out[r]`` is the integral over ``bounds[r]`` in the dimensions ``dims`` at ``points[r]`` in the others.  The
+        kept coordinates route a row to one piece index per kept dimension as :meth:`eval_batch` does; every piece
+        then takes, in one ``pcx_bary_box_batch`` launch, the rows routed to it whose box overlaps its interval in
+        every integrated dimension, with their bounds clipped to it, and the results are added up per row.  A row
+        whose box overlaps no piece is 0.  Host arrays only."""
+        from ._calculus import box_rows
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        d = self.num_dimensions
+        flags, rows = box_rows(d, self.domain, dims, bounds, points)
+        N = rows.shape[0]
+        out = np.zeros(N)
+        if N == 0:
+            return out
+        self._dev()                      # every piece's device model on the spline's device
+        col = np.concatenate([[0], np.cumsum(1 + flags)[:-1]]).astype(int)
+        kept = [k for k in range(d) if not flags[k]]
+        routed = np.zeros((d, N), dtype=np.int64)
+        if kept:
+            full = np.empty((N, d))
+            for k in range(d):
+                full[:, k] = self.domain[k][0] if flags[k] else rows[:, col[k]]
+            routed = np.asarray(np.unravel_index(self.piece_indices(full).astype(np.int64), self._shape))
+        for multi, piece in zip(itertools.product(*[range(n) for n in self._shape]), self._pieces):
+            take = np.ones(N, dtype=bool)
+            for k in range(d):
+                if flags[k]:
+                    lo, hi = self._intervals[k][multi[k]]
+                    take &= np.maximum(rows[:, col[k]], lo) < np.minimum(rows[:, col[k] + 1], hi)
+                else:
+                    take &= routed[k] == multi[k]
+            if not take.any():
+                continue
+            sub = rows[take].copy()
+            for k in range(d):
+                if flags[k]:
+                    lo, hi = self._intervals[k][multi[k]]
+                    sub[:, col[k]] = np.maximum(sub[:, col[k]], lo)
+                    sub[:, col[k] + 1] = np.minimum(sub[:, col[k] + 1], hi)
+            out[take] += piece._box_batch(flags, sub)
+        return out
 
     # ---------------------------------------------------------------- algebra
     # Reference spline.py:1912-2010: piece by piece on the host (ChebyshevApproximation's operators), the

@@ -1436,73 +1436,8 @@ class ChebyshevTT(ErgonomicsMixin):
 
     def _box_rows(self, dims, bounds, points):
         """Validated arguments of :meth:`integrate_batch` -> (flags by user dimension, rows ``(N, d + m)``)."""
-        d = self.num_dimensions
-        dims = self._integrated_dims(dims)
-        m = len(dims)
-        if m < 1:
-            raise ValueError("dims must name at least one dimension")
-        udom = np.asarray(self._user_frame_domain(), dtype=float)
-        kept = [u for u in range(d) if u not in dims]
-        n_rows = []
-        if bounds is None:
-            bnd = udom[dims][None, :, :]
-        else:
-            bnd = np.asarray(bounds, dtype=float)
-            if m == 1 and bnd.ndim == 1:
-                bnd = bnd[None, :]
-            if bnd.ndim == 2 and bnd.shape == (m, 2):
-                bnd = bnd[None, :, :]
-            elif m == 1 and bnd.ndim == 2 and bnd.shape[1] == 2:
-                bnd = bnd[:, None, :]
-            if bnd.ndim != 3 or bnd.shape[1:] != (m, 2):
-                raise ValueError(f"bounds must broadcast to (N, {m}, 2), got shape {np.shape(bounds)}")
-            if bnd.shape[0] != 1:
-                n_rows.append(("bounds", bnd.shape[0]))
-        if points is None:
-            if kept:
-                raise ValueError(f"points is required: {len(kept)} dimensions are kept")
-            pts = None
-        else:
-            pts = np.asarray(points, dtype=float)
-            if pts.ndim != 2 or pts.shape[1] != len(kept):
-                raise ValueError(f"points must have shape (N, {len(kept)}), got {pts.shape}")
-            n_rows.append(("points", pts.shape[0]))
-        if len(n_rows) == 2 and n_rows[0][1] != n_rows[1][1]:
-            raise ValueError(f"bounds has {n_rows[0][1]} rows but points has {n_rows[1][1]}")
-        N = n_rows[0][1] if n_rows else 1
-        bnd = np.broadcast_to(bnd, (N, m, 2))
-        lo, hi = bnd[:, :, 0], bnd[:, :, 1]
-        a, b = udom[dims, 0][None, :], udom[dims, 1][None, :]
-        bad = (lo > hi) | (lo < a - 1e-14) | (hi > b + 1e-14) | ~np.isfinite(lo) | ~np.isfinite(hi)
-        if bad.any():
-            r = int(np.argmax(bad.any(axis=1)))
-            j = int(np.argmax(bad[r]))
-            if lo[r, j] > hi[r, j]:
-                raise ValueError(f"bounds lo={lo[r, j]} > hi={hi[r, j]} for dim {dims[j]} (row {r})")
-            raise ValueError(f"bounds ({lo[r, j]}, {hi[r, j]}) outside domain [{udom[dims[j], 0]}, {udom[dims[j], 1]}] "
-                             f"for dim {dims[j]} (row {r})")
-        if pts is not None and pts.size:
-            pa, pb = udom[kept, 0][None, :], udom[kept, 1][None, :]
-            bad = ~((pts >= pa) & (pts <= pb))
-            if bad.any():
-                r = int(np.argmax(bad.any(axis=1)))
-                j = int(np.argmax(bad[r]))
-                raise ValueError(f"point value {pts[r, j]} for dim {kept[j]} is outside domain "
-                                 f"[{udom[kept[j], 0]}, {udom[kept[j], 1]}] (row {r})")
-        flags = np.zeros(d, dtype=np.int32)
-        flags[dims] = 1
-        rows = np.empty((N, d + m))
-        col = 0
-        for u in range(d):
-            if flags[u]:
-                j = dims.index(u)
-                rows[:, col] = np.maximum(lo[:, j], a[0, j])         # clipped to the domain, as integrate() does
-                rows[:, col + 1] = np.minimum(hi[:, j], b[0, j])
-                col += 2
-            else:
-                rows[:, col] = pts[:, kept.index(u)]
-                col += 1
-        return flags, rows
+        from ._calculus import box_rows
+        return box_rows(self.num_dimensions, self._user_frame_domain(), self._integrated_dims(dims), bounds, points)
 
     def integrate_batch(self, dims, bounds=None, points=None) -> np.ndarray:
         """Box integrals for a batch of rows (extension; the reference computes one with ``integrate(dims, bounds)``
