@@ -277,6 +277,19 @@ int pcx_slider_eval_multi_batch(pcx_slider *h, const double *pts, int64_t N,
 /* Device-resident points and results; synchronous on return. */
 int pcx_slider_eval_multi_batch_dev(pcx_slider *h, const double *d_pts, int64_t N,
                                     const int32_t *derivs, int m, double *d_out);
+/* Box integrals, batched (the reference's integrate(dims, bounds) then eval(point), slider.py:881-1136, one row per call
+ * there).  flags, lo / hi (the slider's domain, d each) and the N x (d + m) rows are those of pcx_bary_box_batch over the
+ * slider's dimensions: the column of dimension u is u + the number of flags set below u; m = 0 is the value.  Per slide a
+ * gather writes the slide's own box row, pcx_bary_box_batch_dev on the slider's stream gives its box integral I_i (its
+ * value where none of its dimensions is integrated), and a last kernel forms, slides in partition order,
+ *     out = pv vol_T + sum_i vol(T \ G_i) (I_i - pv vol(T n G_i)),
+ * vol(S) the product of the row's hi - lo over the integrated dimensions in S (1 for none).  Volumes are products, never
+ * quotients: a row with lo == hi in an integrated dimension gives exactly 0.  Rows are not checked against the domain.
+ * N = 0 returns PCX_OK without a launch.  The _dev form takes device rows and results and is synchronous on return. */
+int pcx_slider_box_batch(pcx_slider *h, const int32_t *flags, const double *lo, const double *hi, const double *rows,
+                         int64_t N, double *out);
+int pcx_slider_box_batch_dev(pcx_slider *h, const int32_t *flags, const double *lo, const double *hi, const double *d_rows,
+                             int64_t N, double *d_out);
 
 /* ---- tensor-train interpolant ---------------------------------------------- */
 /* State of ChebyshevTT (tensor_train.py:1117-1138): Chebyshev COEFFICIENT cores
@@ -348,6 +361,18 @@ int pcx_bary_calculus_batch(pcx_bary *h, int dim, const double *lo, const double
  * chebyshev_nodes / compute_barycentric_weights / compute_differentiation_matrix build them.                      */
 int pcx_tt_calculus_batch(pcx_tt *h, int dim, const double *fixed, int64_t N, int mode, double *roots_out,
                           int32_t *counts_out, double *val_out, double *loc_out);
+/* The same for a slider (reference slider.py:1178-1283 slices to one dimension and re-interpolates): `dim` and the
+ * columns of `fixed` are the slider's dimensions, lo / hi its domain (d doubles each; a handle does not know it).  Every
+ * argument is checked before any launch: NULL handle, dim, mode, the node count of `dim` (<= 64) and the fixed values
+ * against their dimensions' domains (NaN passes), each PCX_ERR_INVALID.  Along `dim` only the slide that owns it varies:
+ * every other slide is evaluated once per row at its columns of `fixed`, the owner at the n fibre points of its own
+ * group -- or, when its group is `dim` alone, not at all: its value tensor is the fibre.  Element (r, j) of the fibre is
+ * pivot, then += v_i - pivot for the slides in partition order, the evaluation's order of operations, so it equals
+ * pcx_slider_eval_batch at (fixed..., x_j).  The solver, its outputs, the NaN padding and counts = -1 are those of
+ * pcx_bary_calculus_batch, with the owner slide's nodes, weights and differentiation matrix of `dim`.  Passes of at most
+ * 2^21 fibre points, one download.  N = 0 returns PCX_OK and touches no output.                                       */
+int pcx_slider_calculus_batch(pcx_slider *h, int dim, const double *lo, const double *hi, const double *fixed, int64_t N,
+                              int mode, double *roots_out, int32_t *counts_out, double *val_out, double *loc_out);
 
 /* ---- TT-Cross build steps (tensor_train.py:123-540) ------------------------- */
 /* One unfolding step of _tt_cross (:332-362 and :449-474): thin SVD of the m x c cross

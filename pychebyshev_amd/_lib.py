@@ -109,6 +109,9 @@ SIGNATURES = {
     "pcx_slider_eval_batch": (_I, [_V, c_f64p, _L, c_i32p, c_f64p]),
     "pcx_slider_eval_multi_batch": (_I, [_V, c_f64p, _L, c_i32p, _I, c_f64p]),
     "pcx_slider_eval_multi_batch_dev": (_I, [_V, _V, _L, c_i32p, _I, _V]),
+    "pcx_slider_calculus_batch": (_I, [_V, _I, c_f64p, c_f64p, c_f64p, _L, _I, c_f64p, c_i32p, c_f64p, c_f64p]),
+    "pcx_slider_box_batch": (_I, [_V, c_i32p, c_f64p, c_f64p, c_f64p, _L, c_f64p]),
+    "pcx_slider_box_batch_dev": (_I, [_V, c_i32p, c_f64p, c_f64p, _V, _L, _V]),
     "pcx_tt_create": (_I, [_I, _I, c_i32p, c_i32p, c_f64p, c_f64p, c_f64p, c_i32p, c_vpp]),
     "pcx_tt_destroy": (_I, [_V]),
     "pcx_tt_eval_batch": (_I, [_V, c_f64p, _L, c_f64p]),

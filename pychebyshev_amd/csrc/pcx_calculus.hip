@@ -5,9 +5,15 @@
 // node values), evaluates them with the handle's existing device evaluation (the node rule of the barycentric kernels
 // makes the weight of dimension `dim` one-hot there) and solves every fibre with k_cheb1d_calculus.  Fibres and results
 // stay in HBM until the one download of the results.
+//
+// The slider entry (pcx_slider_calculus_batch) uses the slider's structure instead of its evaluation: along `dim` only
+// the slide that owns `dim` varies, so every other slide is evaluated once per row and the owner once per fibre point --
+// or not at all when it is one-dimensional, its value tensor being the fibre.  k_slider_fibre_sum then adds them up in
+// the evaluation's order and the same solver runs.
 
-#include "pcx_bary_internal.h"
+#include "pcx_slider_internal.h"
 #include "calculus_kernels.h"
+#include "slider_calc_kernels.h"
 
 // rows per pass of the expand / evaluate / solve pipeline: at most this many fibre points in flight
 static const long kCalcChunkPoints = 1L << 21;
@@ -232,5 +238,111 @@ extern "C" int pcx_tt_calculus_batch(pcx_tt *h, int dim, const double *fixed, in
     rc = calc_fibres(d, dim, mode, fixed, N, a, st, eval, roots_out, counts_out, val_out, loc_out);
     (void)hipStreamSynchronize(st);                            // d_grid is freed on return
     return rc;
+    PCX_API_END
+}
+
+// Columns of the (d - 1)-wide fixed rows (every dimension but `dim`, increasing) that hold the dimensions `dims[0 .. nc)`.
+static SliderCols slider_fixed_cols(const int *dims, int nc, int dim) {
+    SliderCols c;
+    c.nc = nc;
+    for (int k = 0; k < PCX_MAX_DIMS; ++k) c.col[k] = 0;
+    for (int k = 0; k < nc; ++k) c.col[k] = dims[k] < dim ? dims[k] : dims[k] - 1;
+    return c;
+}
+
+extern "C" int pcx_slider_calculus_batch(pcx_slider *h, int dim, const double *lo, const double *hi, const double *fixed,
+                                         int64_t N, int mode, double *roots_out, int32_t *counts_out, double *val_out,
+                                         double *loc_out) {
+    PCX_API_BEGIN
+    if (!h || !lo || !hi) return fail(PCX_ERR_INVALID, "NULL argument");
+    const int d = h->d;
+    if (dim < 0 || dim >= d) return fail(PCX_ERR_INVALID, "dim %d out of range [0, %d]", dim, d - 1);
+    const int o = h->owner[dim];                               // the slide that owns dim, and dim's place in its group
+    pcx_bary *po = h->slides[o];
+    const SliderCols &oc = h->cols[o];
+    int lk = 0;
+    while (oc.col[lk] != dim) ++lk;
+    const int g = oc.nc;
+    const int n = po->dims.n[lk];
+    int rc = calc_check(n, mode, N, lo[dim], hi[dim], po->d_diff, roots_out, counts_out, val_out, loc_out);
+    if (!rc) rc = calc_check_fixed(fixed, N, d, dim, lo, hi);
+    if (rc) return rc;
+    if (N == 0) return PCX_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    std::lock_guard<std::mutex> lk_h(h->mu);
+    hipStream_t st = h->stream;
+    const int ns = (int)h->slides.size();
+    CalcArgs a{};
+    a.n = n; a.mode = mode; a.W = std::max(n - 1, 1); a.lo = lo[dim]; a.hi = hi[dim];
+    a.nodes = po->d_nodes + po->dims.off[lk];
+    a.wts = po->d_wts + po->dims.off[lk];
+    a.diff = po->d_diff + po->doff[lk];
+    const long chunk = std::max<long>(1, std::min<long>(N, kCalcChunkPoints / n));
+    // s_cols: a slide's gathered columns (chunk x nc), or the owner's gathered columns and behind them its fibre points
+    const size_t own_cols = g > 1 ? (((size_t)chunk * (g - 1) + 31) & ~(size_t)31) : 0;      // the points stay 256-byte aligned
+    const size_t cols_doubles = std::max<size_t>((size_t)chunk * h->max_cols, own_cols + (g > 1 ? (size_t)chunk * n * g : 0));
+    DevBuf d_fixed, d_vals;
+    CalcDevOut out;
+    rc = h->s_cols.reserve(cols_doubles * sizeof(double));
+    if (!rc) rc = h->s_vals.reserve((size_t)chunk * ns * sizeof(double));
+    if (!rc) rc = d_fixed.alloc((size_t)N * (d - 1) * sizeof(double));
+    if (!rc) rc = d_vals.alloc((size_t)chunk * n * sizeof(double));
+    if (!rc) rc = out.alloc(mode, N, a.W);
+    if (rc) return rc;
+    if (d > 1) HIP_TRY(hipMemcpyAsync(d_fixed.p, fixed, (size_t)N * (d - 1) * sizeof(double), hipMemcpyHostToDevice, st));
+    double *cols = (double *)h->s_cols.ptr, *svals = (double *)h->s_vals.ptr, *vals = d_vals.as<double>();
+    for (long r0 = 0; r0 < N; r0 += chunk) {
+        const long rows = std::min<long>(chunk, N - r0);
+        const double *frows = d_fixed.as<double>() + (size_t)r0 * (d - 1);
+        // every other slide once per row, into column s of svals (column o stays unread)
+        for (int s = 0; s < ns; ++s) {
+            if (s == o) continue;
+            pcx_bary *pc = h->slides[s];
+            const SliderCols c = slider_fixed_cols(h->cols[s].col, h->cols[s].nc, dim);
+            const long elems = rows * c.nc;
+            hipLaunchKernelGGL(k_gather_columns, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, frows, rows, d - 1, c, cols);
+            HIP_TRY(hipGetLastError());
+            std::lock_guard<std::mutex> plk(pc->mu);
+            pc->call_mark = pc->clock;
+            DerivedTensor *dt = nullptr;
+            if ((rc = bary_get_tensor(pc, nullptr, &dt))) return rc;
+            if ((rc = bary_launch(pc, &dt, 1, dt->slot, cols, rows, svals, ns, s, st, &h->s_partial))) return rc;
+        }
+        {
+            std::lock_guard<std::mutex> plk(po->mu);
+            po->call_mark = po->clock;
+            DerivedTensor *dt = nullptr;
+            if ((rc = bary_get_tensor(po, nullptr, &dt))) return rc;
+            const double *plain = dt->plain;                   // one-dimensional owner: its value tensor is the fibre
+            if (g > 1) {
+                // the owner's other columns (group order), expanded into the n fibre points of the group's own frame
+                int others[PCX_MAX_DIMS];
+                for (int k = 0, c = 0; k < g; ++k)
+                    if (k != lk) others[c++] = oc.col[k];
+                const SliderCols c = slider_fixed_cols(others, g - 1, dim);
+                const long elems = rows * (g - 1);
+                hipLaunchKernelGGL(k_gather_columns, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, frows, rows, d - 1, c, cols);
+                HIP_TRY(hipGetLastError());
+                double *pts = cols + own_cols;
+                const long total = rows * n * g;
+                hipLaunchKernelGGL(k_calc_expand, dim3((unsigned)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, st,
+                                   (const double *)cols, rows, g, lk, n, a.nodes, pts);
+                HIP_TRY(hipGetLastError());
+                if ((rc = bary_launch(po, &dt, 1, dt->slot, pts, rows * n, vals, 1, 0, st, &h->s_partial))) return rc;
+                plain = nullptr;
+            }
+            const long total = rows * n;
+            hipLaunchKernelGGL(k_slider_fibre_sum, dim3((unsigned)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, st, vals,
+                               plain, (const double *)svals, rows, n, ns, o, h->pivot);
+            HIP_TRY(hipGetLastError());
+        }
+        CalcArgs c = a;
+        c.vals = vals;
+        c.counts = out.counts.as<int32_t>() + r0;
+        if (mode == 0) c.roots = out.roots.as<double>() + (size_t)r0 * a.W;
+        else { c.val = out.val.as<double>() + r0; c.loc = out.loc.as<double>() + r0; }
+        if ((rc = calc_launch(c, rows, st))) return rc;
+    }
+    return out.download(mode, N, a.W, roots_out, counts_out, val_out, loc_out, st);
     PCX_API_END
 }

@@ -1,0 +1,23 @@
+// pcx_slider_internal.h -- the slider handle as the translation units that serve it see it (pcx_spline.hip creates and
+// evaluates it, pcx_calculus.hip and pcx_slider_box.hip run its calculus and box integrals).  Not part of the ABI.
+#pragma once
+
+#include "pcx_bary_internal.h"
+#include "gather_kernels.h"
+
+// ---------------------------------------------------------------------------------
+// slider handle (reference slider.py:80-341): slides are borrowed pcx_bary handles
+// ---------------------------------------------------------------------------------
+struct pcx_slider {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int d = 0;
+    double pivot = 0.0;
+    std::vector<pcx_bary *> slides;      // borrowed
+    std::vector<SliderCols> cols;        // the point columns slide s reads
+    std::vector<int> owner;              // dimension -> slide
+    int max_cols = 1;
+    std::mutex mu;
+    HostStage stage;                     // host-pointer batches
+    Scratch s_cols, s_vals, s_partial;
+};

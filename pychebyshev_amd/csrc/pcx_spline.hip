@@ -1,7 +1,7 @@
 // pcx_spline.hip -- C ABI of libpcx_hip.so (see include/pcx.h): piecewise interpolants and sliders, both built
 // out of barycentric handles (pcx_bary.hip).  gfx950 only.
 
-#include "pcx_bary_internal.h"
+#include "pcx_slider_internal.h"
 #include "route_kernels.h"
 
 // ---------------------------------------------------------------------------------
@@ -384,22 +384,8 @@ extern "C" int pcx_spline_piece_ids(pcx_spline *h, const double *pts, int64_t N,
 }
 
 // ---------------------------------------------------------------------------------
-// slider handle (reference slider.py:80-341): slides are borrowed pcx_bary handles
+// slider handle: struct pcx_slider lives in pcx_slider_internal.h
 // ---------------------------------------------------------------------------------
-struct pcx_slider {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int d = 0;
-    double pivot = 0.0;
-    std::vector<pcx_bary *> slides;      // borrowed
-    std::vector<SliderCols> cols;        // the point columns slide s reads
-    std::vector<int> owner;              // dimension -> slide
-    int max_cols = 1;
-    std::mutex mu;
-    HostStage stage;                     // host-pointer batches
-    Scratch s_cols, s_vals, s_partial;
-};
-
 extern "C" int pcx_slider_destroy(pcx_slider *h) {
     PCX_API_BEGIN
     if (!h) return PCX_OK;

@@ -15,7 +15,18 @@ the reference's order.
 
 ``+``, ``-``, ``*`` and ``/`` combine the slides' value tensors and the pivot value on the host.
 
-Out of scope in this tier: calculus, extrude/slice, plotting.
+    extrude / slice                                                       (:621-875)
+    integrate(dims, bounds)   scalar, or a slider over the kept dimensions  (:881-1136)
+    roots / minimize / maximize(dim, fixed)                               (:1178-1283)
+
+``roots_batch`` / ``minimize_batch`` / ``maximize_batch`` and ``integrate_batch`` are extensions.  Along one
+dimension only the slide that owns it varies, so ``pcx_slider_calculus_batch`` evaluates every other slide once per
+row and the owner once per fibre point (not at all when the owner is one-dimensional: its value tensor is the fibre),
+adds them in ``eval``'s order and solves every fibre on the device; the single calls are one-row batches up to 64
+nodes and the host restatement of ``_calculus`` above.  ``pcx_slider_box_batch`` sums the slides' own per-row box
+integrals scaled by the row's box widths.
+
+Out of scope in this tier: plotting.
 """
 from __future__ import annotations
 
@@ -27,13 +38,24 @@ from typing import Callable, List, Sequence, Tuple
 
 import numpy as np
 
-from . import _algebra, _lib
+from . import _algebra, _calculus, _lib
 from ._version import __version__
 from ._derivative_ids import DerivativeIdMixin
 from ._ergonomics import ErgonomicsMixin
-from .barycentric import ChebyshevApproximation
+from .barycentric import ChebyshevApproximation, _integration_bounds
 
 __all__ = ["ChebyshevSlider"]
+
+
+def _partition_intersect(group, integrate_dims):
+    """The reference's ``_slider_partition_intersect``: a slide group against the integrated dimensions -> ``"full"``
+    (every dimension integrated), ``"partial"`` or ``"none"``, and the group's dimensions that are kept."""
+    overlap = set(group) & set(integrate_dims)
+    if not overlap:
+        return "none", list(group)
+    if overlap == set(group):
+        return "full", []
+    return "partial", [d for d in group if d not in overlap]
 
 
 class _DeviceSlider:
@@ -313,6 +335,248 @@ class ChebyshevSlider(ErgonomicsMixin, DerivativeIdMixin):
         if not _algebra.is_scalar(scalar):
             return NotImplemented
         return self.__imul__(1.0 / float(scalar))
+
+    # ---------------------------------------------------------------- extrude / slice
+    def _assembled(self, num_dimensions, domain, n_nodes, partition, pivot_point, slides, pivot_value) -> "ChebyshevSlider":
+        """A built slider over other dimensions than this one's (``function=None``, no device handle yet)."""
+        obj = self._with_slides(slides, pivot_value)
+        obj.num_dimensions = num_dimensions
+        obj.domain = domain
+        obj.n_nodes = n_nodes
+        obj.partition = partition
+        obj.pivot_point = pivot_point
+        obj._dim_to_slide = {d: i for i, group in enumerate(partition) for d in group}
+        return obj
+
+    def extrude(self, params) -> "ChebyshevSlider":
+        """Add dimensions along which the function is constant (reference slider.py:621-739).  ``params`` is one
+        ``(dim_index, (lo, hi), n_nodes)`` or a list of them, ``dim_index`` being the position in the result.  Each
+        new dimension is a one-dimensional slide of its own whose tensor is ``np.full(n, pivot_value)`` -- it adds
+        ``s(x) - pivot_value = 0`` to the sum -- appended to the partition; the existing groups are renumbered and
+        the new pivot coordinate is the midpoint."""
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        from .tensor_train import _extrude_params
+        sorted_params = _extrude_params(params, self.num_dimensions)
+        domain = [list(b) for b in self.domain]
+        n_nodes = list(self.n_nodes)
+        pivot_point = list(self.pivot_point)
+        partition = [list(g) for g in self.partition]
+        slides = list(self.slides)
+        for dim_idx, (lo, hi), n in sorted_params:
+            partition = [[d + 1 if d >= dim_idx else d for d in group] for group in partition]
+            slide = ChebyshevApproximation.from_values(np.full(n, self.pivot_value), 1, [[lo, hi]], [n],
+                                                       max_derivative_order=self.max_derivative_order)
+            slide._device_index = self.__dict__.get("_device_index")
+            partition.append([dim_idx])
+            slides.append(slide)
+            domain.insert(dim_idx, [lo, hi])
+            n_nodes.insert(dim_idx, n)
+            pivot_point.insert(dim_idx, 0.5 * (lo + hi))
+        return self._assembled(self.num_dimensions + len(sorted_params), domain, n_nodes, partition, pivot_point,
+                               slides, self.pivot_value)
+
+    def slice(self, params) -> "ChebyshevSlider":
+        """Fix one or more dimensions (reference slider.py:741-875): ``params`` is one ``(dim_index, value)`` or a
+        list.  A dimension of a multi-dimension group is sliced out of its slide (``ChebyshevApproximation.slice``); a
+        one-dimension group is evaluated to ``s_val``, ``delta = s_val - pivot_value`` goes into every remaining
+        slide's tensor, ``pivot_value`` becomes ``s_val`` and the group is dropped.  Indices are renumbered."""
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        from .tensor_train import _slice_params
+        sorted_params = sorted(_slice_params(params, self.num_dimensions), key=lambda p: p[0], reverse=True)
+        for dim_idx, value in sorted_params:
+            lo, hi = self.domain[dim_idx]
+            if value < lo or value > hi:
+                raise ValueError(f"Slice value {value} for dim {dim_idx} is outside domain [{lo}, {hi}]")
+        domain = [list(b) for b in self.domain]
+        n_nodes = list(self.n_nodes)
+        pivot_point = list(self.pivot_point)
+        partition = [list(g) for g in self.partition]
+        slides = list(self.slides)
+        pivot_value = self.pivot_value
+        for dim_idx, value in sorted_params:                       # descending
+            slide_idx = next(i for i, group in enumerate(partition) if dim_idx in group)
+            if len(partition[slide_idx]) > 1:
+                slides[slide_idx] = slides[slide_idx].slice((partition[slide_idx].index(dim_idx), value))
+                partition[slide_idx].remove(dim_idx)
+            else:
+                s_val = slides[slide_idx].vectorized_eval([value], [0])
+                delta = s_val - pivot_value
+                slides = [s._combined(s.tensor_values + delta) for i, s in enumerate(slides) if i != slide_idx]
+                pivot_value = s_val
+                del partition[slide_idx]
+            partition = [[d - 1 if d > dim_idx else d for d in group] for group in partition]
+            del domain[dim_idx]
+            del n_nodes[dim_idx]
+            del pivot_point[dim_idx]
+        return self._assembled(self.num_dimensions - len(sorted_params), domain, n_nodes, partition, pivot_point,
+                               slides, pivot_value)
+
+    # ---------------------------------------------------------------- integration
+    def integrate(self, dims=None, bounds=None):
+        """Integrate over ``dims`` (all by default; ``bounds``: one ``(lo, hi)`` or ``None`` per integrated dimension)
+        by the closed form of the sliding sum (reference slider.py:881-1136).  A slide whose group is integrated in
+        full goes into the new pivot value ``pv' = pv vol_T + sum vol(T \\ G_i) (I_i - pv vol(G_i))``; every other
+        slide keeps its surviving dimensions with the tensor ``scale . source + (pv' - pv vol_T)``, ``source`` its own
+        partial integral (scale ``vol(T \\ G_i)``) or, where none of its dimensions is integrated, its tensor (scale
+        ``vol_T``).  Returns a float when no dimension is left, else a slider over the surviving dimensions."""
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        if dims is None:
+            dims_sorted = list(range(self.num_dimensions))
+        elif isinstance(dims, (int, np.integer)):
+            dims_sorted = [int(dims)]
+        else:
+            dims_sorted = sorted(set(dims))
+        for d in dims_sorted:
+            if d < 0 or d >= self.num_dimensions:
+                raise ValueError(f"dim {d} out-of-range [0, {self.num_dimensions - 1}]")
+        bounds_for_dim = dict(zip(dims_sorted, _integration_bounds(dims_sorted, bounds, self.domain)))
+        widths = {d: (self.domain[d][1] - self.domain[d][0]) if bd is None else bd[1] - bd[0]
+                  for d, bd in bounds_for_dim.items()}
+        vol_T = 1.0
+        for d in dims_sorted:
+            vol_T *= widths[d]
+
+        def vol_outside(group):
+            v = 1.0
+            for d in dims_sorted:
+                if d not in group:
+                    v *= widths[d]
+            return v
+
+        def slide_integral(slide, group):
+            local = [(i, bounds_for_dim[g]) for i, g in enumerate(group) if g in bounds_for_dim]
+            local_dims, local_bounds = [i for i, _ in local], [b for _, b in local]
+            if all(b is None for b in local_bounds):
+                return slide.integrate(dims=local_dims)
+            return slide.integrate(dims=local_dims, bounds=local_bounds)
+
+        kinds = [_partition_intersect(group, dims_sorted) for group in self.partition]
+        pv_new = self.pivot_value * vol_T
+        for slide, group, (kind, _) in zip(self.slides, self.partition, kinds):
+            if kind != "full":
+                continue
+            I_i = float(slide_integral(slide, group))
+            vol_group = 1.0
+            for d in group:
+                vol_group *= widths[d]
+            pv_new += vol_outside(group) * (I_i - self.pivot_value * vol_group)
+        if len(dims_sorted) == self.num_dimensions:
+            return float(pv_new)
+
+        survive = [d for d in range(self.num_dimensions) if d not in bounds_for_dim]
+        old_to_new = {old: new for new, old in enumerate(survive)}
+        shift = pv_new - self.pivot_value * vol_T
+        new_partition, new_slides = [], []
+        for slide, group, (kind, kept) in zip(self.slides, self.partition, kinds):
+            if kind == "full":
+                continue
+            if kind == "none":
+                new_slides.append(slide._combined(vol_T * slide.tensor_values + shift))
+            else:
+                reduced = slide_integral(slide, group)
+                new_slides.append(reduced._combined(vol_outside(group) * reduced.tensor_values + shift))
+            new_partition.append([old_to_new[d] for d in kept])
+        obj = self._assembled(len(survive), [list(self.domain[d]) for d in survive], [self.n_nodes[d] for d in survive],
+                              new_partition, [self.pivot_point[d] for d in survive], new_slides, pv_new)
+        obj.descriptor = self.descriptor
+        obj.additional_data = self.additional_data
+        return obj
+
+    def integrate_batch(self, dims, bounds=None, points=None) -> np.ndarray:
+        """Box integrals for a batch of rows (extension; the reference computes one with ``integrate(dims, bounds)``
+        and then ``eval(point)``).  Arguments and the ``(N,)`` result as
+        :meth:`ChebyshevApproximation.integrate_batch`.  On the device every slide takes its own box integral of the
+        row and a last kernel sums them scaled by the row's box widths (``pcx_slider_box_batch``).  Host arrays only."""
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        flags, rows = _calculus.box_rows(self.num_dimensions, self.domain, dims, bounds, points)
+        rows = _lib.f64(rows)
+        out = np.empty(rows.shape[0])
+        if rows.shape[0]:
+            s = self._dev()
+            lo, hi = self._domain_arrays()
+            _lib.check(s.lib.pcx_slider_box_batch(s.handle, _lib.p_i32(_lib.i32(flags)), _lib.p_f64(lo), _lib.p_f64(hi),
+                                                  _lib.p_f64(rows), rows.shape[0], _lib.p_f64(out)), s.lib)
+        return out
+
+    # ---------------------------------------------------------------- calculus
+    def _domain_arrays(self):
+        dom = np.asarray(self.domain, dtype=float)
+        return _lib.f64(dom[:, 0]), _lib.f64(dom[:, 1])
+
+    def _owner_grid(self, dim: int):
+        """Nodes, weights and differentiation matrix of ``dim``: those of the slide that owns it."""
+        idx = self._dim_to_slide[dim]
+        local = list(self.partition[idx]).index(dim)
+        slide = self.slides[idx]
+        return slide.nodes[local], slide.weights[local], slide.diff_matrices[local]
+
+    def _calculus_batch(self, dim: int, rows: np.ndarray, mode: int):
+        """``pcx_slider_calculus_batch`` over validated rows (see :func:`pychebyshev_amd._calculus.run_batch`)."""
+        s = self._dev()
+        lo, hi = self._domain_arrays()
+        rows = _lib.f64(rows)
+        N = rows.shape[0]
+
+        def call(r, c, v, loc):
+            return s.lib.pcx_slider_calculus_batch(s.handle, int(dim), _lib.p_f64(lo), _lib.p_f64(hi), _lib.p_f64(rows), N,
+                                                   mode, r, c, v, loc)
+        return _calculus.run_batch(call, s.lib, int(self.n_nodes[dim]), N, mode)
+
+    def _calculus(self, dim, fixed, mode: str):
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        d = self.num_dimensions
+        dim, params = _calculus.validate_calculus_args(d, dim, fixed, self.domain)
+        row = _calculus.fixed_row(d, dim, params)
+        nodes, weights, diff = self._owner_grid(dim)
+        return _calculus.run_single(
+            lambda: self.eval_batch(_calculus.fibre_points(d, dim, row, nodes), [0] * d),
+            lambda m: self._calculus_batch(dim, row, m), int(self.n_nodes[dim]), mode, nodes, weights, diff,
+            (self.domain[dim][0], self.domain[dim][1]))
+
+    def roots(self, dim=None, fixed=None) -> np.ndarray:
+        """Sorted real roots along ``dim`` with every other dimension fixed (``fixed = {dim_index: value}``;
+        reference slider.py:1178-1224, which slices to one dimension and re-interpolates at the nodes).  The fibre is
+        formed and solved on the device; above 64 nodes the solve runs on the host (NumPy ``chebroots``).  A
+        non-finite fibre raises ``numpy.linalg.LinAlgError``."""
+        return self._calculus(dim, fixed, "roots")
+
+    def minimize(self, dim=None, fixed=None):
+        """``(value, location)`` of the minimum along ``dim`` (reference slider.py:1226-1264)."""
+        return self._calculus(dim, fixed, "min")
+
+    def maximize(self, dim=None, fixed=None):
+        """``(value, location)`` of the maximum along ``dim`` (reference slider.py:1266-1283)."""
+        return self._calculus(dim, fixed, "max")
+
+    def _calculus_rows(self, dim, fixed) -> np.ndarray:
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        return _calculus.validate_batch_args(self.num_dimensions, dim, fixed, self.domain, self.n_nodes)
+
+    def roots_batch(self, dim: int, fixed):
+        """Roots along ``dim`` for every row of ``fixed`` (host float64 ``(N, d-1)``: the other dimensions in
+        increasing order), in one device pass (extension).  Returns ``(roots, counts)`` as
+        :meth:`ChebyshevApproximation.roots_batch`.  At most 64 nodes along ``dim``."""
+        rows = self._calculus_rows(dim, fixed)
+        return self._calculus_batch(int(dim), rows, 0)
+
+    def minimize_batch(self, dim: int, fixed):
+        """``(values, locations)``, float64 ``(N,)``, of the minimum along ``dim`` for every row of ``fixed``
+        (extension; arguments as :meth:`roots_batch`).  NaN where a row failed."""
+        rows = self._calculus_rows(dim, fixed)
+        val, loc, _ = self._calculus_batch(int(dim), rows, 1)
+        return val, loc
+
+    def maximize_batch(self, dim: int, fixed):
+        """``(values, locations)`` of the maximum along ``dim`` for every row of ``fixed`` (extension)."""
+        rows = self._calculus_rows(dim, fixed)
+        val, loc, _ = self._calculus_batch(int(dim), rows, 2)
+        return val, loc
 
     # ---------------------------------------------------------------- misc
     @property
