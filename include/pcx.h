@@ -373,6 +373,27 @@ int pcx_tt_calculus_batch(pcx_tt *h, int dim, const double *fixed, int64_t N, in
  * 2^21 fibre points, one download.  N = 0 returns PCX_OK and touches no output.                                       */
 int pcx_slider_calculus_batch(pcx_slider *h, int dim, const double *lo, const double *hi, const double *fixed, int64_t N,
                               int mode, double *roots_out, int32_t *counts_out, double *val_out, double *loc_out);
+/* The same for a spline (reference spline.py:1762-1910: slice to one dimension, solve every piece, merge): `dim` and the
+ * columns of `fixed` are the spline's dimensions, lo / hi its domain (d doubles each; a handle does not know it).  Along
+ * `dim` there are P pieces over [e_j, e_j+1], edges = [lo[dim], knots..., hi[dim]], piece j with n_j nodes (those of the
+ * piece whose other indices are 0).  Every argument is checked before any launch: NULL handle, dim, mode, a node count
+ * above 64 in any piece along `dim`, pieces that share an index along `dim` but differ in their node count there (one
+ * grid serves an index), the fixed values against their dimensions' domains (NaN passes) and NULL outputs for
+ * the mode, each PCX_ERR_INVALID.  A pass of rows expands every row into the F = sum n_j points (fixed..., x_ji), x_ji
+ * piece j's own node values, and sends them through the spline's own evaluation (pcx_spline_eval_batch's routing,
+ * bucketing and per-piece kernels: the other indices of a row's pieces are searchsorted(knots, v, "right") capped at the
+ * last interval), solves the rows x P fibres in one launch with the solver of pcx_bary_calculus_batch on each piece's
+ * interval, and merges the pieces of every row on the device:
+ *   roots_out  N x W, W = sum_j max(n_j - 1, 1): the pieces' roots in piece order, an element kept when it is the first
+ *              or exceeds its immediate predecessor in that sequence (kept or not) by more than
+ *              1e-10 (|hi[dim] - lo[dim]| + 1); ascending, NaN-padded
+ *   counts_out N, always written: roots kept (mode 0), the sum of the pieces' critical points (modes 1, 2), -1 when any
+ *              piece of the row failed -- the row is then NaN everywhere
+ *   val_out, loc_out   N each (modes 1, 2): the first piece, in order, that is strictly best
+ * More than 65535 pieces along `dim`, or more than 2^23 fibre points in one row, are PCX_ERR_UNSUPPORTED.
+ * Passes of at most 2^21 fibre points, one download.  N = 0 returns PCX_OK and touches no output.                      */
+int pcx_spline_calculus_batch(pcx_spline *h, int dim, const double *lo, const double *hi, const double *fixed, int64_t N,
+                              int mode, double *roots_out, int32_t *counts_out, double *val_out, double *loc_out);
 
 /* ---- TT-Cross build steps (tensor_train.py:123-540) ------------------------- */
 /* One unfolding step of _tt_cross (:332-362 and :449-474): thin SVD of the m x c cross

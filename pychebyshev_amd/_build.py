@@ -27,14 +27,15 @@ SOURCES = {
     "pcx_bary_box.hip": HOST_H + ["pcx_bary_internal.h", "bary_kernels.h", "bary_box_kernels.h"],
     "pcx_bary_grid.hip": HOST_H + ["pcx_bary_internal.h", "bary_grid_kernels.h", "bary_weights.h"],
     "pcx_bary_kfold.hip": HOST_H + ["pcx_bary_internal.h", "bary_kfold_kernels.h"],
-    "pcx_spline.hip": HOST_H + ["pcx_bary_internal.h", "pcx_slider_internal.h", "gather_kernels.h", "route_kernels.h"],
+    "pcx_spline.hip": HOST_H + ["pcx_bary_internal.h", "pcx_slider_internal.h", "pcx_spline_internal.h", "gather_kernels.h",
+                       "route_kernels.h"],
     "pcx_slider_box.hip": HOST_H + ["pcx_bary_internal.h", "pcx_slider_internal.h", "gather_kernels.h", "slider_calc_kernels.h"],
     "pcx_tt.hip": HOST_H + ["tt_kernels.h", "tt_lpp_kernels.h", "tt_fd_kernels.h"],
     "pcx_tt_box.hip": HOST_H + ["tt_lpp_kernels.h", "tt_box_kernels.h"],
     "pcx_ttbuild.hip": HOST_H + ["ttcross_kernels.h", "ttsvd_kernels.h", "tt_round_kernels.h"],
     "pcx_tt_als.hip": HOST_H + ["tt_als_kernels.h"],
-    "pcx_calculus.hip": HOST_H + ["pcx_bary_internal.h", "pcx_slider_internal.h", "gather_kernels.h", "calculus_kernels.h",
-                         "slider_calc_kernels.h"],
+    "pcx_calculus.hip": HOST_H + ["pcx_bary_internal.h", "pcx_slider_internal.h", "pcx_spline_internal.h", "gather_kernels.h",
+                         "calculus_kernels.h", "slider_calc_kernels.h", "spline_calc_kernels.h"],
     "pcx_comm.hip": [PCX_H],
 }
 OBJ_DIR = os.path.join(HERE, "_obj")

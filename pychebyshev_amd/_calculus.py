@@ -75,10 +75,11 @@ def validate_batch_args(ndim: int, dim, fixed, domain, n_nodes) -> np.ndarray:
     return rows
 
 
-def run_batch(call, lib, n: int, N: int, mode: int):
+def run_batch(call, lib, n: int, N: int, mode: int, width: int | None = None):
     """Run one ``pcx_*_calculus_batch`` entry (``call(roots, counts, val, loc)`` -> rc) and shape its outputs:
-    mode 0 ``(roots (N, max(n-1, 1)), counts)``, modes 1 and 2 ``(values, locations, counts)``."""
-    W = max(n - 1, 1)
+    mode 0 ``(roots (N, max(n-1, 1)), counts)``, modes 1 and 2 ``(values, locations, counts)``.  ``width`` replaces the
+    roots' column count where it is not that of one fibre (a spline: the sum over its pieces)."""
+    W = max(n - 1, 1) if width is None else int(width)
     counts = np.empty(N, dtype=np.int32)
     if mode == 0:
         roots = np.empty((N, W))
@@ -116,6 +117,31 @@ def single_extremum(val: np.ndarray, loc: np.ndarray, counts: np.ndarray):
     if counts[0] < 0:
         raise np.linalg.LinAlgError("fibre is not finite or the eigenvalue iteration did not converge")
     return float(val[0]), float(loc[0])
+
+
+def merge_pieces(mode: str, found, domain=None, counts=None):
+    """Join the results of the pieces of a spline along one dimension, given in piece order (reference
+    spline.py:1762-1910; the NumPy restatement of ``k_spline_calc_merge``).  ``counts``, when given, holds each piece's
+    solver count: a -1 raises ``LinAlgError``, as the piece's own single call does.
+
+    ``"roots"``: ``found`` holds one ascending array per piece.  The arrays are concatenated -- the pieces are ordered and
+    a piece's roots lie in its own interval -- and an element is kept when it is the first or exceeds its immediate
+    predecessor, kept or not, by more than ``1e-10 (|b - a| + 1)`` (``domain = (a, b)`` of the spline along the
+    dimension).  ``"min"`` / ``"max"``: ``found`` holds one ``(value, location)`` per piece; the result starts at
+    ``(+-inf, 0.0)`` and a piece replaces it only when strictly better, so the first of equal pieces wins."""
+    if counts is not None and any(int(c) < 0 for c in counts):
+        raise np.linalg.LinAlgError("fibre is not finite or the eigenvalue iteration did not converge")
+    if mode == "roots":
+        out = np.concatenate([np.asarray(r, dtype=float).ravel() for r in found]) if len(found) else np.array([], dtype=float)
+        if out.size > 1:
+            scale = abs(domain[1] - domain[0]) + 1
+            out = out[np.concatenate([[True], np.diff(out) > 1e-10 * scale])]
+        return out
+    best = (float("inf") if mode == "min" else float("-inf"), 0.0)
+    for val, loc in found:
+        if (val < best[0]) if mode == "min" else (val > best[0]):
+            best = (float(val), float(loc))
+    return best
 
 
 # ---------------------------------------------------------------------------------------------- host restatement

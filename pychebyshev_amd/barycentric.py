@@ -811,6 +811,30 @@ class ChebyshevApproximation(ErgonomicsMixin, DerivativeIdMixin):
                 del lst[dim_idx]
         return self._reduced(tensor, nodes, weights, diffs, domain, n_nodes)
 
+    def extrude(self, params) -> "ChebyshevApproximation":
+        """Add dimensions along which the function is constant (reference barycentric.py:1977-2062).  ``params`` is one
+        ``(dim_index, (lo, hi), n_nodes)`` or a list of them, ``dim_index`` being the position in the result.  The value
+        tensor is repeated ``n_nodes`` times along each new axis -- the barycentric weights sum to one, so any coordinate
+        there gives the same value -- and the new dimension gets its own nodes, weights and differentiation matrix.  Host
+        only, as in the reference; returns a new built interpolant."""
+        if self.tensor_values is None:
+            raise RuntimeError("Call build() first")
+        from .tensor_train import _extrude_params
+        sorted_params = _extrude_params(params, self.num_dimensions)
+        tensor = np.asarray(self.tensor_values, dtype=float)
+        nodes, weights, diffs = list(self.nodes), list(self.weights), list(self.diff_matrices)
+        domain, n_nodes = [list(b) for b in self.domain], list(self.n_nodes)
+        for dim_idx, (lo, hi), n in sorted_params:                   # ascending: each index is final when it is taken
+            tensor = np.repeat(np.expand_dims(tensor, dim_idx), n, axis=dim_idx)
+            x = chebyshev_nodes(lo, hi, n)
+            w = compute_barycentric_weights(x)
+            nodes.insert(dim_idx, x)
+            weights.insert(dim_idx, w)
+            diffs.insert(dim_idx, compute_differentiation_matrix(x, w))
+            domain.insert(dim_idx, [lo, hi])
+            n_nodes.insert(dim_idx, n)
+        return self._reduced(np.ascontiguousarray(tensor), nodes, weights, diffs, domain, n_nodes)
+
     # ---------------------------------------------------------------- algebra
     # Reference barycentric.py:2433-2500.  The value tensors are combined with NumPy; the result shares this
     # object's nodes, weights and differentiation matrices, and its device model is built on first evaluation.

@@ -10,10 +10,17 @@
 // the slide that owns `dim` varies, so every other slide is evaluated once per row and the owner once per fibre point --
 // or not at all when it is one-dimensional, its value tensor being the fibre.  k_slider_fibre_sum then adds them up in
 // the evaluation's order and the same solver runs.
+//
+// The spline entry (pcx_spline_calculus_batch) has P pieces along `dim`, each with its own interval and node count: the
+// fibre points of all pieces go through the spline's own chunk evaluation (spline_eval_chunk: route, bucket, the pieces'
+// barycentric kernels), one launch solves the rows x P fibres (k_cheb1d_calculus_pieces, the same calc_row) and
+// k_spline_calc_merge joins the pieces of every row (spline_calc_kernels.h).
 
 #include "pcx_slider_internal.h"
+#include "pcx_spline_internal.h"
 #include "calculus_kernels.h"
 #include "slider_calc_kernels.h"
+#include "spline_calc_kernels.h"
 
 // rows per pass of the expand / evaluate / solve pipeline: at most this many fibre points in flight
 static const long kCalcChunkPoints = 1L << 21;
@@ -344,5 +351,100 @@ extern "C" int pcx_slider_calculus_batch(pcx_slider *h, int dim, const double *l
         if ((rc = calc_launch(c, rows, st))) return rc;
     }
     return out.download(mode, N, a.W, roots_out, counts_out, val_out, loc_out, st);
+    PCX_API_END
+}
+
+extern "C" int pcx_spline_calculus_batch(pcx_spline *h, int dim, const double *lo, const double *hi, const double *fixed,
+                                         int64_t N, int mode, double *roots_out, int32_t *counts_out, double *val_out,
+                                         double *loc_out) {
+    PCX_API_BEGIN
+    if (!h || !lo || !hi) return fail(PCX_ERR_INVALID, "NULL argument");
+    const int d = h->sd.d;
+    if (dim < 0 || dim >= d) return fail(PCX_ERR_INVALID, "dim %d out of range [0, %d]", dim, d - 1);
+    // the pieces along dim: index j there, 0 in every other dimension (C order over the per-dimension intervals)
+    const int P = h->sd.shape[dim];
+    long stride = 1;
+    for (int k = dim + 1; k < d; ++k) stride *= h->sd.shape[k];
+    std::vector<SplineCalcPiece> tab(P);
+    long F = 0, Wtot = 0;
+    int nmax = 1;
+    for (int j = 0; j < P; ++j) {
+        const pcx_bary *pc = h->pieces[(size_t)j * stride];
+        SplineCalcPiece &e = tab[j];
+        e.n = pc->dims.n[dim];
+        e.W = std::max(e.n - 1, 1);
+        e.lo = j == 0 ? lo[dim] : h->knots[h->sd.koff[dim] + j - 1];
+        e.hi = j == P - 1 ? hi[dim] : h->knots[h->sd.koff[dim] + j];
+        e.nodes = pc->d_nodes + pc->dims.off[dim];
+        e.wts = pc->d_wts + pc->dims.off[dim];
+        e.diff = pc->d_diff + pc->doff[dim];
+        e.voff = F;
+        e.roff = Wtot;
+        int rc = calc_check(e.n, mode, N, e.lo, e.hi, pc->d_diff, roots_out, counts_out, val_out, loc_out);
+        if (rc) return rc;
+        F += e.n;
+        Wtot += e.W;
+        nmax = std::max(nmax, e.n);
+    }
+    for (int i = 0; i < h->n_pieces; ++i)                      // one grid per index along dim (auto-N pieces may differ)
+        if (h->pieces[i]->dims.n[dim] != tab[(i / stride) % P].n)
+            return fail(PCX_ERR_INVALID, "piece %d has %d nodes along dim %d, the pieces of its interval %d", i,
+                        h->pieces[i]->dims.n[dim], dim, tab[(i / stride) % P].n);
+    int rc = calc_check_fixed(fixed, N, d, dim, lo, hi);
+    if (rc) return rc;
+    if (N == 0) return PCX_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    std::lock_guard<std::mutex> lk(h->mu);
+    hipStream_t st = h->stream;
+    const long chunk = std::max<long>(1, std::min<long>(N, kCalcChunkPoints / F));
+    // the expand kernel carries the piece index in grid.y, and one pass goes through spline_eval_chunk as one chunk
+    if (P > 65535) return fail(PCX_ERR_UNSUPPORTED, "%d pieces along dim %d: at most 65535", P, dim);
+    if (chunk * F > kChunkPoints) return fail(PCX_ERR_UNSUPPORTED, "%ld fibre points per row: at most %lld", F, (long long)kChunkPoints);
+    DevBuf d_tab, d_fixed, d_pts, d_vals, p_roots, p_counts, p_val, p_loc;
+    CalcDevOut out;
+    rc = d_tab.alloc((size_t)P * sizeof(SplineCalcPiece));
+    if (!rc) rc = d_fixed.alloc((size_t)N * (d - 1) * sizeof(double));
+    if (!rc) rc = d_pts.alloc((size_t)chunk * F * d * sizeof(double));
+    if (!rc) rc = d_vals.alloc((size_t)chunk * F * sizeof(double));
+    if (!rc) rc = p_roots.alloc(mode == 0 ? (size_t)chunk * Wtot * sizeof(double) : 0);
+    if (!rc) rc = p_counts.alloc((size_t)chunk * P * sizeof(int32_t));
+    if (!rc) rc = p_val.alloc(mode != 0 ? (size_t)chunk * P * sizeof(double) : 0);
+    if (!rc) rc = p_loc.alloc(mode != 0 ? (size_t)chunk * P * sizeof(double) : 0);
+    if (!rc) rc = out.alloc(mode, N, (int)Wtot);
+    if (rc) return rc;
+    // the table once per call, with a blocking copy: `tab` (pageable) has left the host when it returns
+    HIP_TRY(hipMemcpy(d_tab.p, tab.data(), (size_t)P * sizeof(SplineCalcPiece), hipMemcpyHostToDevice));
+    if (d > 1) HIP_TRY(hipMemcpyAsync(d_fixed.p, fixed, (size_t)N * (d - 1) * sizeof(double), hipMemcpyHostToDevice, st));
+    const SplineCalcPiece *dt = d_tab.as<SplineCalcPiece>();
+    SplineCalcOut po;
+    po.vals = d_vals.as<double>();
+    po.roots = p_roots.as<double>();
+    po.counts = p_counts.as<int32_t>();
+    po.val = p_val.as<double>();
+    po.loc = p_loc.as<double>();
+    const int m = nmax - 1;                                    // the LDS class, as calc_launch chooses it
+    auto finish = [&](int code) {                              // the device buffers are freed on return
+        (void)hipStreamSynchronize(st);
+        return code;
+    };
+    for (long r0 = 0; r0 < N; r0 += chunk) {
+        const long rows = std::min<long>(chunk, N - r0);
+        const unsigned bx = (unsigned)std::min<long>((rows * nmax * d + 255) / 256, 4096);
+        hipLaunchKernelGGL(k_spline_calc_expand, dim3(bx, (unsigned)P), dim3(256), 0, st,
+                           d_fixed.as<double>() + (size_t)r0 * (d - 1), rows, d, dim, dt, d_pts.as<double>());
+        if (hipGetLastError() != hipSuccess) return finish(fail(PCX_ERR_HIP, "k_spline_calc_expand launch failed"));
+        if ((rc = spline_eval_chunk(h, d_pts.as<double>(), rows * F, nullptr, 1, d_vals.as<double>()))) return finish(rc);
+        const unsigned fibres = (unsigned)(rows * P);
+        if (m <= 16) hipLaunchKernelGGL(k_cheb1d_calculus_pieces<16>, dim3(fibres), dim3(64), 0, st, dt, rows, mode, po);
+        else if (m <= 32) hipLaunchKernelGGL(k_cheb1d_calculus_pieces<32>, dim3(fibres), dim3(64), 0, st, dt, rows, mode, po);
+        else hipLaunchKernelGGL(k_cheb1d_calculus_pieces<64>, dim3(fibres), dim3(64), 0, st, dt, rows, mode, po);
+        if (hipGetLastError() != hipSuccess) return finish(fail(PCX_ERR_HIP, "k_cheb1d_calculus_pieces launch failed"));
+        hipLaunchKernelGGL(k_spline_calc_merge, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, dt, P, rows, mode,
+                           (int)Wtot, lo[dim], hi[dim], po, mode == 0 ? out.roots.as<double>() + (size_t)r0 * Wtot : nullptr,
+                           out.counts.as<int32_t>() + r0, mode != 0 ? out.val.as<double>() + r0 : nullptr,
+                           mode != 0 ? out.loc.as<double>() + r0 : nullptr);
+        if (hipGetLastError() != hipSuccess) return finish(fail(PCX_ERR_HIP, "k_spline_calc_merge launch failed"));
+    }
+    return finish(out.download(mode, N, (int)Wtot, roots_out, counts_out, val_out, loc_out, st));
     PCX_API_END
 }

@@ -112,6 +112,14 @@ struct SplinePieceModel {
     BarySmallScale sc;
 };
 
+// the knots of a piecewise interpolant as its routing kernels read them (route_kernels.h)
+struct SplineDims {
+    int d;
+    int nknots[PCX_MAX_DIMS];   // knots per dimension
+    int koff[PCX_MAX_DIMS];     // offset of dimension k's knots in knots_cat
+    int shape[PCX_MAX_DIMS];    // pieces per dimension = nknots + 1
+};
+
 // ---- tensor-train kernel parameters ---------------------------------------------
 struct TTDims {
     int d;

@@ -2,36 +2,12 @@
 // out of barycentric handles (pcx_bary.hip).  gfx950 only.
 
 #include "pcx_slider_internal.h"
+#include "pcx_spline_internal.h"
 #include "route_kernels.h"
 
 // ---------------------------------------------------------------------------------
-// spline (piecewise) handle
+// spline (piecewise) handle: struct pcx_spline lives in pcx_spline_internal.h
 // ---------------------------------------------------------------------------------
-struct pcx_spline {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    SplineDims sd;
-    int n_pieces = 0;
-    std::vector<pcx_bary *> pieces;      // borrowed
-    double *d_knots = nullptr;
-    int *d_counts = nullptr;             // n_pieces: histogram, then bucket cursors
-    int lds_hist = 1;                    // routing kernels count per workgroup in LDS (<= PCX_SPLINE_LDS_PIECES pieces)
-    // the per-piece launches of one batch are independent: they go round-robin over a few side streams so
-    // that small buckets overlap instead of queueing behind each other's launch latency
-    static const int kSide = 4;
-    hipStream_t side[kSide] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_join[kSide] = {nullptr, nullptr, nullptr, nullptr};
-    std::mutex mu;
-    HostStage stage;                     // host-pointer batches (and the points of pcx_spline_piece_ids)
-    Scratch s_piece, s_perm, s_partial;
-    // one launch for all pieces (pieces of equal shape on the lane-per-point kernel): per-piece model table,
-    // per-workgroup (piece, first slot) lists; staged through a pinned host buffer
-    bool fused_ok = false;
-    Scratch s_models, s_blk;
-    void *pin_stage = nullptr;
-    size_t pin_cap = 0;
-};
-
 extern "C" int pcx_spline_destroy(pcx_spline *h) {
     PCX_API_BEGIN
     if (!h) return PCX_OK;
@@ -76,6 +52,7 @@ extern "C" int pcx_spline_create(int device, int d, const int32_t *n_knots, cons
         h->sd.shape[k] = n_knots[k] + 1;
         for (int j = 1; j < n_knots[k]; ++j)
             if (!(knots_cat[nk_total + j - 1] <= knots_cat[nk_total + j])) { delete h; return fail(PCX_ERR_INVALID, "knots of dimension %d are not sorted", k); }
+        if (n_knots[k] > 0 && knots_cat) h->knots.insert(h->knots.end(), knots_cat + nk_total, knots_cat + nk_total + n_knots[k]);
         nk_total += n_knots[k];
         total *= n_knots[k] + 1;
         if (total > (1 << 20)) { delete h; return fail(PCX_ERR_UNSUPPORTED, "more than 2^20 pieces"); }
@@ -233,7 +210,7 @@ static int spline_launch_fused(pcx_spline *h, const double *dp, const std::vecto
 
 // One chunk of device-resident points through routing, bucketing and the per-piece launches, on h->stream
 // (results land in dout in point order; the launches are queued, not awaited).  Caller holds h->mu.
-static int spline_eval_chunk(pcx_spline *h, const double *dp, long cnt, const int32_t *derivs, int m, double *dout) {
+PCX_HIDDEN int spline_eval_chunk(pcx_spline *h, const double *dp, long cnt, const int32_t *derivs, int m, double *dout) {
     std::vector<int> counts, offsets;
     int rc = spline_bucket(h, dp, cnt, counts, offsets);
     if (rc) return rc;

@@ -1,0 +1,39 @@
+// pcx_spline_internal.h -- the spline (piecewise) handle as the translation units that serve it see it (pcx_spline.hip
+// creates and evaluates it, pcx_calculus.hip runs its calculus).  Not part of the ABI.
+#pragma once
+
+#include "pcx_bary_internal.h"
+
+// ---------------------------------------------------------------------------------
+// spline (piecewise) handle
+// ---------------------------------------------------------------------------------
+struct pcx_spline {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    SplineDims sd;
+    int n_pieces = 0;
+    std::vector<pcx_bary *> pieces;      // borrowed
+    std::vector<double> knots;           // knots_cat on the host (the piece edges of pcx_spline_calculus_batch)
+    double *d_knots = nullptr;
+    int *d_counts = nullptr;             // n_pieces: histogram, then bucket cursors
+    int lds_hist = 1;                    // routing kernels count per workgroup in LDS (<= PCX_SPLINE_LDS_PIECES pieces)
+    // the per-piece launches of one batch are independent: they go round-robin over a few side streams so
+    // that small buckets overlap instead of queueing behind each other's launch latency
+    static const int kSide = 4;
+    hipStream_t side[kSide] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev_fork = nullptr, ev_join[kSide] = {nullptr, nullptr, nullptr, nullptr};
+    std::mutex mu;
+    HostStage stage;                     // host-pointer batches (and the points of pcx_spline_piece_ids)
+    Scratch s_piece, s_perm, s_partial;
+    // one launch for all pieces (pieces of equal shape on the lane-per-point kernel): per-piece model table,
+    // per-workgroup (piece, first slot) lists; staged through a pinned host buffer
+    bool fused_ok = false;
+    Scratch s_models, s_blk;
+    void *pin_stage = nullptr;
+    size_t pin_cap = 0;
+};
+
+// pcx_spline.hip: one chunk of cnt device-resident points (cnt x d) through routing, bucketing and the per-piece
+// launches on h->stream, m specs (derivs NULL: the values), results into dout (cnt x m) in point order; the launches are
+// queued, not awaited.  Caller holds h->mu.
+PCX_HIDDEN int spline_eval_chunk(pcx_spline *h, const double *dp, long cnt, const int32_t *derivs, int m, double *dout);

@@ -10,12 +10,7 @@
 // route every point to its piece, bucket the points, then run the barycentric kernel once
 // per non-empty piece on that piece's bucket (its `perm` argument).
 // ---------------------------------------------------------------------------------
-struct SplineDims {
-    int d;
-    int nknots[PCX_MAX_DIMS];   // knots per dimension
-    int koff[PCX_MAX_DIMS];     // offset of dimension k's knots in knots_cat
-    int shape[PCX_MAX_DIMS];    // pieces per dimension = nknots + 1
-};
+// (struct SplineDims, the layout of the knots, is in pcx_common.h: the handle in pcx_spline_internal.h holds one)
 
 // One atomic per wave and distinct key instead of one per lane: the lanes of a wave that hold the same
 // key elect a leader, the leader adds their count, every lane gets base + its rank among them.  (With

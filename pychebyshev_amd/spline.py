@@ -16,11 +16,14 @@ launches all run on the device (``pcx_spline_eval_batch``: ``k_spline_piece_id``
 
 Auto-N pieces (``error_threshold``) build through the pieces' own doubling loop; ``.pcb`` files
 (class tag 2) are read and written byte-compatibly.  ``sobol_indices`` aggregates the pieces' device-side indices
-on the host as the reference does.  ``roots`` / ``minimize`` / ``maximize`` solve each piece along the
-dimension on the device and combine the pieces on the host.  ``+``, ``-``, ``*`` and ``/`` combine the pieces' value tensors on the host.
+on the host as the reference does.  ``roots_batch`` / ``minimize_batch`` / ``maximize_batch`` expand every row into the
+fibre points of all pieces along the dimension, evaluate them with the spline's own routing and kernels, solve every fibre
+and merge the pieces of a row on the device (``pcx_spline_calculus_batch``); ``roots`` / ``minimize`` / ``maximize`` are
+the one-row batch, or, above 64 nodes in a piece, the pieces' own calls merged on the host.  ``slice`` picks the pieces
+that contain the value and slices each on the device; ``extrude`` repeats every piece's tensor on the host.  ``+``, ``-``, ``*`` and ``/`` combine the pieces' value tensors on the host.
 ``integrate`` contracts each piece on the device and sums the pieces along the integrated dimensions;
 ``integrate_batch`` is the box integral with another box per row: one ``pcx_bary_box_batch`` launch per piece on the
-rows whose box reaches it.  Not provided: roots / minimize / maximize batches, extrude/slice, auto_knots.
+rows whose box reaches it.  Not provided: auto_knots.
 """
 from __future__ import annotations
 
@@ -475,40 +478,157 @@ class ChebyshevSpline(ErgonomicsMixin, DerivativeIdMixin):
         pieces = [self._pieces[int(np.ravel_multi_index(multi, self._shape))] for multi in itertools.product(*ranges)]
         return dim, pieces, sub
 
+    def _dim_counts(self, dim: int):
+        """Node counts along ``dim`` of the pieces with index 0, 1, ... there, or None when pieces that share an index
+        differ (auto-N pieces may): the device batch takes the nodes of index j from one piece."""
+        along = np.array([p.n_nodes[dim] for p in self._pieces], dtype=int).reshape(self._shape)
+        along = np.moveaxis(along, dim, 0).reshape(self._shape[dim], -1)
+        if np.any(along != along[:, :1]):
+            return None
+        return [int(v) for v in along[:, 0]]
+
+    def _calculus_batch(self, dim: int, rows: np.ndarray, mode: int):
+        """``pcx_spline_calculus_batch`` over validated rows (see :func:`pychebyshev_amd._calculus.run_batch`)."""
+        from . import _calculus
+        counts = self._dim_counts(dim)
+        s = self._dev()
+        lo = _lib.f64([float(b[0]) for b in self.domain])
+        hi = _lib.f64([float(b[1]) for b in self.domain])
+        rows = _lib.f64(rows)
+        N = rows.shape[0]
+
+        def call(r, c, v, loc):
+            return s.lib.pcx_spline_calculus_batch(s.handle, int(dim), _lib.p_f64(lo), _lib.p_f64(hi), _lib.p_f64(rows), N,
+                                                   mode, r, c, v, loc)
+        return _calculus.run_batch(call, s.lib, max(counts), N, mode, width=sum(max(n - 1, 1) for n in counts))
+
+    def _calculus(self, dim, fixed, mode: str):
+        """A single call: the one-row batch when every piece along ``dim`` has at most 64 nodes (one device call for all
+        pieces), else every piece on its own (their single calls finish long fibres on the host) and the host merge."""
+        from . import _calculus
+        dim, pieces, sub = self._calculus_pieces(dim, fixed)
+        counts = self._dim_counts(dim)
+        if counts is not None and max(counts) <= _calculus.MAX_DEVICE_N:
+            row = _calculus.fixed_row(self.num_dimensions, dim, list((sub or {}).items()))
+            out = self._calculus_batch(dim, row, _calculus._MODES[mode])
+            return _calculus.single_roots(*out) if mode == "roots" else _calculus.single_extremum(*out)
+        if mode == "roots":
+            return _calculus.merge_pieces("roots", [p.roots(dim, sub) for p in pieces], self.domain[dim])
+        return _calculus.merge_pieces(mode, [(p.minimize if mode == "min" else p.maximize)(dim, sub) for p in pieces])
+
     def roots(self, dim=None, fixed=None) -> np.ndarray:
         """Sorted roots along ``dim`` (reference spline.py:1762-1820): every piece along ``dim`` is solved on its own
-        domain (one device call each), the roots are concatenated, sorted, and near-duplicates at the knots
-        (``1e-10 (|domain[dim]| + 1)``) dropped."""
-        dim, pieces, sub = self._calculus_pieces(dim, fixed)
-        found = [p.roots(dim, sub) for p in pieces]
-        if not found:
-            return np.array([], dtype=float)
-        out = np.sort(np.concatenate(found))
-        if len(out) > 1:
-            scale = abs(self.domain[dim][1] - self.domain[dim][0]) + 1
-            out = out[np.concatenate([[True], np.diff(out) > 1e-10 * scale])]
-        return out
+        interval, the roots are concatenated in piece order and near-duplicates at the knots (``1e-10 (|domain[dim]| +
+        1)``) dropped -- in one device call (the one-row :meth:`roots_batch`) up to 64 nodes per piece."""
+        return self._calculus(dim, fixed, "roots")
 
     def minimize(self, dim=None, fixed=None):
         """``(value, location)`` of the minimum along ``dim`` over the pieces in order, strictly smaller wins
         (reference spline.py:1822-1865)."""
-        dim, pieces, sub = self._calculus_pieces(dim, fixed)
-        best = (float("inf"), 0.0)
-        for p in pieces:
-            val, loc = p.minimize(dim, sub)
-            if val < best[0]:
-                best = (val, loc)
-        return best
+        return self._calculus(dim, fixed, "min")
 
     def maximize(self, dim=None, fixed=None):
         """``(value, location)`` of the maximum along ``dim`` (reference spline.py:1867-1910)."""
-        dim, pieces, sub = self._calculus_pieces(dim, fixed)
-        best = (float("-inf"), 0.0)
-        for p in pieces:
-            val, loc = p.maximize(dim, sub)
-            if val > best[0]:
-                best = (val, loc)
-        return best
+        return self._calculus(dim, fixed, "max")
+
+    def _calculus_rows(self, dim, fixed) -> np.ndarray:
+        from . import _calculus
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        largest = [max(int(p.n_nodes[k]) for p in self._pieces) for k in range(self.num_dimensions)]
+        rows = _calculus.validate_batch_args(self.num_dimensions, dim, fixed, self.domain, largest)
+        if self._dim_counts(int(dim)) is None:
+            raise ValueError(f"pieces that share an interval of dimension {dim} differ in their node counts there: "
+                             f"the batched solver needs one grid per interval (the single-row calls handle this)")
+        return rows
+
+    def roots_batch(self, dim: int, fixed):
+        """Roots along ``dim`` for every row of ``fixed`` (host float64 ``(N, d-1)``: the other dimensions in increasing
+        order) in one device pass (extension; ``pcx_spline_calculus_batch``): the fibre points of every piece along
+        ``dim`` go through the spline's own evaluation, one launch solves all rows and pieces, a last kernel merges the
+        pieces of a row as :meth:`roots` does.  Returns ``(roots, counts)``: ``roots`` float64 ``(N, W)`` with ``W`` the
+        sum of ``max(n_j - 1, 1)`` over the pieces along ``dim``, ascending and NaN-padded; ``counts`` int32 ``(N,)``,
+        -1 where a piece's fibre was not finite or its eigenvalue iteration failed.  At most 64 nodes per piece."""
+        rows = self._calculus_rows(dim, fixed)
+        return self._calculus_batch(int(dim), rows, 0)
+
+    def minimize_batch(self, dim: int, fixed):
+        """``(values, locations)``, float64 ``(N,)``, of the minimum along ``dim`` for every row of ``fixed``
+        (extension; arguments as :meth:`roots_batch`).  NaN where a row failed."""
+        rows = self._calculus_rows(dim, fixed)
+        val, loc, _ = self._calculus_batch(int(dim), rows, 1)
+        return val, loc
+
+    def maximize_batch(self, dim: int, fixed):
+        """``(values, locations)`` of the maximum along ``dim`` for every row of ``fixed`` (extension)."""
+        rows = self._calculus_rows(dim, fixed)
+        val, loc, _ = self._calculus_batch(int(dim), rows, 2)
+        return val, loc
+
+    # ---------------------------------------------------------------- extrude / slice
+    def _reshaped(self, pieces, domain, knots, n_nodes) -> "ChebyshevSpline":
+        """A built spline over other dimensions than this one's: ``function=None``, no device handle yet, the form of
+        ``n_nodes`` (flat or nested), ``max_derivative_order`` and the device index kept."""
+        obj = self._with_pieces(pieces)
+        obj.num_dimensions = len(domain)
+        obj.domain = domain
+        obj.knots = knots
+        obj.n_nodes = n_nodes
+        obj._intervals = []
+        for (lo, hi), kn in zip(domain, knots):
+            edges = [lo] + list(kn) + [hi]
+            obj._intervals.append([(edges[i], edges[i + 1]) for i in range(len(edges) - 1)])
+        obj._shape = tuple(len(iv) for iv in obj._intervals)
+        return obj
+
+    def extrude(self, params) -> "ChebyshevSpline":
+        """Add dimensions along which the function is constant (reference spline.py:1391-1473).  ``params`` is one
+        ``(dim_index, (lo, hi), n_nodes)`` or a list of them, ``dim_index`` being the position in the result.  Every
+        piece is extruded (:meth:`ChebyshevApproximation.extrude`); a new dimension has no knots, one interval, and the
+        ``n_nodes`` entry ``[n]`` when the spline's ``n_nodes`` is nested, ``n`` when it is flat."""
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        from .tensor_train import _extrude_params
+        sorted_params = _extrude_params(params, self.num_dimensions)
+        domain = [list(b) for b in self.domain]
+        knots = [list(k) for k in self.knots]
+        n_nodes = [list(v) if isinstance(v, list) else v for v in self.n_nodes]
+        for dim_idx, (lo, hi), n in sorted_params:
+            domain.insert(dim_idx, [lo, hi])
+            knots.insert(dim_idx, [])
+            n_nodes.insert(dim_idx, [n] if self._n_nodes_nested else n)
+        # a new dimension has shape 1: the C order of the pieces stays
+        return self._reshaped([piece.extrude(sorted_params) for piece in self._pieces], domain, knots, n_nodes)
+
+    def slice(self, params) -> "ChebyshevSpline":
+        """Fix one or more dimensions (reference spline.py:1475-1575): ``params`` is one ``(dim_index, value)`` or a list.
+        Along a sliced dimension only the pieces of interval ``min(searchsorted(knots, value, "right"), shape - 1)``
+        survive -- a value on a knot belongs to the piece on its right -- and each is sliced on the device
+        (:meth:`ChebyshevApproximation.slice`).  Returns a new, lower-dimensional built spline."""
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        from .tensor_train import _slice_params
+        sorted_params = sorted(_slice_params(params, self.num_dimensions), key=lambda p: p[0], reverse=True)
+        for dim_idx, value in sorted_params:
+            lo, hi = self.domain[dim_idx]
+            if value < lo or value > hi:
+                raise ValueError(f"Slice value {value} for dim {dim_idx} is outside domain [{lo}, {hi}]")
+        domain = [list(b) for b in self.domain]
+        knots = [list(k) for k in self.knots]
+        n_nodes = [list(v) if isinstance(v, list) else v for v in self.n_nodes]
+        grid = np.empty(len(self._pieces), dtype=object)
+        grid[:] = self._pieces
+        grid = grid.reshape(self._shape)
+        for dim_idx, value in sorted_params:                       # descending: the lower indices stay valid
+            at = min(int(np.searchsorted(knots[dim_idx], value, side="right")), grid.shape[dim_idx] - 1) if knots[dim_idx] else 0
+            grid = np.take(grid, at, axis=dim_idx)
+            rest = grid.shape
+            flat = grid.reshape(-1)
+            for i in range(flat.size):
+                flat[i] = flat[i].slice((dim_idx, value))
+            grid = flat.reshape(rest)
+            del domain[dim_idx], knots[dim_idx], n_nodes[dim_idx]
+        return self._reshaped(list(grid.reshape(-1)), domain, knots, n_nodes)
 
     # ---------------------------------------------------------------- integration
     def integrate(self, dims=None, bounds=None):
