@@ -147,20 +147,25 @@ def merge_pieces(mode: str, found, domain=None, counts=None):
 # ---------------------------------------------------------------------------------------------- host restatement
 def roots_1d(values: np.ndarray, domain) -> np.ndarray:
     """Real roots in ``domain`` of the interpolant through ``values`` at ascending type-I nodes (reference
-    ``_roots_1d``): ``chebroots`` of the coefficients, |imag| < 1e-10, inside [-1, 1] up to 1e-10, clipped, mapped,
-    sorted, near-duplicates (``1e-10 (b - a + 1)``) dropped."""
+    ``_roots_1d``): ``chebroots`` of the coefficients, |imag| < 1e-10, inside [-1, 1] up to 1e-10, mapped, sorted,
+    near-duplicates (``1e-10 (b - a + 1)``) dropped.  An eigenvalue within 1e-10 of +-1, on either side, is that end
+    and gives exactly ``a`` or ``b``; the reference clips only from outside, which leaves a root at an end a few ulp
+    inside it as often as not."""
     from numpy.polynomial.chebyshev import chebroots
 
     from .barycentric import ChebyshevApproximation
     coeffs = ChebyshevApproximation._chebyshev_coefficients_1d(values)
     raw = chebroots(coeffs)
     tol = 1e-10
-    keep = [np.clip(r.real, -1.0, 1.0) for r in np.atleast_1d(raw)
-            if abs(r.imag) < tol and -1.0 - tol <= r.real <= 1.0 + tol]
-    if not keep:
+    keep = np.array([r.real for r in np.atleast_1d(raw)
+                     if abs(r.imag) < tol and -1.0 - tol <= r.real <= 1.0 + tol], dtype=float)
+    if not keep.size:
         return np.array([], dtype=float)
     a, b = domain
-    physical = np.sort(0.5 * (a + b) + 0.5 * (b - a) * np.array(keep))
+    physical = 0.5 * (a + b) + 0.5 * (b - a) * keep
+    physical[keep >= 1.0 - tol] = b
+    physical[keep <= tol - 1.0] = a
+    physical = np.sort(physical)
     if len(physical) > 1:
         physical = physical[np.concatenate([[True], np.diff(physical) > 1e-10 * (b - a + 1)])]
     return physical

@@ -1062,12 +1062,16 @@ class ChebyshevApproximation(ErgonomicsMixin, DerivativeIdMixin):
         """Sorted real roots along ``dim`` with every other dimension fixed (``fixed = {dim_index: value}``) by the
         colleague-matrix method (reference barycentric.py:2277-2327, _calculus.py:198-244).  The fibre is evaluated
         and solved on the device; above 64 nodes the solve runs on the host (NumPy ``chebroots``).  A non-finite
-        fibre raises ``numpy.linalg.LinAlgError``."""
+        fibre raises ``numpy.linalg.LinAlgError``.  Unlike the reference, which clips from outside only, a root
+        within ``1e-10`` (of the half-width) of an end of ``domain[dim]``, on either side of it, is returned as exactly
+        that end; the batched forms and the critical points of :meth:`minimize` / :meth:`maximize` follow the same
+        rule."""
         return self._calculus(dim, fixed, "roots")
 
     def minimize(self, dim=None, fixed=None):
         """``(value, location)`` of the minimum along ``dim`` (reference barycentric.py:2329-2377): the roots of the
-        derivative series and the two ends are the candidates, the first smallest value wins."""
+        derivative series and the two ends are the candidates, the first smallest value wins.  A critical point
+        within ``1e-10`` of an end is that end (see :meth:`roots`)."""
         return self._calculus(dim, fixed, "min")
 
     def maximize(self, dim=None, fixed=None):

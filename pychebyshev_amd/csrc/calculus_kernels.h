@@ -15,8 +15,10 @@
 //      roots some 1e-8 away from NumPy's (which are then accurate to ~1e-15)
 //   5. eigenvalues by the Francis double-shift QR of LAPACK dlahqr (eigenvalues only): deflation on a negligible
 //      subdiagonal, exceptional shifts every 10 iterations, 30 max(10, m) iterations at most, 2 x 2 blocks by dlanv2
-//   6. keep |imag| < 1e-10 and -1 - 1e-10 <= re <= 1 + 1e-10, clip, map to [lo, hi], rank-sort, drop a root that does
-//      not exceed its predecessor by more than 1e-10 (hi - lo + 1)
+//   6. keep |imag| < 1e-10 and -1 - 1e-10 <= re <= 1 + 1e-10; an eigenvalue within 1e-10 of +-1, on either side, is
+//      that end and gives exactly lo or hi (the reference clips only from outside, so a root at an end came back a few
+//      ulp inside it as often as not); the others are mapped to [lo, hi]; rank-sort, drop a root that does not exceed
+//      its predecessor by more than 1e-10 (hi - lo + 1)
 //   7. min/max: the candidates [lo, critical points..., hi] evaluated barycentrically on v (first node within 1e-14
 //      -> that node's value), the first best one wins (a NaN wins, as in np.argmin / np.argmax)
 //
@@ -502,11 +504,11 @@ CALC_FN int calc_roots(const CalcLds &L, int n, double lo, double hi) {
         if (!calc_hqr<S>(H, m, L.wr, L.wi)) return -1;
     }
     const double tol = 1e-10;
-    CALC_LANES(e, 0, m) {                                      // filter, clip, map
+    CALC_LANES(e, 0, m) {                                      // filter, snap to an end within tol of it, map
         const double re = L.wr[e];
         const bool ok = fabs(L.wi[e]) < tol && -1.0 - tol <= re && re <= 1.0 + tol;
-        const double t = fmin(fmax(re, -1.0), 1.0);
-        L.key[e] = ok ? 0.5 * (lo + hi) + 0.5 * (hi - lo) * t : NAN;
+        const double x = 0.5 * (lo + hi) + 0.5 * (hi - lo) * re;
+        L.key[e] = !ok ? NAN : (re >= 1.0 - tol ? hi : (re <= tol - 1.0 ? lo : x));
     }
     CALC_SYNC();
     int cnt = 0;

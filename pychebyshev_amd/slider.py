@@ -542,7 +542,9 @@ class ChebyshevSlider(ErgonomicsMixin, DerivativeIdMixin):
         """Sorted real roots along ``dim`` with every other dimension fixed (``fixed = {dim_index: value}``;
         reference slider.py:1178-1224, which slices to one dimension and re-interpolates at the nodes).  The fibre is
         formed and solved on the device; above 64 nodes the solve runs on the host (NumPy ``chebroots``).  A
-        non-finite fibre raises ``numpy.linalg.LinAlgError``."""
+        non-finite fibre raises ``numpy.linalg.LinAlgError``.  A root within ``1e-10`` (of the half-width) of an end
+        of ``domain[dim]``, on either side of it, is returned as exactly that end, and so is a critical point of
+        :meth:`minimize` / :meth:`maximize` (the reference clips from outside only)."""
         return self._calculus(dim, fixed, "roots")
 
     def minimize(self, dim=None, fixed=None):

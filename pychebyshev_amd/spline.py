@@ -519,7 +519,10 @@ class ChebyshevSpline(ErgonomicsMixin, DerivativeIdMixin):
     def roots(self, dim=None, fixed=None) -> np.ndarray:
         """Sorted roots along ``dim`` (reference spline.py:1762-1820): every piece along ``dim`` is solved on its own
         interval, the roots are concatenated in piece order and near-duplicates at the knots (``1e-10 (|domain[dim]| +
-        1)``) dropped -- in one device call (the one-row :meth:`roots_batch`) up to 64 nodes per piece."""
+        1)``) dropped -- in one device call (the one-row :meth:`roots_batch`) up to 64 nodes per piece.  A root within
+        ``1e-10`` (of the half-width) of an end of its piece's interval, on either side of it, is returned as exactly
+        that end, a knot included, and so is a critical point of :meth:`minimize` / :meth:`maximize` (the reference
+        clips from outside only)."""
         return self._calculus(dim, fixed, "roots")
 
     def minimize(self, dim=None, fixed=None):

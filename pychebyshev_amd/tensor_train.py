@@ -1029,7 +1029,9 @@ class ChebyshevTT(ErgonomicsMixin):
     def roots(self, dim=None, fixed=None) -> np.ndarray:
         """Sorted roots along user dimension ``dim`` with the others fixed (reference tensor_train.py:1749-1790): the
         fibre is the TT's values at the nodes of ``dim``, evaluated and solved on the device (above 64 nodes the
-        solve runs on the host).  ``dim`` and ``fixed`` are in the user's frame."""
+        solve runs on the host).  ``dim`` and ``fixed`` are in the user's frame.  A root within ``1e-10`` (of the
+        half-width) of an end of the domain along ``dim``, on either side of it, is returned as exactly that end, and so
+        is a critical point of :meth:`minimize` / :meth:`maximize` (the reference clips from outside only)."""
         return self._calculus(dim, fixed, "roots")
 
     def minimize(self, dim=None, fixed=None):

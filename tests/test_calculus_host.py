@@ -145,3 +145,17 @@ def test_matrix_dct_puts_no_spurious_root_inside_the_window_for_constants():
     for n in range(1, 129):
         for c in (5.0, -1.0, 1e-3):
             assert _calculus.roots_1d(np.full(n, c), (-1.0, 1.0)).size == 0, (n, c)
+
+
+@pytest.mark.parametrize("dom", [(-1.0, 1.0), (1e6, 1e6 + 1.0), (-1e-3, 1e-3), (-2.0, 3.0)])
+def test_restatement_returns_the_endpoints_of_lobatto_rows_exactly(dom):
+    """A root within 1e-10 of an end is that end, from either side: (1 - x^2) U_(n-3) has roots at both ends, and the
+    restatement -- the host route of fibres above 64 nodes -- returns lo and hi themselves on any interval, as the
+    device solver does."""
+    import calc_fibres as CF
+
+    def solve(n):
+        r = _calculus.roots_1d(CF.lobatto_row(n), dom)
+        return r, r.size
+    missed = CF.missed_endpoints(dom, solve, list(range(4, 65)) + [65, 96, 128])
+    assert not missed, missed

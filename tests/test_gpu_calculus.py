@@ -10,6 +10,7 @@ The worst errors are printed (pytest -s) for DESIGN."""
 import numpy as np
 import pytest
 
+from calc_fibres import WORST, _bary, _check_opt, _check_roots
 from conftest import golden
 import functions as F
 
@@ -17,8 +18,6 @@ from pychebyshev_amd import ChebyshevApproximation, ChebyshevSpline, ChebyshevTT
 from pychebyshev_amd.barycentric import chebyshev_nodes, compute_barycentric_weights, compute_differentiation_matrix
 
 pytestmark = pytest.mark.gpu
-
-WORST = {"root": 0.0, "value": 0.0, "location": 0.0}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -31,39 +30,6 @@ def _report():
 @pytest.fixture(scope="module")
 def g20():
     return golden("g20_calculus")
-
-
-def _check_roots(got, want, a, b, tag):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (tag, got, want)
-    if want.size:
-        err = float(np.max(np.abs(got - want))) / (b - a)
-        WORST["root"] = max(WORST["root"], err)
-        assert err <= 1e-10, (tag, got, want)
-
-
-def _check_opt(got, want, scale, a, b, value_at, tag):
-    """got / want = (value, location); value_at(x) evaluates the interpolant along the fibre."""
-    ev = abs(got[0] - want[0]) / scale
-    WORST["value"] = max(WORST["value"], ev)
-    assert ev <= 1e-12, (tag, got, want)
-    el = abs(got[1] - want[1]) / (b - a)
-    if el <= 1e-8:
-        WORST["location"] = max(WORST["location"], el)
-    else:       # not well defined: a flat optimum or a tie -- the point found must be as good
-        assert a <= got[1] <= b, (tag, got, want)
-        assert abs(value_at(got[1]) - want[0]) <= 1e-12 * scale, (tag, got, want)
-
-
-def _bary(v, x, w):
-    def at(t):
-        d = t - x
-        hit = np.nonzero(np.abs(d) < 1e-14)[0]
-        if hit.size:
-            return float(v[hit[0]])
-        u = w / d
-        return float(u @ v / u.sum())
-    return at
 
 
 def _rand(g, n):
