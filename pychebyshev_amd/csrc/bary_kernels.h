@@ -200,10 +200,48 @@ __device__ __forceinline__ pcx_seed<R> load_seed(pcx_seed_ptr seed, long t, int 
 // LDS byte offset row * PW * 8 of its table row (16 bits: rows <= 255, PW <= 32), so that a look-up address is the
 // lane's table base plus a half-word -- one vector instruction per field instead of extract + shift-add.  Per tile t
 // and lane group g two 16-byte words, [t][g][w][j]: word 0 holds fields 0 | 1 << 16 of rows j = 0..3, word 1 fields
-// 2 | 3 << 16 (read only when NF >= 3).  One table per PW (pcx_bary_create).
-__device__ __forceinline__ pcx_u4 load_row_offs(const unsigned *__restrict__ offs, long t, int g, int w) {
-    const uint4 q = reinterpret_cast<const uint4 *>(offs)[8 * t + 2 * g + w];
-    return pcx_u4{{q.x, q.y, q.z, q.w}};
+// 2 | 3 << 16 (read only when NF >= 3).  One table per PW (pcx_bary_create); read by k_bary_mfma's load_codes.
+
+// Buffer resources of the pipelined loop.  It loads fragments, row codes / offsets and seeds as resource base + lane offset
+// (a loop-invariant VGPR) + scalar or immediate offset, so walking the tables costs scalar instructions only.  A resource is
+// a WINDOW of one table, from the tile being read to the table's end, rebased per row tile with 64-bit scalar arithmetic --
+// offsets inside a window stay below two tiles whatever the size of the table -- and sized to the byte (the size field has
+// 32 bits: a longer rest is cut to the whole tiles that fit), so that a load past the end of the table returns zero.
+// Everything a window is built from must be wave-uniform: kernel arguments, block indices, and pointers passed through
+// pcx_uniform.
+typedef __amdgpu_buffer_rsrc_t pcx_rsrc;
+__device__ __forceinline__ const char *pcx_uniform(const void *p) {
+    const unsigned long long a = (unsigned long long)p;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a);
+    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+    return (const char *)(((unsigned long long)hi << 32) | lo);
+}
+// the window from tile t to the end of a table of `tiles` tiles of TILE bytes each
+template <unsigned TILE>
+__device__ __forceinline__ pcx_rsrc buffer_window(const char *p, int tiles, int t) {
+    const unsigned left = (unsigned)(tiles - t);
+    const unsigned held = left < 0xffffffffu / TILE ? left : 0xffffffffu / TILE;       // whole tiles within 32 bits
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(p + (size_t)t * TILE), 0, (int)(held * TILE), 0x00020000);
+}
+__device__ __forceinline__ double buffer_f64(pcx_rsrc rs, int voff, int soff) {
+    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 0));
+}
+__device__ __forceinline__ pcx_u4 buffer_u4(pcx_rsrc rs, int voff, int soff) {
+    const auto q = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0);
+    return pcx_u4{{q[0], q[1], q[2], q[3]}};
+}
+// load_seed through the window of tile t over the seed array; voff = the lane group's slot g * R * 32
+template <int R>
+__device__ __forceinline__ pcx_seed<R> buffer_seed(pcx_rsrc rs, int voff) {
+    pcx_seed<R> q;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const auto lo = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 32 * r, 0);
+        const auto hi = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 32 * r + 16, 0);
+        typedef unsigned u8v __attribute__((ext_vector_type(8)));
+        q.v[r] = __builtin_bit_cast(pcx_d4, (u8v){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
+    }
+    return q;
 }
 
 template <int NF>
@@ -374,7 +412,7 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
     // of tile t+1 are fetched at k-step CODE_STEP of tile t, behind the last look-up, straight into
     // the registers the look-ups read: no second set and no copies, and (loads return in order) by
     // the top of tile t+1 they are the oldest loads in flight, so waiting for them drains nothing.
-    // The narrow instantiations read pre-scaled row offsets instead of row codes (load_row_offs).
+    // The narrow instantiations read pre-scaled row offsets instead of row codes (above load_row_codes).
     // The seed of tile t+1 (R > 0) is fetched with its first fragments.
     // Fences keep hipcc from sinking the loads back to their uses.  Same arithmetic in the same
     // order as the plain loop below: identical results.
@@ -383,12 +421,23 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
     constexpr bool OFFS = PIPELINED && !WIDE && !G0;     // row offsets (two fields per word) instead of row codes
     constexpr bool CODE2 = WIDE || (OFFS && NF >= 3);    // a second word per row
     constexpr int CODE_STEP = 8;       // the last look-up is at k-step 6 (7: wide); < 12 <= KS
+    // Its loads go through buffer windows (buffer_window): the tables' wave-uniform bases and exact sizes, the bytes of a
+    // tile in each, and the lane offsets, which never change.
+    constexpr unsigned FRAG_TILE = KS * 512, SEED_TILE = 128 * (R > 0 ? R : 1), CODE_TILE = OFFS ? 128 : 64;
+    const char *const ufrag = PIPELINED ? pcx_uniform((const double *)frag) : nullptr;
+    const char *const useed = PIPELINED ? ufrag + (size_t)plan.MT * FRAG_TILE : nullptr;       // the seed array lies behind the image
+    const char *const ucode = PIPELINED ? pcx_uniform(OFFS ? rowoff : rowcode) : nullptr;
+    const char *const ucode_hi = (PIPELINED && WIDE) ? pcx_uniform(rowcode_hi) : nullptr;
+    const int frag_lane = lane * 8, seed_lane = g * 32 * R, code_lane = g * (int)(CODE_TILE / 4);
+    auto frag_window = [&](int t) { return buffer_window<FRAG_TILE>(ufrag, plan.MT, t); };
+    auto seed_window = [&](int t) { return buffer_window<SEED_TILE>(useed, plan.MT, t); };
     unsigned cc[4] = {0u, 0u, 0u, 0u}, cch[4] = {0u, 0u, 0u, 0u};
-    auto load_codes = [&](long t) {
-        const pcx_u4 q = OFFS ? load_row_offs(rowoff, t, g, 0) : load_row_codes(rowcode, t, g);
+    auto load_codes = [&](int t) {
+        const pcx_rsrc cw = buffer_window<CODE_TILE>(ucode, plan.MT, t);
+        const pcx_u4 q = buffer_u4(cw, code_lane, 0);
         pcx_u4 qh = q;
-        if constexpr (WIDE) qh = load_row_codes(rowcode_hi, t, g);
-        else if constexpr (CODE2) qh = load_row_offs(rowoff, t, g, 1);
+        if constexpr (WIDE) qh = buffer_u4(buffer_window<CODE_TILE>(ucode_hi, plan.MT, t), code_lane, 0);
+        else if constexpr (CODE2) qh = buffer_u4(cw, code_lane, 16);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             cc[j] = q.v[j];
@@ -424,11 +473,117 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
 #pragma unroll
     for (int i = 0; i < DEPTH; ++i) head[i] = 0.0;
     if (PIPELINED && t_begin < t_end) {
-        if constexpr (R > 0) seed_acc(load_seed<R>(seed, t_begin, g));
+        if constexpr (R > 0) seed_acc(buffer_seed<R>(seed_window(t_begin), seed_lane));
         load_codes(t_begin);
+        const pcx_rsrc fw = frag_window(t_begin);
 #pragma unroll
-        for (int i = 0; i < DEPTH; ++i) head[i] = tf[((size_t)t_begin * KS + i) * 64];
+        for (int i = 0; i < DEPTH; ++i) head[i] = buffer_f64(fw, frag_lane, i * 512);
     }
+    // DEFER (narrow pipelined instantiations): two accumulator sets alternate per tile.  Tile t+1's seed is formed into
+    // the idle set behind tile t's last matrix instructions without waiting for their results, and tile t's epilogue --
+    // its 8 cs FMAs, the chunk-end fold and the split store -- runs at k-step 1 of tile t+1, when tile t's results have
+    // retired behind that tile's first matrix instructions and before k-step 2 overwrites w[nt][0]; after the loop one
+    // flush finishes the last tile.  No wave then waits for a matrix instruction at the hand-over.  Every addition into
+    // cs, total and partial keeps its place in the order.  The second set is 8 NT registers: instantiations whose B
+    // operands alone are more than 64 doubles per lane (36 and 40 k-steps at two column tiles) do not have them.
+    // The loop is written out beside the one below, which the other instantiations keep unchanged: routed through
+    // shared lambdas, hipcc spilled in wide kernels that do not spill today.
+    constexpr bool DEFER = OFFS && NT * KS <= 64;
+    if constexpr (DEFER) {
+        pcx_d4 acc2[NT];
+        double w[NT][4];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {           // nothing is pending before the first tile: its epilogue adds +0.0 * +0.0
+            if constexpr (R == 0) acc[nt] = (pcx_d4){0.0, 0.0, 0.0, 0.0};
+            acc2[nt] = (pcx_d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w[nt][j] = 0.0;
+        }
+        auto add_tile = [&](pcx_d4 (&a)[NT]) {       // a tile's results times its head weights into the chunk sum
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) cs[nt] = __builtin_fma(a[nt][j], w[nt][j], cs[nt]);
+        };
+        auto end_chunk = [&](int t) {               // the chunk that ends with tile t
+            if (split) {
+                const int ch = t / PCX_CHUNK_TILES;
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    long pidx = base + 16 * nt + c;
+                    if (pidx < N)
+                        partial[(((size_t)blockIdx.z * nchunks + ch) * 4 + g) * (size_t)part_n + (pidx - part_p0)] = cs[nt];
+                }
+            }
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) { total[nt] += cs[nt]; cs[nt] = 0.0; }
+        };
+        // tile t into `cur`; the epilogue of tile t-1, whose results are in `idle`, at k-step 1; then tile t+1's seed into `idle`
+        auto tile = [&](int t, pcx_d4 (&cur)[NT], pcx_d4 (&idle)[NT]) {
+            const int t_next = (t + 1 < t_end) ? t + 1 : t;
+            const pcx_rsrc ft = frag_window(t), fn = frag_window(t_next);
+            pcx_seed<R> sdn;
+            double ring[DEPTH];
+#pragma unroll
+            for (int i = 0; i < DEPTH; ++i) ring[i] = head[i];
+            double wr[4][NT][4];
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                const double a = ring[s % DEPTH];
+                if (s + DEPTH < KS) ring[s % DEPTH] = buffer_f64(ft, frag_lane, (s + DEPTH) * 512);
+                else head[s + DEPTH - KS] = buffer_f64(fn, frag_lane, (s + DEPTH - KS) * 512);
+                if constexpr (R > 0) {
+                    if (s == KS - DEPTH) sdn = buffer_seed<R>(seed_window(t_next), seed_lane);
+                }
+                if (s == CODE_STEP) load_codes(t_next);
+                if (s == 1) {
+                    add_tile(idle);
+                    if (t > t_begin && t % PCX_CHUNK_TILES == 0) end_chunk(t - 1);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (s == 2 * j) {
+#pragma unroll
+                        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                            for (int f = 0; f < (NF < 4 ? NF : 4); ++f) wr[j][nt][f] = head_entry(j, nt, f);
+                    }
+                    if (s == 2 * j + 2) {
+#pragma unroll
+                        for (int nt = 0; nt < NT; ++nt)
+                            w[nt][j] = NF >= 4 ? (wr[j][nt][0] * wr[j][nt][1]) * (wr[j][nt][2] * wr[j][nt][3])
+                                     : (NF == 3 ? (wr[j][nt][0] * wr[j][nt][1]) * wr[j][nt][2]
+                                                : wr[j][nt][0] * wr[j][nt][1]);
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+                    cur[nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, B[nt][s], cur[nt], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) idle[nt] = (pcx_d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) idle[nt][j] = __builtin_fma(sdn.v[r][j], ws[nt][r], idle[nt][j]);
+        };
+        int t = t_begin;
+        for (; t + 1 < t_end; t += 2) {
+            tile(t, acc, acc2);
+            tile(t + 1, acc2, acc);
+        }
+        if (t < t_end) {                            // the last tile is still pending
+            tile(t, acc, acc2);
+            add_tile(acc);
+        } else if (t_begin < t_end) {
+            add_tile(acc2);
+        }
+        if (t_begin < t_end) end_chunk(t_end - 1);  // t_end is the end of a chunk or of the tensor
+    } else
     for (int t = t_begin; t < t_end; ++t) {
         double w[NT][4];
         pcx_seed<R> sdn;
@@ -436,10 +591,9 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
             if constexpr (R > 0) sdn = load_seed<R>(seed, t, g);
             seed_acc(sdn);
         }
-        const gptr_t tt = tf + (size_t)t * KS * 64;
         if constexpr (PIPELINED) {
             const int t_next = (t + 1 < t_end) ? t + 1 : t;
-            const gptr_t tn = tf + (size_t)t_next * KS * 64;
+            const pcx_rsrc ft = frag_window(t), fn = frag_window(t_next);
             double ring[DEPTH];
 #pragma unroll
             for (int i = 0; i < DEPTH; ++i) ring[i] = head[i];
@@ -448,10 +602,10 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
                 const double a = ring[s % DEPTH];
-                if (s + DEPTH < KS) ring[s % DEPTH] = tt[(s + DEPTH) * 64];
-                else head[s + DEPTH - KS] = tn[(s + DEPTH - KS) * 64];
+                if (s + DEPTH < KS) ring[s % DEPTH] = buffer_f64(ft, frag_lane, (s + DEPTH) * 512);
+                else head[s + DEPTH - KS] = buffer_f64(fn, frag_lane, (s + DEPTH - KS) * 512);
                 if constexpr (R > 0) {          // with tile t+1's first fragments: live for DEPTH k-steps only
-                    if (s == KS - DEPTH) sdn = load_seed<R>(seed, t_next, g);
+                    if (s == KS - DEPTH) sdn = buffer_seed<R>(seed_window(t_next), seed_lane);
                 }
                 if (s == CODE_STEP) load_codes(t_next);
 #pragma unroll
@@ -490,6 +644,7 @@ k_bary_mfma(BaryDims dims, BaryMfmaPlan plan, const double *__restrict__ nodes,
                 __builtin_amdgcn_sched_barrier(0);
             }
         } else {
+            const gptr_t tt = tf + (size_t)t * KS * 64;
             const pcx_u4 q = load_row_codes(rowcode, t, g);
             pcx_u4 qh = q;
             if (WIDE) qh = load_row_codes(rowcode_hi, t, g);

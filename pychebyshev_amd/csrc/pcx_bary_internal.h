@@ -50,7 +50,7 @@ struct pcx_bary {
     unsigned *d_rowcode = nullptr, *d_kcode = nullptr;
     unsigned *d_rowcode_hi = nullptr, *d_kcode_hi = nullptr;   // fields 4..7 (wide plans only)
     bool wide = false;      // more than four head or tail dimensions
-    // pipelined narrow plans (KS >= 12): the row codes as pre-scaled LDS byte offsets, one table per PW = 16, 32 (load_row_offs)
+    // pipelined narrow plans (KS >= 12): the row codes as pre-scaled LDS byte offsets, one table per PW = 16, 32 (bary_kernels.h)
     unsigned *d_rowoff[2] = {nullptr, nullptr};
     int tail_mode = 1;               // tail split of large launches (launch_mfma_t): 1 where the row-tile walk is long enough to pay
                                      // for the second kernel; PCX_BARY_TAIL=0 at create: never, =2: wherever the geometry allows
