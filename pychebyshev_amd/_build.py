@@ -19,22 +19,24 @@ LIB = os.path.join(HERE, "libpcx_hip.so")
 # translation unit -> headers it includes (an object is rebuilt when any of them is newer)
 PCX_H = os.path.join("..", "..", "include", "pcx.h")
 HOST_H = ["pcx_common.h", "pcx_internal.h", PCX_H]
+BARY_H = HOST_H + ["pcx_bary_internal.h", "bary_plan.h"]
 SOURCES = {
     "pcx_core.hip": HOST_H,
-    "pcx_bary.hip": HOST_H + ["pcx_bary_internal.h", "bary_kernels.h", "bary_mfma_launch.h", "gather_kernels.h", "sobol_kernels.h"],
-    "pcx_bary_seed1.hip": HOST_H + ["pcx_bary_internal.h", "bary_kernels.h", "bary_mfma_launch.h"],
-    "pcx_bary_seed2.hip": HOST_H + ["pcx_bary_internal.h", "bary_kernels.h", "bary_mfma_launch.h"],
-    "pcx_bary_box.hip": HOST_H + ["pcx_bary_internal.h", "bary_kernels.h", "bary_box_kernels.h"],
-    "pcx_bary_grid.hip": HOST_H + ["pcx_bary_internal.h", "bary_grid_kernels.h", "bary_weights.h"],
-    "pcx_bary_kfold.hip": HOST_H + ["pcx_bary_internal.h", "bary_kfold_kernels.h"],
-    "pcx_spline.hip": HOST_H + ["pcx_bary_internal.h", "pcx_slider_internal.h", "pcx_spline_internal.h", "gather_kernels.h",
+    "pcx_bary_plan.hip": HOST_H + ["bary_plan.h"],
+    "pcx_bary.hip": BARY_H + ["bary_kernels.h", "bary_mfma_launch.h", "gather_kernels.h", "sobol_kernels.h"],
+    "pcx_bary_seed1.hip": BARY_H + ["bary_kernels.h", "bary_mfma_launch.h"],
+    "pcx_bary_seed2.hip": BARY_H + ["bary_kernels.h", "bary_mfma_launch.h"],
+    "pcx_bary_box.hip": BARY_H + ["bary_kernels.h", "bary_box_kernels.h"],
+    "pcx_bary_grid.hip": BARY_H + ["bary_grid_kernels.h", "bary_weights.h"],
+    "pcx_bary_kfold.hip": BARY_H + ["bary_kfold_kernels.h"],
+    "pcx_spline.hip": BARY_H + ["pcx_slider_internal.h", "pcx_spline_internal.h", "gather_kernels.h",
                        "route_kernels.h"],
-    "pcx_slider_box.hip": HOST_H + ["pcx_bary_internal.h", "pcx_slider_internal.h", "gather_kernels.h", "slider_calc_kernels.h"],
+    "pcx_slider_box.hip": BARY_H + ["pcx_slider_internal.h", "gather_kernels.h", "slider_calc_kernels.h"],
     "pcx_tt.hip": HOST_H + ["tt_kernels.h", "tt_lpp_kernels.h", "tt_fd_kernels.h"],
     "pcx_tt_box.hip": HOST_H + ["tt_lpp_kernels.h", "tt_box_kernels.h"],
     "pcx_ttbuild.hip": HOST_H + ["ttcross_kernels.h", "ttsvd_kernels.h", "tt_round_kernels.h"],
     "pcx_tt_als.hip": HOST_H + ["tt_als_kernels.h"],
-    "pcx_calculus.hip": HOST_H + ["pcx_bary_internal.h", "pcx_slider_internal.h", "pcx_spline_internal.h", "gather_kernels.h",
+    "pcx_calculus.hip": BARY_H + ["pcx_slider_internal.h", "pcx_spline_internal.h", "gather_kernels.h",
                          "calculus_kernels.h", "slider_calc_kernels.h", "spline_calc_kernels.h"],
     "pcx_comm.hip": [PCX_H],
 }

@@ -9,14 +9,6 @@
 #include "pcx_bary_internal.h"
 #include "bary_kernels.h"
 
-static size_t mfma4_lds_bytes(const BaryDims &dm, int ks) {
-    return ((size_t)8 * (dm.sum_n + 2) * 32 + (size_t)2 * ks * 64) * sizeof(double);
-}
-
-static size_t mfma_lds_bytes(const BaryDims &dm, int nt) {
-    return (size_t)4 * (dm.sum_n + 2) * 16 * nt * sizeof(double);
-}
-
 // Workgroups of `kern` the device holds at once (256 threads, `lds` bytes each): the occupancy query times the
 // compute units, at most the 512 (256 CUs at two per CU) every launch was sized for before the query existed.
 static int resident_slots(const void *kern, size_t lds, int device, int *slots) {

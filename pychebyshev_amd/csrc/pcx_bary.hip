@@ -1,7 +1,9 @@
 // pcx_bary.hip -- C ABI of libpcx_hip.so (see include/pcx.h): the barycentric handle.  gfx950 only.
 //
-// Host side: argument validation, device buffers, launch planning, kernel launches, host-pointer pipelines and the
-// single-process fan-out.  No CPU arithmetic fallback lives here: every numeric result comes from a HIP kernel.
+// Host side: argument validation, device buffers, kernel launches, host-pointer pipelines and the single-process
+// fan-out; the launch plan of a handle is made in pcx_bary_plan.hip (bary_plan.h).  No CPU arithmetic fallback lives here: every numeric result comes from a HIP kernel.
+
+#include <memory>
 
 #include "pcx_bary_internal.h"
 #include "bary_kernels.h"
@@ -12,73 +14,20 @@
 // ---------------------------------------------------------------------------------
 // barycentric handle
 // ---------------------------------------------------------------------------------
-// How many dim-0 orders above its base tensor's a slab GEMM serves.  Differentiating AFTER the contraction (as the
-// reference's vectorized_eval_multi does) rounds differently from the reference's batch path, which differentiates the
-// tensor first: each D_0 applied to the partial sums amplifies their rounding by ~|D_0| |P| / |result|.  One level keeps
-// 5-D Black-Scholes delta / vanna within 2e-13 of the reference's batch result; two levels put gamma at 4.4e-12 --
-// outside the 1e-12 bar -- so the default is 1 (price + delta share a GEMM, gamma keeps its own);
-// PCX_BARY_G0_SPAN=2 trades that for one GEMM less, 0 switches the grouping off.
-static const int g_g0_span_default = [] { const char *e = getenv("PCX_BARY_G0_SPAN"); return e ? std::min(8, std::max(0, atoi(e))) : 1; }();
-
-// Largest measured deviation of a shared spec from its own GEMM (relative to the probe batch's scale) at which a pair is
-// still formed.  3e-13 keeps a factor of three to the 1e-12 parity bar for whatever batch and pairing order follow
-// (PCX_BARY_GROUP_TOL / pcx_bary_set_group_tolerance override it).
-static const double g_group_tol_default = [] { const char *e = getenv("PCX_BARY_GROUP_TOL"); double v = e ? atof(e) : 0.0; return v > 0.0 ? v : 3e-13; }();
-
-static const long kSmallTensorElems = 4096;   // auto: tensors up to this size run on k_bary_small
 static const int kCacheSpecs = 96;    // derivative tensors kept per handle besides the untransformed one
 
-// every k-step count up to 32 is instantiated: no padding of the folded K axis beyond 4;
-// 36..64 (one column tile per wave only: the B operands alone are up to 128 VGPRs) let two
-// tail dimensions of 12..16 nodes fold into K; 42 exists in the seeded sets only (13 x 13 = 1 + 4 x 42)
-static const int kKsList[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22,
-                              23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 36, 40, 42, 44, 48, 52, 56, 60, 64};
-
-// K columns of which the first R are the accumulators' seed: the instantiated k-step count that runs the rest
-static int pick_ks(int K, int R = 0) {
-    int need = (K - R + 3) / 4;
-    for (int ks : kKsList)
-        if (ks >= need && (ks != 42 || R > 0)) return ks;
-    return -1;
-}
-
-// K mod 4 = 1 or 2: those columns become the seed of the accumulators (R vector FMAs per accumulator register)
-// and the k-loop runs (K - R) / 4 whole k-steps -- against a k-step of its own that multiplies mostly padding.
-// A remainder of 3 stays a k-step (12 NT vector FMAs against NT matrix instructions).  PCX_BARY_SEED=0, read per
-// handle (a process may build both forms: tests, tools/seed_ab.py), keeps every plan unseeded.
-static int seed_columns(long K, bool seed) {
-    const int r = (int)(K % 4);
-    return (seed && K > 4 && (r == 1 || r == 2)) ? r : 0;
-}
-
-// choose the head/tail split minimising the estimated time: MT row tiles, each KS MFMAs plus
-// an epilogue (head-weight look-ups and products) worth about 5 MFMAs (measured on 15^4,
-// tools/bary_rate_probe.py); the single-column-tile kernels re-read A twice as often
-// (costs in half MFMAs: a seeded tile pays about half a matrix instruction for its R x 4 NT vector FMAs)
-static bool plan_mfma(const BaryDims &dm, BaryMfmaPlan &best, bool seed) {
-    bool found = false;
-    long best_cost = 0;
-    for (int split = std::max(0, dm.d - 2 * PCX_CODE_FIELDS); split < dm.d; ++split) {
-        if (split > 2 * PCX_CODE_FIELDS) continue;  // head dims must fit the two words of a row code
-        long M = 1, K = 1, head_rows = 0, tail_rows = 0;
-        for (int k = 0; k < split; ++k) { M *= dm.n[k]; head_rows += dm.n[k]; }
-        for (int k = split; k < dm.d; ++k) { K *= dm.n[k]; tail_rows += dm.n[k]; }
-        if (K > 256 || M > (1 << 24)) continue;
-        if (head_rows > PCX_MAX_PART_ROWS || tail_rows > PCX_MAX_PART_ROWS) continue;   // 8-bit code fields per table part
-        const int R = seed_columns(K, seed);
-        int ks = pick_ks((int)K, R);
-        if (ks < 0) continue;
-        long mt = (M + 15) / 16;
-        long cost = mt * (2 * ks + 10 + (R > 0 ? 1 : 0)) * (ks > 32 ? 23 : 20);
-        if (!found || cost < best_cost || (cost == best_cost && K > best.K)) {
-            found = true;
-            best_cost = cost;
-            best.split = split; best.M = (int)M; best.K = (int)K; best.MT = (int)mt; best.KS = ks; best.R = R;
-            best.tail_base = (int)head_rows + 1;
-            best.rows = dm.sum_n + 2;
-        }
-    }
-    return found;
+// everything the handle owns; the caller has made its device current and drained its stream (pcx_bary_destroy)
+pcx_bary::~pcx_bary() {
+    for (auto &kv : cache) kv.second.free_all();
+    for (void *p : {(void *)d_tab, (void *)d_nodes, (void *)d_wts, (void *)d_diff, (void *)d_cheb, (void *)d_boxq, (void *)d_snodes,
+                    (void *)d_gsnodes, (void *)d_rowcode, (void *)d_kcode, (void *)d_rowcode_hi, (void *)d_kcode_hi,
+                    (void *)d_rowcode_g0, (void *)d_rowoff[0], (void *)d_rowoff[1]})
+        (void)hipFree(p);
+    for (Scratch *sc : {&s_partial, &s_cheb[0], &s_cheb[1], &s_sobol, &s_rot, &s_rot2}) sc->release();
+    for (pcx_bary *r : rot)
+        if (r) pcx_bary_destroy(r);
+    stage.release();
+    if (stream) (void)hipStreamDestroy(stream);
 }
 
 extern "C" int pcx_bary_destroy(pcx_bary *h) {
@@ -86,23 +35,6 @@ extern "C" int pcx_bary_destroy(pcx_bary *h) {
     if (!h) return PCX_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (auto &kv : h->cache) kv.second.free_all();
-    (void)hipFree(h->d_tab);
-    h->s_partial.release();
-    (void)hipFree(h->d_nodes); (void)hipFree(h->d_wts); (void)hipFree(h->d_diff);
-    (void)hipFree(h->d_cheb);
-    (void)hipFree(h->d_boxq);
-    h->s_cheb[0].release(); h->s_cheb[1].release(); h->s_sobol.release();
-    (void)hipFree(h->d_snodes);
-    (void)hipFree(h->d_gsnodes);
-    (void)hipFree(h->d_rowcode); (void)hipFree(h->d_kcode);
-    (void)hipFree(h->d_rowcode_hi); (void)hipFree(h->d_kcode_hi);
-    (void)hipFree(h->d_rowcode_g0);
-    (void)hipFree(h->d_rowoff[0]); (void)hipFree(h->d_rowoff[1]);
-    for (pcx_bary *&r : h->rot) { if (r) pcx_bary_destroy(r); r = nullptr; }
-    h->stage.release();
-    h->s_rot.release(); h->s_rot2.release();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return PCX_OK;
     PCX_API_END
@@ -140,6 +72,17 @@ static int bary_pack(pcx_bary *h, DerivedTensor &dt) {
     return PCX_OK;
 }
 
+// a host-built table (or any host array) as a device buffer the handle owns from here on
+template <typename T>
+static int upload(T *&dst, const T *src, size_t count) {
+    HIP_TRY(hipMalloc((void **)&dst, count * sizeof(T)));
+    HIP_TRY(hipMemcpy(dst, src, count * sizeof(T), hipMemcpyHostToDevice));
+    return PCX_OK;
+}
+template <typename T>
+static int upload(T *&dst, const std::vector<T> &v) { return upload(dst, v.data(), v.size()); }
+
+// validate, plan (bary_make_plan: pcx_bary_plan.hip decides everything about the launches), upload
 extern "C" int pcx_bary_create(int device, int d, const int32_t *n_nodes, const double *nodes_cat,
                                const double *weights_cat, const double *diffmat_cat,
                                const double *tensor, pcx_bary **out) {
@@ -151,333 +94,62 @@ extern "C" int pcx_bary_create(int device, int d, const int32_t *n_nodes, const 
         return fail(PCX_ERR_INVALID, "NULL model array");
     int rc = use_device(device);
     if (rc) return rc;
-    pcx_bary *h = new (std::nothrow) pcx_bary();
+    std::unique_ptr<pcx_bary, int (*)(pcx_bary *)> h(new (std::nothrow) pcx_bary(), pcx_bary_destroy);
     if (!h) return fail(PCX_ERR_NOMEM, "out of host memory");
     h->device = device;
     h->dims.d = d;
-    h->g0_span = g_g0_span_default;
-    h->group_tol = g_group_tol_default;
     long total = 1, sum_n = 0, sum_n2 = 0;
     for (int k = 0; k < d; ++k) {
-        if (n_nodes[k] < 1 || n_nodes[k] > 4096) { delete h; return fail(PCX_ERR_INVALID, "n_nodes[%d]=%d outside [1, 4096]", k, n_nodes[k]); }
+        if (n_nodes[k] < 1 || n_nodes[k] > 4096) return fail(PCX_ERR_INVALID, "n_nodes[%d]=%d outside [1, 4096]", k, n_nodes[k]);
         h->dims.n[k] = n_nodes[k];
         h->dims.off[k] = (int)sum_n;
         h->doff.push_back((int)sum_n2);
         sum_n += n_nodes[k];
         sum_n2 += (long)n_nodes[k] * n_nodes[k];
         total *= n_nodes[k];
-        if (total > (1L << 33)) { delete h; return fail(PCX_ERR_UNSUPPORTED, "tensor larger than 2^33 elements"); }
+        if (total > (1L << 33)) return fail(PCX_ERR_UNSUPPORTED, "tensor larger than 2^33 elements");
     }
     for (int k = d; k < PCX_MAX_DIMS; ++k) { h->dims.n[k] = 1; h->dims.off[k] = 0; }
     h->dims.sum_n = (int)sum_n;
     h->total = total;
+    const BaryDims &dm = h->dims;
 
-#define CREATE_TRY(expr)                                                                   \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            int c_ = fail(PCX_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));     \
-            pcx_bary_destroy(h);                                                           \
-            return c_;                                                                     \
-        }                                                                                  \
-    } while (0)
+    // shapes no kernel covers fail here, at create, not at the first evaluation
+    const BaryEnv env = bary_read_env();
+    h->g0_span = env.g0_span;
+    h->group_tol = env.group_tol;
+    if ((rc = bary_make_plan(dm, total, nodes_cat, env, *h))) return rc;
 
-    CREATE_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    CREATE_TRY(hipMalloc((void **)&h->d_nodes, sum_n * sizeof(double)));
-    CREATE_TRY(hipMalloc((void **)&h->d_wts, sum_n * sizeof(double)));
-    CREATE_TRY(hipMalloc((void **)&h->d_diff, sum_n2 * sizeof(double)));
-    CREATE_TRY(hipMemcpy(h->d_nodes, nodes_cat, sum_n * sizeof(double), hipMemcpyHostToDevice));
-    CREATE_TRY(hipMemcpy(h->d_wts, weights_cat, sum_n * sizeof(double), hipMemcpyHostToDevice));
-    CREATE_TRY(hipMemcpy(h->d_diff, diffmat_cat, sum_n2 * sizeof(double), hipMemcpyHostToDevice));
-
-    // rows kernel geometry: lanes per point = smallest power of two >= number of rows
-    long Mrows = total / h->dims.n[d - 1];
-    int lpp = 1;
-    while (lpp < 64 && lpp < Mrows) lpp <<= 1;
-    // its LDS weight table is (256 / lpp) points x sum_n doubles: widen the groups until it fits
-    while (lpp < 64 && (size_t)(256 / lpp) * sum_n * sizeof(double) > 48 * 1024) lpp <<= 1;
-    h->lpp = lpp;
-
-    // MFMA plan + row/k codes
-    { const char *e = getenv("PCX_BARY_SEED"); h->seed = !(e && e[0] == '0'); }
-    { const char *e = getenv("PCX_BARY_TAIL"); h->tail_mode = (e && e[0] == '0') ? 0 : ((e && e[0] == '2') ? 2 : 1); }
-    h->mfma_ok = plan_mfma(h->dims, h->plan, h->seed);
+    // the grid arrays and the tables the plan asks for
+    HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    if ((rc = upload(h->d_nodes, nodes_cat, sum_n)) || (rc = upload(h->d_wts, weights_cat, sum_n)) ||
+        (rc = upload(h->d_diff, diffmat_cat, sum_n2)))
+        return rc;
+    if (h->small_nlp && (rc = upload(h->d_snodes, bary_scaled_nodes(dm, nodes_cat, false)))) return rc;
+    if ((h->grid_ok || h->kfold_ok) && (rc = upload(h->d_gsnodes, bary_scaled_nodes(dm, nodes_cat, true)))) return rc;
     if (h->mfma_ok) {
-        // two column tiles per wave while the B operands fit the register file beside them: up to 32 k-steps, 36 and 40 with
-        // narrow codes (232 ... 256 VGPRs at two waves per SIMD; round 4, one against two column tiles: 12^4 0.642 -> 0.683,
-        // 12 x 12 x 10 x 16 0.629 -> 0.682, 6 x 6 x 6 x 12 x 12 0.644 -> 0.692 -- each fragment load feeds two matrix instructions)
-        const bool narrow = h->plan.split <= PCX_CODE_FIELDS && d - h->plan.split <= PCX_CODE_FIELDS;
-        h->nt = (h->plan.KS <= 32 || (narrow && h->plan.KS <= 40)) ? 2 : 1;
-        if (mfma_lds_bytes(h->dims, h->nt) > 150 * 1024) h->nt = 1;
-        if (mfma_lds_bytes(h->dims, h->nt) > 150 * 1024) h->mfma_ok = false;
-    }
-    // shapes no kernel covers fail here, at create, not at the first evaluation: the rows kernel
-    // keeps (256 / lpp) x sum_n weights in LDS
-    if (!h->mfma_ok && (size_t)(256 / h->lpp) * sum_n * sizeof(double) > 160 * 1024) {
-        int c_ = fail(PCX_ERR_UNSUPPORTED, "sum of node counts %ld too large for any kernel (MFMA plan: each of the "
-                      "head / tail parts <= %d rows and a tail product <= 256; row kernel: sum <= 5120)", sum_n, PCX_MAX_PART_ROWS);
-        pcx_bary_destroy(h);
-        return c_;
-    }
-    h->mfma4_ok = h->mfma_ok && mfma4_lds_bytes(h->dims, h->plan.KS) <= 160 * 1024 &&
-                  h->plan.KS <= 32 && h->plan.split <= PCX_CODE_FIELDS && d - h->plan.split <= PCX_CODE_FIELDS;
-    // lane-per-point kernel (k_bary_small): d <= 4, last dimension <= 64 nodes (weights in registers),
-    // outer weights table (sum of outer n) x 64 lanes x 8 B within 64 KB.  Preferred by auto while the
-    // tensor is small enough that the MFMA kernel's prologue outweighs its tiles
-    // (tools/bary_rate_probe.py, profiles/r02_bary_rate_probe.txt).
-    {
-        // every node count up to 16 has its own instantiation (no padding, no per-node tests); classes above
-        static const int kNlp[] = {2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 24, 32, 48, 64};
-        const int nl = h->dims.n[d - 1];
-        const long outer_rows = sum_n - nl;
-        if (d <= 4 && nl <= 64 && outer_rows * 64 * (long)sizeof(double) <= 64 * 1024 && total <= (1L << 22)) {
-            for (int v : kNlp)
-                if (v >= nl) { h->small_nlp = v; break; }
-            // ... and 2-D tensors with a last dimension of 49 ... 64 nodes while the first has at most 48 (round 4,
-            // lane-per-point / MFMA in 1e9 pts/s: 20 x 64 5.8 / 2.2, 30 x 50 3.5 / 2.6, 40 x 64 2.7 / 1.9, 48 x 64 2.1 / 1.9; 50^2
-            // 2.0 / 2.1, 60^2 1.6 / 1.9, 64^2 1.6 / 1.7; 3-D shapes of that kind -- 8 x 8 x 50 -- stay on the MFMA kernel)
-            h->small_preferred = total <= kSmallTensorElems && (nl <= 48 || (d == 2 && n_nodes[0] <= 48));
-            // mid-size tensors with equal trailing node counts: both trailing weight vectors in registers (k_bary_sq)
-            if (d >= 2 && n_nodes[d - 2] == nl && ((nl >= 4 && nl <= 24) || nl == 26 || nl == 28 || nl == 30 || nl == 32) &&
-                (outer_rows - nl) * 64 * (long)sizeof(double) <= 48 * 1024) {
-                h->sq_nl = nl;
-                static const bool sq_auto = [] { const char *e = getenv("PCX_BARY_SQ"); return !(e && e[0] == '0'); }();
-                // tools/bary_rate_probe.py (profiles/r03_bary_rate_probe.txt): ahead of k_bary_small everywhere it applies
-                // (12^2 +33 %, 8^3 +37 %, 11^3 +44 %, 6^4 +50 %) and of the MFMA kernel's short plans for d <= 3
-                // (17^3 +48 %, 20^3 +11 %, 24^3 +15 %); from 10^4 up the MFMA kernel (K = n^2 >= 100) is ahead
-                // 21 and 23 nodes: hipcc runs out of scalar registers on the odd row length (SGPR spills in the block,
-                // 0.37 / 0.36 of the peak against 0.39 / 0.44 on the MFMA kernel): available, not preferred
-                // 26 / 28 / 30 nodes: ahead in 2-D (26^2 0.40 against 0.21), behind the MFMA kernel in 3-D (30^3 0.32 against 0.42)
-                // round 4 (k_bary_mfma_grid): 20^3 0.45 -> 0.48, 24^3 0.545 -> 0.56, 32^3 0.48 -> 0.63 on the MFMA kernel
-                // (21 nodes: 0.44 here against 0.40 on the grid MFMA kernel -- preferred again; 23: 0.465 against 0.47)
-                h->sq_preferred = sq_auto && (d <= 3 || total <= kSmallTensorElems) && nl != 23 &&
-                                  !(d >= 3 && nl >= 24) && !(d == 3 && nl == 20 && n_nodes[0] == 20);      // 24^3: grid 0.56, here 0.545
-            }
-            // 2^e ~ 2 / (node span): exact to apply, keeps the prefix / suffix products of the weights in range
-            std::vector<double> sn((size_t)sum_n);
-            for (int k = 0; k < d; ++k) {
-                const double *nd = nodes_cat + h->dims.off[k];
-                const double span = nd[n_nodes[k] - 1] - nd[0];
-                int e = 0;
-                if (span > 0.0 && std::isfinite(span)) (void)std::frexp(2.0 / span, &e);
-                const double sck = std::ldexp(1.0, e - 1);
-                h->small_scale.s[k] = sck;
-                for (int j = 0; j < n_nodes[k]; ++j) sn[h->dims.off[k] + j] = nd[j] * sck;
-            }
-            CREATE_TRY(hipMalloc((void **)&h->d_snodes, sum_n * sizeof(double)));
-            CREATE_TRY(hipMemcpy(h->d_snodes, sn.data(), sum_n * sizeof(double), hipMemcpyHostToDevice));
-        }
-    }
-    if (h->mfma_ok) {
-        const BaryMfmaPlan &p = h->plan;
-        // all-ones rows: the last row of the head part (row codes) and of the tail part (k codes, below)
-        const unsigned ones_h = (unsigned)(p.tail_base - 1);
-        std::vector<unsigned> rowcode((size_t)p.MT * 16), rowcode_hi((size_t)p.MT * 16);
-        h->wide = p.split > PCX_CODE_FIELDS || d - p.split > PCX_CODE_FIELDS;
-        for (long m = 0; m < (long)p.MT * 16; ++m) {
-            unsigned f[2 * PCX_CODE_FIELDS] = {ones_h, ones_h, ones_h, ones_h, ones_h, ones_h, ones_h, ones_h};
-            if (m < p.M) {
-                long rem = m;
-                for (int k = p.split - 1; k >= 0; --k) {
-                    int i = (int)(rem % h->dims.n[k]);
-                    rem /= h->dims.n[k];
-                    f[k] = (unsigned)(h->dims.off[k] + i);
-                }
-            }
-            rowcode[m] = f[0] | (f[1] << 8) | (f[2] << 16) | (f[3] << 24);
-            rowcode_hi[m] = f[4] | (f[5] << 8) | (f[6] << 16) | (f[7] << 24);
-        }
-        // device layout of the row codes: the four codes a lane needs for a tile (rows g, g+4, g+8, g+12 of
-        // tile t) side by side, [t][g][j], so that one 16-byte load fetches them
-        auto lane_order = [&](std::vector<unsigned> &v) {
-            std::vector<unsigned> o(v.size());
-            for (long t = 0; t < (long)p.MT; ++t)
-                for (int g = 0; g < 4; ++g)
-                    for (int j = 0; j < 4; ++j) o[(size_t)(4 * t + g) * 4 + j] = v[(size_t)16 * t + g + 4 * j];
-            v.swap(o);
-        };
-        lane_order(rowcode);
-        lane_order(rowcode_hi);
-        if (h->wide) {
-            CREATE_TRY(hipMalloc((void **)&h->d_rowcode_hi, rowcode_hi.size() * sizeof(unsigned)));
-            CREATE_TRY(hipMemcpy(h->d_rowcode_hi, rowcode_hi.data(), rowcode_hi.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-        }
-        CREATE_TRY(hipMalloc((void **)&h->d_rowcode, rowcode.size() * sizeof(unsigned)));
-        CREATE_TRY(hipMemcpy(h->d_rowcode, rowcode.data(), rowcode.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-        // the pipelined loop of the narrow instantiations (k_bary_mfma, KS >= 12) reads row OFFSETS: every field as
-        // the LDS byte offset row * PW * 8 of its table row, 16 bits each (rows <= 255, PW <= 32), two 16-byte words
-        // per (tile, lane group): [t][g][fields 0 | 1 << 16, fields 2 | 3 << 16][j].  One table per PW = 16 NT.
-        if (!h->wide && p.KS >= 12) {
-            std::vector<unsigned> offs((size_t)p.MT * 32);
-            for (int nt = 1; nt <= 2; ++nt) {
-                const unsigned sc = 16u * nt * sizeof(double);
-                for (size_t q = 0; q < (size_t)p.MT * 4; ++q)              // q = 4 t + g
-                    for (int j = 0; j < 4; ++j) {
-                        const unsigned code = rowcode[4 * q + j];
-                        offs[8 * q + j] = ((code & 255u) * sc) | ((((code >> 8) & 255u) * sc) << 16);
-                        offs[8 * q + 4 + j] = (((code >> 16) & 255u) * sc) | (((code >> 24) * sc) << 16);
-                    }
-                CREATE_TRY(hipMalloc((void **)&h->d_rowoff[nt - 1], offs.size() * sizeof(unsigned)));
-                CREATE_TRY(hipMemcpy(h->d_rowoff[nt - 1], offs.data(), offs.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-            }
-        }
-        // dim-0 groups: head = dimension 0 x (dimensions 1 .. split-1); the rows of one i0 form a slab padded to whole
-        // tiles.  Needs two column tiles per wave (large batches only), narrow codes, and room for two n0-vectors
-        // per point in the tail part of the LDS table (dead once the B operands are in registers); n0 <= 16 bounds the
-        // rounding amplification of the D_0 step (~ n0^2 eps).
-        long M1 = 1;
-        for (int k = 1; k < p.split; ++k) M1 *= h->dims.n[k];
-        if (!h->wide && p.split >= 2 && p.split <= PCX_CODE_FIELDS && h->nt == 2 && p.KS <= 32 && M1 >= 16 &&
-            2 * h->dims.n[0] <= p.rows - p.tail_base && h->dims.n[0] >= 2 && h->dims.n[0] <= 16) {
-            const int tps = (int)((M1 + 15) / 16);
-            const long mtg = (long)tps * h->dims.n[0];
-            // padding must stay cheap: at most 15 % more row tiles than the plain plan
-            if (mtg * 100 <= (long)p.MT * 115) {
-                std::vector<unsigned> rc((size_t)mtg * 16);
-                for (long t = 0; t < mtg; ++t)
-                    for (int r = 0; r < 16; ++r) {
-                        const long m1 = (t % tps) * 16 + r;
-                        unsigned f[PCX_CODE_FIELDS] = {ones_h, ones_h, ones_h, ones_h};
-                        if (m1 < M1) {
-                            long rem = m1;
-                            for (int k = p.split - 1; k >= 1; --k) {
-                                int i = (int)(rem % h->dims.n[k]);
-                                rem /= h->dims.n[k];
-                                f[k - 1] = (unsigned)(h->dims.off[k] + i);
-                            }
-                        }
-                        rc[(size_t)16 * t + r] = f[0] | (f[1] << 8) | (f[2] << 16) | (f[3] << 24);
-                    }
-                std::vector<unsigned> o(rc.size());
-                for (long t = 0; t < mtg; ++t)
-                    for (int g = 0; g < 4; ++g)
-                        for (int j = 0; j < 4; ++j) o[(size_t)(4 * t + g) * 4 + j] = rc[(size_t)16 * t + g + 4 * j];
-                CREATE_TRY(hipMalloc((void **)&h->d_rowcode_g0, o.size() * sizeof(unsigned)));
-                CREATE_TRY(hipMemcpy(h->d_rowcode_g0, o.data(), o.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-                h->g0_ok = true;
-                h->g0_tps = tps;
-                h->g0_nf = std::max(2, p.split - 1);
-            }
-        }
-    }
-
-    // short plans: the grid form (bary_grid_kernels.h) -- unless the shape can share GEMMs between specs one order apart
-    // (dim-0 groups above), which needs the slab packing of the row-code form
-    // Their planners and packers know no seed: they are priced, and where one of them is taken run, on the plan with
-    // every column in the k-loop
-    BaryMfmaPlan uplan = h->plan;
-    uplan.R = 0;
-    if (h->mfma_ok) uplan.KS = pick_ks(uplan.K);
-    if (h->mfma_ok && !(h->plan.split > PCX_CODE_FIELDS || d - h->plan.split > PCX_CODE_FIELDS)) {
-        // 3-D tensors one of whose dimensions fills whole row tiles: the k-fold form (bary_kfold_kernels.h) ahead of the grid
-        // form -- and of the dim-0 groups: 9 x 48 x 30 runs at 0.30 of the peak on the row-code form a group would share, the
-        // k-fold form (rows = the 48) takes every launch of it to 0.8
-        long kfold_est = 0;                               // permille of the FP64 peak expected of the k-fold plan
-        {
-            const long keff = bary_plan_kfold(h->dims, h->kf);
-            kfold_est = bary_kfold_estimate(h->kf, keff);
-            long geff = 0;
-            BaryGridPlan gtry;
-            gtry.MT = 0;
-            if (keff > 0 && !h->g0_ok) {
-                // the alternative is the grid form -- or the row-code form where the grid planner declines, which it does when it
-                // expects no more of its own form: priced as a grid plan either way (25 x 25 x 40: row codes 0.44, k-fold 0.6)
-                (void)bary_plan_grid(h->dims, uplan, gtry);
-                if (gtry.MT > 0)
-                    geff = (long)((double)uplan.M * uplan.K * 10000.0 / ((double)gtry.MT * 16.0 * uplan.KS * 4.0));
-            }
-            h->kfold_ok = bary_kfold_take(h->kf, keff, geff, uplan.KS);
-        }
-        if (h->kfold_ok) {
-            const int nt_rc = h->nt;
-            h->nt = 2;
-            if (bary_kfold_lds_bytes(h->kf, 2) > (size_t)72 * 1024) h->nt = 1;      // two workgroups per CU
-            if (bary_kfold_lds_bytes(h->kf, h->nt) > (size_t)150 * 1024) { h->kfold_ok = false; h->nt = nt_rc; }   // a very long middle dimension
-        }
-        // where the k-fold form is taken it is also ahead of the lane-per-point kernels (round 4, k-fold / k_bary_sq in fractions of
-        // the FP64 peak: 45 x 20 x 20 0.68 / 0.31, 30 x 20 x 20 0.65 / 0.42, 32 x 16 x 16 0.65 / 0.41, 64 x 8 x 8 0.45 / 0.21, 24 x 20 x 20
-        // 0.53 / 0.46, 22^3 0.49 / 0.46; without it -- 40 x 12 x 12, 26 x 14 x 14, 21^3 -- they keep their rule)
-        // -- for tensors of 4,096 elements or more and plans expected at half the peak or better: (2, 17, 17) stays where it was
-        if (h->kfold_ok && total >= kSmallTensorElems && kfold_est >= 500) h->sq_preferred = h->small_preferred = false;
-        if (h->kfold_ok && h->g0_ok) {
-            h->g0_ok = false;
-            (void)hipFree(h->d_rowcode_g0);
-            h->d_rowcode_g0 = nullptr;
-        }
-        if (!h->kfold_ok && !h->g0_ok) h->grid_ok = bary_plan_grid(h->dims, uplan, h->gp);
-        if (h->grid_ok) {
-            h->nt = uplan.KS > 32 ? 1 : 2;                       // the table is per wave and holds one part at a time
-            const size_t cap = (size_t)(h->gp.wpb == 4 ? 150 : 64) * 1024;
-            if (bary_grid_lds_bytes(h, h->nt) > cap) h->nt = 1;
-            if (bary_grid_lds_bytes(h, h->nt) > cap) h->grid_ok = false;
-        }
-    }
-    if (h->grid_ok || h->kfold_ok) {
-        // division-free weights for the grid and k-fold forms (bary_weights.h; as k_bary_small): nodes scaled by 2^e ~ 2 / span
-        // per dimension; PCX_BARY_GRID_PROD=0 (read per handle) keeps the weights by division (A/B measurements)
-        std::vector<double> sn((size_t)sum_n + PCX_MAX_DIMS, 0.0);
-        h->grid_prod = true;
-        for (int k = 0; k < d; ++k) {
-            const double *nd = nodes_cat + h->dims.off[k];
-            const double span = nd[n_nodes[k] - 1] - nd[0];
-            int e = 0;
-            if (span > 0.0 && std::isfinite(span)) (void)std::frexp(2.0 / span, &e);
-            const double sck = std::ldexp(1.0, e - 1);
-            sn[(size_t)sum_n + k] = sck;
-            for (int j = 0; j < n_nodes[k]; ++j) sn[h->dims.off[k] + j] = nd[j] * sck;
-            if (n_nodes[k] > 64) h->grid_prod = false;
-        }
-        { const char *e = getenv("PCX_BARY_GRID_PROD"); if (e && e[0] == '0') h->grid_prod = false; }
-        CREATE_TRY(hipMalloc((void **)&h->d_gsnodes, sn.size() * sizeof(double)));
-        CREATE_TRY(hipMemcpy(h->d_gsnodes, sn.data(), sn.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (h->grid_ok || h->kfold_ok) h->mfma4_ok = false;
-    if (h->grid_ok || h->kfold_ok) h->plan = uplan;
-    if (h->mfma_ok) {
-        // k codes: entry kk names column R + kk (the fragment image starts behind the seed columns); the R seed
-        // columns 0 .. R-1 follow at 4 KS + r
-        const BaryMfmaPlan &p = h->plan;
-        const unsigned ones_t = (unsigned)(p.rows - 1 - p.tail_base);
-        std::vector<unsigned> kcode((size_t)p.KS * 4 + p.R), kcode_hi((size_t)p.KS * 4 + p.R);
-        for (long kk = 0; kk < (long)kcode.size(); ++kk) {
-            unsigned f[2 * PCX_CODE_FIELDS] = {ones_t, ones_t, ones_t, ones_t, ones_t, ones_t, ones_t, ones_t};
-            const long col = kk < (long)p.KS * 4 ? p.R + kk : kk - (long)p.KS * 4;
-            if (col < p.K) {
-                long rem = col;
-                for (int k = d - 1; k >= p.split; --k) {
-                    int i = (int)(rem % h->dims.n[k]);
-                    rem /= h->dims.n[k];
-                    f[k - p.split] = (unsigned)(h->dims.off[k] - h->dims.off[p.split] + i);   // relative to the tail part
-                }
-            }
-            kcode[kk] = f[0] | (f[1] << 8) | (f[2] << 16) | (f[3] << 24);
-            kcode_hi[kk] = f[4] | (f[5] << 8) | (f[6] << 16) | (f[7] << 24);
-        }
-        if (h->wide) {
-            CREATE_TRY(hipMalloc((void **)&h->d_kcode_hi, kcode_hi.size() * sizeof(unsigned)));
-            CREATE_TRY(hipMemcpy(h->d_kcode_hi, kcode_hi.data(), kcode_hi.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-        }
-        CREATE_TRY(hipMalloc((void **)&h->d_kcode, kcode.size() * sizeof(unsigned)));
-        CREATE_TRY(hipMemcpy(h->d_kcode, kcode.data(), kcode.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+        const std::vector<unsigned> rowcode = bary_row_codes(dm, h->plan, 0);
+        if ((rc = upload(h->d_rowcode, rowcode)) || (rc = upload(h->d_kcode, bary_k_codes(dm, h->plan, 0)))) return rc;
+        if (h->wide && ((rc = upload(h->d_rowcode_hi, bary_row_codes(dm, h->plan, 1))) ||
+                        (rc = upload(h->d_kcode_hi, bary_k_codes(dm, h->plan, 1)))))
+            return rc;
+        for (int nt = 1; nt <= 2 && bary_plan_row_offsets(*h); ++nt)
+            if ((rc = upload(h->d_rowoff[nt - 1], bary_row_offsets(rowcode, nt)))) return rc;
+        if (h->g0_ok && (rc = upload(h->d_rowcode_g0, bary_slab_row_codes(dm, *h)))) return rc;
     }
 
     // value tensor (derivative spec all-zero) enters the cache at create
-    DerivedTensor dt;
+    DerivedTensor &dt = h->cache[std::vector<int>(d, 0)];
     {
         DevBuf plain;
-        rc = alloc_plain(plain, total);
-        if (rc) { pcx_bary_destroy(h); return rc; }
+        if ((rc = alloc_plain(plain, total))) return rc;
         dt.plain = plain.release<double>();
     }
-    { hipError_t e_ = hipMemcpy(dt.plain, tensor, total * sizeof(double), hipMemcpyHostToDevice);
-      if (e_ != hipSuccess) { (void)hipFree(dt.plain); int c_ = fail(PCX_ERR_HIP, "tensor upload: %s", hipGetErrorString(e_)); pcx_bary_destroy(h); return c_; } }
-    rc = bary_pack(h, dt);
-    if (rc) { (void)hipFree(dt.plain); pcx_bary_destroy(h); return rc; }
-    h->cache[std::vector<int>(d, 0)] = dt;
-    CREATE_TRY(hipMalloc((void **)&h->d_tab, kMaxSpecs * sizeof(double *)));
-    CREATE_TRY(hipStreamSynchronize(h->stream));
-#undef CREATE_TRY
-    *out = h;
+    HIP_TRY(hipMemcpy(dt.plain, tensor, total * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = bary_pack(h.get(), dt))) return rc;
+    HIP_TRY(hipMalloc((void **)&h->d_tab, kMaxSpecs * sizeof(double *)));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    *out = h.release();
     return PCX_OK;
     PCX_API_END
 }
@@ -785,12 +457,8 @@ static int bary_pack_g0(pcx_bary *h, DerivedTensor &dt) {
 
 static const long kG0MinPoints = 65536;      // below: per-spec launches (they split over row tiles and need no second pass)
 
-// the kernel a launch will take: 1 rows, 2 MFMA 16x16x4, 3 MFMA 4x4x4, 4 lane-per-point
-PCX_HIDDEN int bary_effective_variant(const pcx_bary *h) {
-    if (h->variant != 0) return h->variant;
-    if (h->sq_nl && h->sq_preferred) return 5;
-    return (h->small_nlp && (h->small_preferred || !h->mfma_ok)) ? 4 : (h->mfma_ok ? 2 : 1);
-}
+// the kernel a launch will take: 1 rows, 2 MFMA 16x16x4, 3 MFMA 4x4x4, 4 lane-per-point, 5 k_bary_sq
+PCX_HIDDEN int bary_effective_variant(const pcx_bary *h) { return h->variant != 0 ? h->variant : bary_auto_variant(*h); }
 
 // frag_tab is a device table holding the m tensor pointers of a multi-spec launch: fragment images for
 // the MFMA kernels, plain tensors for the lane-per-point kernel (see bary_spec_table); for m = 1 the MFMA
@@ -836,38 +504,51 @@ PCX_HIDDEN int bary_launch(pcx_bary *h, DerivedTensor *const *dts, int m, const 
 }
 
 // The model with dimension q moved to the front (the other dimensions keep their order), or NULL when that shape has
-// no slab plan.  Built on first use from the device copies of the grid arrays and the value tensor: a transposed copy of a
-// tensor of at most 2^24 elements, once per handle and dimension.  Caller holds h->mu.
+// no slab plan -- which the planner says from the node counts and nodes, before anything else is downloaded.  Built on
+// first use from the device copies of the grid arrays and the value tensor: a transposed copy of a tensor of at most
+// 2^24 elements, once per handle and dimension.  Caller holds h->mu.
 static const long kRotMaxElems = 1L << 24;
 static pcx_bary *bary_rot(pcx_bary *h, int q) {
     if (h->rot_state[q]) return h->rot[q];
     h->rot_state[q] = 2;
     const int d = h->dims.d;
     if (q < 1 || q >= d || h->total > kRotMaxElems || h->dims.n[q] < 2 || h->dims.n[q] > 16) return nullptr;
+    int pd[PCX_MAX_DIMS];                       // pd[c] = original dimension at position c of the sub-model
+    pd[0] = q;
+    for (int k = 0, c = 1; k < d; ++k)
+        if (k != q) pd[c++] = k;
+    // ask the planner first: the rotated node counts and nodes decide whether that shape has a slab plan
     const long sum_n = h->dims.sum_n;
+    std::vector<double> nodes((size_t)sum_n), rn;
+    if (hipMemcpy(nodes.data(), h->d_nodes, sum_n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    std::vector<int32_t> nn(d);
+    BaryDims rdm = h->dims;
+    for (int c = 0, off = 0; c < d; off += nn[c], ++c) {
+        const int k = pd[c];
+        nn[c] = rdm.n[c] = h->dims.n[k];
+        rdm.off[c] = off;
+        rn.insert(rn.end(), nodes.begin() + h->dims.off[k], nodes.begin() + h->dims.off[k] + nn[c]);
+    }
+    BaryLaunchPlan rplan;
+    if (bary_make_plan(rdm, h->total, rn.data(), bary_read_env(), rplan) != PCX_OK || !rplan.g0_ok) return nullptr;
     long sum_n2 = 0;
     for (int k = 0; k < d; ++k) sum_n2 += (long)h->dims.n[k] * h->dims.n[k];
-    std::vector<double> nodes((size_t)sum_n), wts((size_t)sum_n), diff((size_t)sum_n2), T((size_t)h->total), TR((size_t)h->total);
+    std::vector<double> wts((size_t)sum_n), diff((size_t)sum_n2), T((size_t)h->total), TR((size_t)h->total);
     const DerivedTensor &val = h->cache[std::vector<int>(d, 0)];
-    if (hipMemcpy(nodes.data(), h->d_nodes, sum_n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(wts.data(), h->d_wts, sum_n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+    if (hipMemcpy(wts.data(), h->d_wts, sum_n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(diff.data(), h->d_diff, sum_n2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(T.data(), val.plain, h->total * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
         (void)hipGetLastError();
         return nullptr;
     }
-    int pd[PCX_MAX_DIMS];                       // pd[c] = original dimension at position c of the sub-model
-    pd[0] = q;
-    for (int k = 0, c = 1; k < d; ++k)
-        if (k != q) pd[c++] = k;
-    std::vector<int32_t> nn(d);
-    std::vector<double> rn, rw, rd;
+    std::vector<double> rw, rd;
     long stride[PCX_MAX_DIMS];                  // element strides of the original C-order tensor
     { long acc = 1; for (int k = d - 1; k >= 0; --k) { stride[k] = acc; acc *= h->dims.n[k]; } }
     for (int c = 0; c < d; ++c) {
         const int k = pd[c], n = h->dims.n[k];
-        nn[c] = n;
-        rn.insert(rn.end(), nodes.begin() + h->dims.off[k], nodes.begin() + h->dims.off[k] + n);
         rw.insert(rw.end(), wts.begin() + h->dims.off[k], wts.begin() + h->dims.off[k] + n);
         rd.insert(rd.end(), diff.begin() + h->doff[k], diff.begin() + h->doff[k] + (long)n * n);
     }
@@ -886,7 +567,6 @@ static pcx_bary *bary_rot(pcx_bary *h, int q) {
     }
     pcx_bary *r = nullptr;
     if (pcx_bary_create(h->device, d, nn.data(), rn.data(), rw.data(), rd.data(), TR.data(), &r) != PCX_OK || !r) return nullptr;
-    if (!r->g0_ok) { pcx_bary_destroy(r); return nullptr; }
     h->rot[q] = r;
     h->rot_state[q] = 1;
     return r;
@@ -1573,10 +1253,9 @@ extern "C" int pcx_bary_set_kernel(pcx_bary *h, int variant) {
     PCX_API_BEGIN
     if (!h) return fail(PCX_ERR_INVALID, "handle is NULL");
     if (variant < 0 || variant > 5) return fail(PCX_ERR_INVALID, "variant %d outside [0, 5]", variant);
-    if (variant == 4 && !h->small_nlp) return fail(PCX_ERR_UNSUPPORTED, "lane-per-point kernel does not cover this shape");
-    if (variant == 5 && !h->sq_nl) return fail(PCX_ERR_UNSUPPORTED, "square-trailing lane-per-point kernel does not cover this shape");
-    if (variant == 2 && !h->mfma_ok) return fail(PCX_ERR_UNSUPPORTED, "MFMA kernel does not cover this shape");
-    if (variant == 3 && !h->mfma4_ok) return fail(PCX_ERR_UNSUPPORTED, "4x4x4 MFMA kernel does not cover this shape");
+    static const char *const kName[] = {"MFMA", "4x4x4 MFMA", "lane-per-point", "square-trailing lane-per-point"};
+    if (variant >= 2 && !bary_plan_has_variant(*h, variant))
+        return fail(PCX_ERR_UNSUPPORTED, "%s kernel does not cover this shape", kName[variant - 2]);
     std::lock_guard<std::mutex> lk(h->mu);
     h->variant = variant;
     return PCX_OK;
@@ -1606,14 +1285,7 @@ extern "C" int pcx_bary_set_group_tolerance(pcx_bary *h, double tol) {
 extern "C" int pcx_bary_kernel_info(pcx_bary *h, int32_t *info) {
     PCX_API_BEGIN
     if (!h || !info) return fail(PCX_ERR_INVALID, "NULL argument");
-    { const int keep = h->variant; h->variant = 0; info[0] = bary_effective_variant(h); h->variant = keep; }
-    info[1] = h->mfma_ok ? (h->kfold_ok ? h->kf.MT : (h->grid_ok ? h->gp.MT : h->plan.MT)) : 0;
-    info[2] = h->mfma_ok ? (h->kfold_ok ? h->kf.nbody * h->kf.P : h->plan.KS) : 0;
-    info[3] = h->mfma_ok ? (int32_t)(h->kfold_ok ? bary_kfold_lds_bytes(h->kf, h->nt)
-                                                  : (h->grid_ok ? bary_grid_lds_bytes(h, h->nt) : mfma_lds_bytes(h->dims, h->nt)))
-                         : (256 / h->lpp) * h->dims.sum_n * 8;
-    info[4] = h->mfma_ok ? 64 * h->nt : 256 / h->lpp;
-    info[5] = h->mfma_ok ? h->plan.split : h->dims.d - 1;
+    bary_plan_kernel_info(*h, h->dims, info);
     return PCX_OK;
     PCX_API_END
 }
@@ -1625,9 +1297,9 @@ extern "C" int pcx_bary_kernel_info(pcx_bary *h, int32_t *info) {
 extern "C" int pcx_bary_tail_info(pcx_bary *h, int32_t *info) {
     PCX_API_BEGIN
     if (!h || !info) return fail(PCX_ERR_INVALID, "NULL argument");
-    for (int i = 0; i < 6; ++i) info[i] = 0;
+    bary_plan_tail_info(*h, info);
     std::lock_guard<std::mutex> lk(h->mu);
-    if (!h->mfma_ok || h->kfold_ok || h->grid_ok) return PCX_OK;
+    if (!bary_plan_rowcode_form(*h)) return PCX_OK;
     if (!h->slots[h->nt - 1]) {
         int rc = use_device(h->device);
         if (rc) return rc;
@@ -1641,9 +1313,6 @@ extern "C" int pcx_bary_tail_info(pcx_bary *h, int32_t *info) {
         if (rc) return rc;
     }
     info[0] = h->slots[h->nt - 1];
-    info[1] = 64 * h->nt;
-    info[2] = (h->plan.MT + PCX_CHUNK_TILES - 1) / PCX_CHUNK_TILES;
-    info[3] = h->tail_mode;
     info[4] = h->last_tail_P;
     info[5] = h->last_tail_blocks;
     return PCX_OK;
@@ -1653,10 +1322,7 @@ extern "C" int pcx_bary_tail_info(pcx_bary *h, int32_t *info) {
 extern "C" int pcx_bary_grid_info(pcx_bary *h, int32_t *info) {
     PCX_API_BEGIN
     if (!h || !info) return fail(PCX_ERR_INVALID, "NULL argument");
-    info[0] = h->grid_ok ? 1 : (h->kfold_ok ? 2 : 0);
-    info[1] = h->grid_ok ? h->gp.RA : 0;
-    info[2] = h->grid_ok ? h->gp.MT : (h->kfold_ok ? h->kf.MT : 0);
-    info[3] = h->grid_ok ? h->gp.nchunks : (h->kfold_ok ? h->kf.KS2 : 0);
+    bary_plan_grid_info(*h, info);
     return PCX_OK;
     PCX_API_END
 }

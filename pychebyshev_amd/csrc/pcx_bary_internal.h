@@ -3,6 +3,7 @@
 #pragma once
 
 #include "pcx_internal.h"
+#include "bary_plan.h"
 
 // "Plain" (C-order) tensors carry PCX_PLAIN_PAD zeroed doubles behind their end: k_bary_small reads a
 // row with a fixed-width run of scalar loads that may reach past the last row.
@@ -31,7 +32,10 @@ struct DerivedTensor {
     }
 };
 
-struct pcx_bary {
+// The launch plan (BaryLaunchPlan, bary_plan.h: made by bary_make_plan at create and constant afterwards) and what the
+// device holds for it.  The destructor releases everything the handle owns, the sub-models of `rot` included.
+struct pcx_bary : BaryLaunchPlan {
+    ~pcx_bary();
     int device = 0;
     hipStream_t stream = nullptr;
     BaryDims dims;
@@ -42,34 +46,17 @@ struct pcx_bary {
     double *d_cheb = nullptr;        // values -> Chebyshev coefficients matrix per dimension, at doff[k] (pcx_bary_sobol; lazy)
     Scratch s_cheb[2];               // the coefficient passes ping-pong between these (prod n doubles each, kept after first use)
     Scratch s_sobol;                 // k_sobol_energy's slab + k_sobol_finish's result
-    // launch plan
-    bool mfma_ok = false;
-    bool seed = true;                // K-remainder columns seed the accumulators (PCX_BARY_SEED=0 at create: never)
-    BaryMfmaPlan plan;
-    int nt = 2;                      // point tiles per wave in the MFMA kernel
+    // the plan's tables (bary_plan.h has their builders)
     unsigned *d_rowcode = nullptr, *d_kcode = nullptr;
     unsigned *d_rowcode_hi = nullptr, *d_kcode_hi = nullptr;   // fields 4..7 (wide plans only)
-    bool wide = false;      // more than four head or tail dimensions
     // pipelined narrow plans (KS >= 12): the row codes as pre-scaled LDS byte offsets, one table per PW = 16, 32 (bary_kernels.h)
     unsigned *d_rowoff[2] = {nullptr, nullptr};
-    int tail_mode = 1;               // tail split of large launches (launch_mfma_t): 1 where the row-tile walk is long enough to pay
-                                     // for the second kernel; PCX_BARY_TAIL=0 at create: never, =2: wherever the geometry allows
+    unsigned *d_rowcode_g0 = nullptr;   // dim-0 groups: the slabs' row codes
+    double *d_gsnodes = nullptr;     // grid and k-fold forms: nodes times a power of two per dimension, then the PCX_MAX_DIMS scales themselves
+    double *d_snodes = nullptr;      // lane-per-point kernels: the nodes times small_scale
     int slots[2] = {0, 0};           // resident workgroups of the row-code kernel per NT = 1, 2; queried at the first launch
     int last_tail_P = 0, last_tail_blocks = 0;   // geometry of the latest launch_mfma_t (pcx_bary_tail_info: the tests' witness)
     bool slots_query = false;        // the launch tables only fill `slots` (pcx_bary_tail_info)
-    // short plans: row tiles = RA x RB blocks of the last two head dimensions, no row codes (bary_grid_kernels.h);
-    // the fragment image of every derivative tensor is then packed in that order
-    bool grid_ok = false;
-    BaryGridPlan gp;
-    double *d_gsnodes = nullptr;     // nodes times a power of two per dimension, then the PCX_MAX_DIMS scales themselves
-    bool kfold_ok = false;           // 3-D, whole row tiles along dimension 0: k_bary_mfma_kfold (bary_kfold_kernels.h)
-    BaryKfoldPlan kf;
-    bool grid_prod = false;          // every dimension <= 64 nodes: division-free weights (grid_weights_prod)
-    // dim-0 groups (BaryG0): specs differing only in their dim-0 order share one slab-packed GEMM
-    bool g0_ok = false;
-    int g0_tps = 0;                  // row tiles per dim-0 slab
-    int g0_nf = 2;                   // live row-code fields (head dimensions 1 .. split-1, at least two)
-    unsigned *d_rowcode_g0 = nullptr;
     int g0_span = 1;                 // dim-0 orders above its base tensor's a slab GEMM serves (pcx_bary_set_group_span)
     // dim-q groups (q > 0): the same model with dimension q moved to the front, built on first use (bary_rot); a pair of
     // specs one order apart along q shares ITS dim-0 slab GEMM, on the batch with its columns in that order
@@ -80,15 +67,7 @@ struct pcx_bary {
     // a pair is formed when that is at most group_tol
     std::map<std::vector<int>, double> pair_dev;
     double group_tol = 3e-13;
-    int lpp = 64;                    // lanes per point in the rows kernel
-    bool mfma4_ok = false;           // 4x4x4_4b form available (LDS budget)
-    int small_nlp = 0;               // lane-per-point kernel for small tensors: padded last-dim width, 0 = not available
     std::vector<double> dom_lo, dom_hi;   // the domain, when the handle came from a .pcb file (pcx_bary_save_pcb)
-    BarySmallScale small_scale;      // its power-of-two coordinate scales and the nodes times them
-    double *d_snodes = nullptr;
-    bool small_preferred = false;    // auto picks it (few row tiles: the MFMA kernel would be all prologue)
-    int sq_nl = 0;                   // k_bary_sq (last two dimensions of sq_nl nodes each, d <= 4): 0 = not available
-    bool sq_preferred = false;       // auto picks it
     int variant = 0;                 // 0 auto, 1 rows, 2 mfma 16x16x4, 3 mfma 4x4x4_4b, 4 lane-per-point (small tensors)
     std::mutex mu;
     std::map<std::vector<int>, DerivedTensor> cache;
@@ -119,15 +98,8 @@ static int eval_spec_groups(int64_t N, const int32_t *derivs, int d, int m, doub
     return PCX_OK;
 }
 
-// pcx_bary_grid.hip
-PCX_HIDDEN bool bary_plan_grid(const BaryDims &dm, const BaryMfmaPlan &plan, BaryGridPlan &gp);
+// pcx_bary_grid.hip, pcx_bary_kfold.hip
 PCX_HIDDEN int bary_pack_grid(pcx_bary *h, const double *plain, double *frag);
-PCX_HIDDEN size_t bary_grid_lds_bytes(const pcx_bary *h, int nt);
-PCX_HIDDEN long bary_plan_kfold(const BaryDims &dm, BaryKfoldPlan &kp);
-PCX_HIDDEN long bary_kfold_estimate(const BaryKfoldPlan &kp, long eff);
-PCX_HIDDEN bool bary_kfold_take(const BaryKfoldPlan &kp, long eff, long grid_eff, int grid_ks);
-PCX_HIDDEN size_t bary_kfold_frag_count(const BaryKfoldPlan &kp);
-PCX_HIDDEN size_t bary_kfold_lds_bytes(const BaryKfoldPlan &kp, int nt);
 PCX_HIDDEN int bary_pack_kfold(pcx_bary *h, const double *plain, double *frag);
 PCX_HIDDEN int bary_launch_kfold(pcx_bary *h, const double *const *frag_tab, int m, const double *d_pts, long N, double *d_out,
                                  long ostride, long ooff, hipStream_t st, const int *perm);
