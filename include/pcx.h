@@ -330,6 +330,17 @@ int pcx_tt_stream(pcx_tt *h, void **stream);
 int pcx_tt_box_batch(pcx_tt *h, const int32_t *integrated, const double *rows, int64_t N, double *out);
 int pcx_tt_box_batch_dev(pcx_tt *h, const int32_t *integrated, const double *d_rows, int64_t N, double *d_out,
                          void *stream);
+/* Analytic derivatives, batched: out[p * m + s] = the partial derivative of the interpolant with the orders of spec s at
+ * point p.  Arguments as pcx_tt_eval_multi_batch[_dev]: derivs = m x d orders (0, 1 or 2; anything else is
+ * PCX_ERR_INVALID, "... not supported ...") in the USER's dimension order, out is N x m.  One chain per (point, spec)
+ * with T_j, T'_j or T''_j (times (2 / (b - a))^order) as the basis of a dimension: no stencil, no truncation error, any
+ * number of differentiated dimensions; an order that reaches a dimension's node count gives exactly 0.  N = 0 or m = 0
+ * returns PCX_OK without a launch (after the argument checks).  More than 64 specs are split over launches.  Models with
+ * a lane-per-point image (ranks <= 16, n <= 16) run one point per lane, every other model one point per wave on the
+ * plain cores. */
+int pcx_tt_deriv_batch(pcx_tt *h, const double *pts, int64_t N, const int32_t *derivs, int m, double *out);
+int pcx_tt_deriv_batch_dev(pcx_tt *h, const double *d_pts, int64_t N, const int32_t *derivs, int m, double *d_out,
+                           void *stream);
 /* Kernel selection: 0 = auto, 1 = direct form on v_mfma_f64_16x16x4 (one GEMM over (node, left
  * rank) per dimension; ranks <= 64), 2 = small-rank "W first" form (ranks <= 12, cores in LDS),
  * 3 = small-rank direct form on v_mfma_f64_4x4x4_4b (ranks <= 12, n <= 16, cores in LDS),

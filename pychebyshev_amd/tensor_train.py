@@ -28,6 +28,12 @@ is always a ``pcx_tt_eval_batch`` launch; there is no CPU fallback.
 the row's coordinates in the kept dimensions -- is one launch of the TT chain with the antiderivative basis in the
 integrated dimensions (``pcx_tt_box_batch``, ``csrc/tt_box_kernels.h``).
 
+``eval_multi`` / ``eval_multi_batch`` take ``method="analytic"`` for the exact derivatives of the interpolant in place
+of the reference's finite differences (the default, unchanged): the same chain with ``T_j``, ``T'_j`` or ``T''_j`` as the
+basis of a differentiated dimension, one launch for all rows and specs (``pcx_tt_deriv_batch``,
+``csrc/tt_deriv_kernels.h``).  ``differentiate`` returns the derivative as a model: the coefficient-derivative
+recurrence on the host cores.
+
 ``orth_left`` / ``orth_right`` run their Householder QR sweep on the device (``pcx_tt_orth``).  ``run_completion`` --
 fixed-rank alternating least squares against the values on the whole grid -- runs all its outer iterations in one
 device call (``pcx_tt_als``, ``csrc/tt_als_kernels.h``): with the neighbouring cores orthonormal each core's solve is
@@ -125,6 +131,11 @@ def _coeff_core_to_value_core(coeff_core: np.ndarray) -> np.ndarray:
     theta = np.pi * (2.0 * np.arange(n - 1, -1, -1) + 1.0) / (2.0 * n)      # ascending nodes x_i = cos(theta_i)
     basis = np.cos(np.outer(theta, np.arange(n)))
     return np.einsum("ij,rjs->ris", basis, c)
+
+
+def _check_derivative_method(method) -> None:
+    if method not in ("fd", "analytic"):
+        raise ValueError(f"method must be 'fd' or 'analytic', got {method!r}")
 
 
 def _entry_list(params, arity: int) -> list:
@@ -715,12 +726,17 @@ class ChebyshevTT(ErgonomicsMixin):
         from .device import is_device_array
         return self._eval_user_points(points if is_device_array(points) else np.asarray(points))
 
-    def eval_multi(self, point, derivative_orders) -> List[float]:
+    def eval_multi(self, point, derivative_orders, *, method: str = "fd") -> List[float]:
         """Value and central-finite-difference derivatives at one point (reference
         :2267-2463).  All stencil points of all specs go to the device in ONE batch; the
         stencil arithmetic (h = 1e-4 (b - a), boundary nudge 1.5 h, 2/3/4-point and nested
-        rules) is then replayed on the host in the reference's order."""
+        rules) is then replayed on the host in the reference's order.  ``method="analytic"`` (extension): the exact
+        derivatives of the interpolant, row 0 of a one-row :meth:`eval_multi_batch` with that method."""
         self._check_built()
+        _check_derivative_method(method)
+        if method == "analytic":
+            row = self.eval_multi_batch(np.asarray([list(point)], dtype=float), derivative_orders, method="analytic")
+            return [float(v) for v in row[0]]
         d = self.num_dimensions
         order = self._dim_order
         if order != list(range(d)):
@@ -744,15 +760,21 @@ class ChebyshevTT(ErgonomicsMixin):
         it = iter(vals)
         return run(lambda p: float(next(it)))         # pass 2: same traversal, real values
 
-    def eval_multi_batch(self, points, derivative_orders, *, chunk: int = 1 << 18):
+    def eval_multi_batch(self, points, derivative_orders, *, chunk: int = 1 << 18, method: str = "fd"):
         """Batched :meth:`eval_multi` (extension; the reference evaluates one point per call): ``(N, d)``
         points x ``m`` specs -> ``(N, m)``.  The finite-difference rules of the reference
         (``tensor_train.py:2322-2463``) run ON THE DEVICE (``pcx_tt_eval_multi_batch``, ``csrc/tt_fd_kernels.h``):
         every stencil point is formed from the query row in registers and evaluated by the model's own chain, so
         row i equals ``eval_multi(points[i], derivative_orders)`` bit for bit and no stencil batch crosses PCIe.
         A device array in gives a device array out.  Specs with more than three differenced dimensions (27+
-        stencil points) keep the host-side traversal (``_eval_multi_batch_host``)."""
+        stencil points) keep the host-side traversal (``_eval_multi_batch_host``).
+
+        ``method="analytic"``: the exact derivatives of the interpolant instead (``pcx_tt_deriv_batch``,
+        ``csrc/tt_deriv_kernels.h``) -- one chain per (row, spec) with ``T_j``, ``T'_j`` or ``T''_j`` as the basis of a
+        dimension.  No step size, no nudge at a domain end, any number of differentiated dimensions, host or device
+        arrays; ``chunk`` is not used."""
         self._check_built()
+        _check_derivative_method(method)
         d = self.num_dimensions
         specs_user = [[int(v) for v in s] for s in derivative_orders]
         for spec in specs_user:
@@ -767,11 +789,14 @@ class ChebyshevTT(ErgonomicsMixin):
         if m == 0:
             n0 = int(points.shape[0]) if hasattr(points, "shape") else len(points)
             return np.empty((n0, 0))
-        if any(sum(1 for o in spec if o) > 3 for spec in specs_user):
+        analytic = method == "analytic"
+        if not analytic and any(sum(1 for o in spec if o) > 3 for spec in specs_user):
             if on_device:
                 raise NotImplementedError("specs with more than three differenced dimensions need host arrays")
             return self._eval_multi_batch_host(points, specs_user, chunk=chunk)
         t = self._dev()
+        host_entry = t.lib.pcx_tt_deriv_batch if analytic else t.lib.pcx_tt_eval_multi_batch
+        dev_entry = t.lib.pcx_tt_deriv_batch_dev if analytic else t.lib.pcx_tt_eval_multi_batch_dev
         block = _lib.i32(np.asarray(specs_user).reshape(-1))
         if on_device:
             dev_pts = as_device_array(points)
@@ -780,8 +805,8 @@ class ChebyshevTT(ErgonomicsMixin):
             if n:
                 st = ctypes.c_void_p()
                 _lib.check(t.lib.pcx_tt_stream(t.handle, ctypes.byref(st)), t.lib)
-                _lib.check(t.lib.pcx_tt_eval_multi_batch_dev(t.handle, ctypes.c_void_p(dev_pts.ptr), n, _lib.p_i32(block), m,
-                                                             ctypes.c_void_p(dout.ptr), st), t.lib)
+                _lib.check(dev_entry(t.handle, ctypes.c_void_p(dev_pts.ptr), n, _lib.p_i32(block), m,
+                                     ctypes.c_void_p(dout.ptr), st), t.lib)
                 _lib.check(t.lib.pcx_stream_synchronize(st), t.lib)
             return dout
         pts = _lib.f64(np.asarray(points, dtype=float))
@@ -789,8 +814,7 @@ class ChebyshevTT(ErgonomicsMixin):
             raise ValueError(f"points must have shape (N, {d}), got {pts.shape}")
         out = np.empty((pts.shape[0], m))
         if pts.shape[0]:
-            _lib.check(t.lib.pcx_tt_eval_multi_batch(t.handle, _lib.p_f64(pts), pts.shape[0], _lib.p_i32(block), m,
-                                                     _lib.p_f64(out)), t.lib)
+            _lib.check(host_entry(t.handle, _lib.p_f64(pts), pts.shape[0], _lib.p_i32(block), m, _lib.p_f64(out)), t.lib)
         return out
 
     def _eval_multi_batch_host(self, points, derivative_orders, *, chunk: int = 1 << 18) -> np.ndarray:
@@ -1459,6 +1483,37 @@ class ChebyshevTT(ErgonomicsMixin):
             _lib.check(t.lib.pcx_tt_box_batch(t.handle, _lib.p_i32(flags), _lib.p_f64(rows), rows.shape[0],
                                               _lib.p_f64(out)), t.lib)
         return out
+
+    def differentiate(self, derivative_order) -> "ChebyshevTT":
+        """The partial derivative as a model of its own (extension): ``derivative_order`` gives an order >= 0 per user
+        dimension, and each differentiated core goes through the Chebyshev coefficient-derivative recurrence along
+        axis 1 (``c'_{j-1} = c'_{j+1} + 2 j c_j``, the constant halved) that many times, scaled by ``2 / (b - a)`` per
+        order.  Host NumPy on cores of a few kilobytes, as :meth:`slice` and :meth:`integrate`.  Node counts, domain and
+        ``dim_order`` are kept (the top coefficients of a differentiated core are zero); an order that reaches a
+        dimension's node count gives the zero model.  ``function`` is ``None``.  The result evaluates, slices,
+        integrates and goes through ``roots`` / ``minimize`` like any other model -- the zeros of a delta are
+        ``tt.differentiate(spec).roots(...)`` -- and its ``eval_batch`` is a second route to
+        ``eval_multi_batch(points, [spec], method="analytic")``."""
+        from numpy.polynomial.chebyshev import chebder
+        self._check_built()
+        d = self.num_dimensions
+        spec = list(derivative_order)
+        if len(spec) != d:
+            raise ValueError(f"derivative_order needs {d} orders, got {len(spec)}")
+        for o in spec:
+            if not isinstance(o, (int, np.integer)) or isinstance(o, bool) or o < 0:
+                raise ValueError(f"Derivative order {o!r} not supported (use an integer >= 0)")
+        cores = []
+        for pos, core in enumerate(self._coeff_cores):
+            p = int(spec[self._dim_order[pos]])
+            new = np.array(core, dtype=float)
+            if p:
+                a, b = self.domain[pos]
+                der = chebder(new, m=p, scl=2.0 / (b - a), axis=1)      # p >= n: one zero coefficient
+                new = np.zeros_like(new)
+                new[:, :der.shape[1], :] = der
+            cores.append(new)
+        return self._derived(cores)
 
 
     # ---------------------------------------------------------------- persistence
