@@ -164,6 +164,33 @@ int pcx_bary_sobol(pcx_bary *h, double *variance_out, double *first_out, double 
 int pcx_tensor_contract_axis(int device, int d, const int32_t *n_nodes, const double *tensor,
                              int axis, const double *vec, double *out);
 
+/* Rectangular mode product of host arrays, the companion of pcx_tensor_contract_axis and the pass of a tensor-product
+ * grid evaluation:   Y[o, j, q] = sum_i W[j, i] * X[o, i, q],   o < outer, i < n, j < m, q < inner   (C order, FP64).
+ * variant: 0 = auto, 1 = any-shape VALU form (one fma chain per output, i ascending), 2 = v_mfma_f64_16x16x4_f64 form
+ * (the same chain per output: both forms agree bit for bit, whatever the tile an output falls in).  Any other variant:
+ * PCX_ERR_INVALID; more than 2^40 elements in X or Y: PCX_ERR_UNSUPPORTED.  A row of W that is one-hot (a single 1.0,
+ * zeros elsewhere) is a gather of X, not a sum: identical on finite data, and it keeps a NaN or Inf elsewhere in the
+ * fibre out of that output.                                                                                        */
+int pcx_tensor_mode_product(int device, int64_t outer, int n, int64_t inner, const double *X, int m, const double *W,
+                            double *Y, int variant);
+
+/* The interpolant (or its derivative `deriv`, NULL = plain values) on the tensor-product grid x_0 x ... x x_{d-1}:
+ * out[i_0, ..., i_{d-1}] (C order, prod m_k doubles) = the value at (x_0[i_0], ..., x_{d-1}[i_{d-1}]).  m holds the d
+ * axis lengths (each >= 1: an empty axis is PCX_ERR_INVALID), axes_cat the sum m_k coordinates, dimension 0 first,
+ * always on the HOST.  Axes may be unsorted, repeat values and leave the domain; they are not checked.
+ *   Weights: per axis the m_k x n_k matrix W_k of the reference's pointwise rule (barycentric.py:941-947): a
+ *     coordinate within 1e-14 of a node gives a one-hot row at the FIRST such node (a gather of the tensor, bit for
+ *     bit); otherwise (w_i / (x - node_i)) / sum_i (w_i / (x - node_i)).
+ *   Order: d mode products of the handle's derivative tensor, dimensions by ascending m_k / n_k (compared exactly as
+ *     m_a n_b < m_b n_a in 64-bit integers; ties: the higher dimension first), so the intermediates stay small; they
+ *     ping-pong between two scratch buffers of the handle and the last pass writes the result.
+ * Parity with pointwise evaluation (pcx_bary_eval_batch on the meshgrid: 1e-12 normwise) holds for FINITE tensors: the
+ * two routes sum in different orders and spread a NaN or Inf differently.  Every allocation precedes the first launch.
+ * The _dev form writes d_out in HBM, enqueues on `stream` (NULL = the handle's own) and returns without synchronizing. */
+int pcx_bary_eval_tensor_grid(pcx_bary *h, const int32_t *deriv, const int32_t *m, const double *axes_cat, double *out);
+int pcx_bary_eval_tensor_grid_dev(pcx_bary *h, const int32_t *deriv, const int32_t *m, const double *axes_cat,
+                                  double *d_out, void *stream);
+
 /* Kernel selection and introspection.  variant: 0 = auto, 1 = row-parallel VALU kernel
  * (any shape), 2 = MFMA kernel (v_mfma_f64_16x16x4_f64), 3 = the same contraction on
  * v_mfma_f64_4x4x4_4b_f64 with LDS-staged tiles (bit-identical to 2; opt-in, never picked
@@ -427,6 +454,15 @@ int pcx_tt_value_to_coeff_core(int device, const double *value_core, int rl, int
  * coeff_cores_cat).  Used by the convergence check (:287-297).                        */
 int pcx_tt_grid_eval(int device, int d, const int32_t *n_nodes, const int32_t *ranks,
                      const double *value_cores_cat, const int32_t *idx, int count, double *out);
+
+/* The dense tensor of a tensor train on a tensor-product grid (stateless, like pcx_tt_round): grid_cores_cat holds the
+ * value cores ON THE GRID, G_k of shape (r_k, m_k, r_{k+1}) with ranks[0] = ranks[d] = 1, C order, concatenated; out
+ * receives prod m_k doubles, C order, dimensions in storage order.  The chain
+ *   P_{k+1} = reshape(P_k, (m_0 .. m_{k-1}, r_k)) . reshape(G_k, (r_k, m_k r_{k+1}))
+ * runs on the device as d - 1 mode products (pcx_tensor_mode_product with outer = 1), from the left or from the right,
+ * whichever has the smaller largest intermediate (a tie: from the left).  An empty axis is PCX_ERR_INVALID.  (Not to
+ * be confused with pcx_tt_grid_eval above, which evaluates integer grid INDEX tuples for TT-Cross.)                   */
+int pcx_tt_tensor_grid(int device, int d, const int32_t *m, const int32_t *ranks, const double *grid_cores_cat, double *out);
 
 /* TT-SVD compression of a dense C-order value tensor (d dims, n_nodes): replaces
  * _tt_svd_from_tensor (tensor_train.py:638-690), used by ChebyshevTT.from_values (:2871-2965)

@@ -29,6 +29,7 @@ SOURCES = {
     "pcx_bary_box.hip": BARY_H + ["bary_kernels.h", "bary_box_kernels.h"],
     "pcx_bary_grid.hip": BARY_H + ["bary_grid_kernels.h", "bary_weights.h"],
     "pcx_bary_kfold.hip": BARY_H + ["bary_kfold_kernels.h"],
+    "pcx_mode_product.hip": BARY_H + ["grid_plan.h", "mode_product_kernels.h"],
     "pcx_spline.hip": BARY_H + ["pcx_slider_internal.h", "pcx_spline_internal.h", "gather_kernels.h",
                        "route_kernels.h"],
     "pcx_slider_box.hip": BARY_H + ["pcx_slider_internal.h", "gather_kernels.h", "slider_calc_kernels.h"],

@@ -86,6 +86,10 @@ SIGNATURES = {
     "pcx_bary_calculus_batch": (_I, [_V, _I, c_f64p, c_f64p, c_f64p, _L, _I, c_f64p, c_i32p, c_f64p, c_f64p]),
     "pcx_tt_calculus_batch": (_I, [_V, _I, c_f64p, _L, _I, c_f64p, c_i32p, c_f64p, c_f64p]),
     "pcx_tensor_contract_axis": (_I, [_I, _I, c_i32p, c_f64p, _I, c_f64p, c_f64p]),
+    "pcx_tensor_mode_product": (_I, [_I, _L, _I, _L, c_f64p, _I, c_f64p, c_f64p, _I]),
+    "pcx_bary_eval_tensor_grid": (_I, [_V, c_i32p, c_i32p, c_f64p, c_f64p]),
+    "pcx_bary_eval_tensor_grid_dev": (_I, [_V, c_i32p, c_i32p, c_f64p, _V, _V]),
+    "pcx_tt_tensor_grid": (_I, [_I, _I, c_i32p, c_i32p, c_f64p, c_f64p]),
     "pcx_bary_set_kernel": (_I, [_V, _I]),
     "pcx_bary_set_group_span": (_I, [_V, _I]),
     "pcx_bary_count_gemms": (_I, [_V, c_i32p, _I, _L, c_i32p]),

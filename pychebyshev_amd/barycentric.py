@@ -188,6 +188,28 @@ def _unwrap_typed(domain, n_nodes, special_points):
     return domain, n_nodes, special_points
 
 
+def _grid_axes(axes, num_dimensions: int):
+    """The axes of a tensor-product grid as ``num_dimensions`` one-dimensional float64 arrays (a scalar counts as
+    length 1); ``ValueError`` names the offending dimension."""
+    try:
+        axes = list(axes)
+    except TypeError:
+        raise ValueError(f"axes must be a sequence of {num_dimensions} one-dimensional arrays") from None
+    if len(axes) != num_dimensions:
+        raise ValueError(f"axes must have {num_dimensions} entries (one per dimension), got {len(axes)}")
+    out = []
+    for k, a in enumerate(axes):
+        arr = np.asarray(a, dtype=float)
+        if arr.ndim == 0:
+            arr = arr.reshape(1)
+        if arr.ndim != 1:
+            raise ValueError(f"axes[{k}] must be one-dimensional, got shape {arr.shape} for dimension {k}")
+        if arr.size == 0:
+            raise ValueError(f"axes[{k}] is empty: dimension {k} needs at least one coordinate")
+        out.append(np.ascontiguousarray(arr))
+    return out
+
+
 class _DeviceModel:
     """Owner of one ``pcx_bary`` handle (freed on garbage collection)."""
 
@@ -578,6 +600,57 @@ class ChebyshevApproximation(ErgonomicsMixin, DerivativeIdMixin):
             raise ValueError(f"points must have shape (N, {self.num_dimensions}), got {pts.shape}")
         out = np.empty((pts.shape[0], specs.shape[0]))
         self._eval_host(pts, specs, out)
+        return out
+
+    def eval_grid(self, axes, derivative_order=None, *, derivative_id=None, out=None):
+        """The interpolant on the tensor-product grid ``axes[0] x ... x axes[d-1]`` (extension; what the reference's
+        ``plot_2d_surface`` / ``plot_2d_contour`` and a risk ladder evaluate point by point):
+        ``result[i_0, ..., i_{d-1}] = vectorized_eval([axes[0][i_0], ...], derivative_order)``, shape
+        ``(m_0, ..., m_{d-1})``.
+
+        ``axes``: ``d`` one-dimensional array-likes (a scalar counts as length 1); unsorted, repeated and out-of-domain
+        values are taken as they are, like ``vectorized_eval`` takes them.  ``derivative_order`` / ``derivative_id`` as
+        in ``vectorized_eval``; both ``None`` means the plain values.  The value tensor is multiplied along each axis
+        by the ``m_k x n_k`` matrix of barycentric weights (``pcx_bary_eval_tensor_grid``): ``prod m . n`` flops in all
+        where the meshgrid through ``vectorized_eval_batch`` pays ``prod n`` per point.
+
+        ``out=None`` returns a NumPy array.  ``out=`` a :class:`~pychebyshev_amd.device.DeviceArray` of that shape on
+        the model's device is filled in HBM and returned (complete on return)."""
+        if derivative_order is None and derivative_id is None:
+            derivative_order = [0] * self.num_dimensions
+        else:
+            derivative_order = self._resolve_derivative_args(derivative_order, derivative_id)
+        if self.tensor_values is None:
+            raise RuntimeError("Call build() first")
+        ax = _grid_axes(axes, self.num_dimensions)
+        spec = self._check_orders(derivative_order)
+        shape = tuple(a.size for a in ax)
+        m = _lib.i32(shape)
+        cat = _lib.f64(np.concatenate(ax))
+        if out is None:
+            model = self._model()
+            res = np.empty(shape)
+            _lib.check(model.lib.pcx_bary_eval_tensor_grid(model.handle, _lib.p_i32(spec), _lib.p_i32(m), _lib.p_f64(cat),
+                                                          _lib.p_f64(res)), model.lib)
+            return res
+        from .device import as_device_array
+        dev_out = as_device_array(out)
+        if dev_out is None:
+            raise ValueError("out must be a DeviceArray (or None for a NumPy result)")
+        if dev_out.ndim != len(shape):
+            raise ValueError(f"out.shape={dev_out.shape} has {dev_out.ndim} dimensions, the grid {shape} has {len(shape)}")
+        for k, (have, want) in enumerate(zip(dev_out.shape, shape)):
+            if have != want:
+                raise ValueError(f"out.shape={dev_out.shape} does not match the grid {shape} at dimension {k}")
+        model = self._model()
+        if dev_out.device != model.device:
+            raise ValueError(f"out lives on device {dev_out.device} but the model is on device {model.device}; "
+                             f"call to_device({dev_out.device}) on the model first")
+        st = ctypes.c_void_p()
+        _lib.check(model.lib.pcx_bary_stream(model.handle, ctypes.byref(st)), model.lib)
+        _lib.check(model.lib.pcx_bary_eval_tensor_grid_dev(model.handle, _lib.p_i32(spec), _lib.p_i32(m), _lib.p_f64(cat),
+                                                          ctypes.c_void_p(dev_out.ptr), st), model.lib)
+        _lib.check(model.lib.pcx_stream_synchronize(st), model.lib)
         return out
 
     # aliases for the words BASELINE.json uses; the reference names above stay primary

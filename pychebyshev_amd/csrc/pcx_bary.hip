@@ -23,7 +23,9 @@ pcx_bary::~pcx_bary() {
                     (void *)d_gsnodes, (void *)d_rowcode, (void *)d_kcode, (void *)d_rowcode_hi, (void *)d_kcode_hi,
                     (void *)d_rowcode_g0, (void *)d_rowoff[0], (void *)d_rowoff[1]})
         (void)hipFree(p);
-    for (Scratch *sc : {&s_partial, &s_cheb[0], &s_cheb[1], &s_sobol, &s_rot, &s_rot2}) sc->release();
+    for (Scratch *sc : {&s_partial, &s_cheb[0], &s_cheb[1], &s_sobol, &s_rot, &s_rot2, &s_grid[0], &s_grid[1], &s_gridw, &s_gridout})
+        sc->release();
+    if (grid_done) (void)hipEventDestroy(grid_done);
     for (pcx_bary *r : rot)
         if (r) pcx_bary_destroy(r);
     stage.release();
@@ -119,6 +121,8 @@ extern "C" int pcx_bary_create(int device, int d, const int32_t *n_nodes, const 
     h->g0_span = env.g0_span;
     h->group_tol = env.group_tol;
     if ((rc = bary_make_plan(dm, total, nodes_cat, env, *h))) return rc;
+    h->h_nodes.assign(nodes_cat, nodes_cat + sum_n);
+    h->h_wts.assign(weights_cat, weights_cat + sum_n);
 
     // the grid arrays and the tables the plan asks for
     HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));

@@ -46,6 +46,13 @@ struct pcx_bary : BaryLaunchPlan {
     double *d_cheb = nullptr;        // values -> Chebyshev coefficients matrix per dimension, at doff[k] (pcx_bary_sobol; lazy)
     Scratch s_cheb[2];               // the coefficient passes ping-pong between these (prod n doubles each, kept after first use)
     Scratch s_sobol;                 // k_sobol_energy's slab + k_sobol_finish's result
+    // tensor-product grids (pcx_mode_product.hip): the passes ping-pong between s_grid, the W_k sit in s_gridw, a host
+    // result is staged in s_gridout; grid_done is recorded behind the last pass of a call, and the next call waits for
+    // it before it touches any of them (a _dev caller may be on a stream of its own)
+    std::vector<double> h_nodes, h_wts;   // host copies of nodes_cat / weights_cat: the grid planner forms W_k from them
+    Scratch s_grid[2], s_gridw, s_gridout;
+    std::vector<double> grid_w_host;
+    hipEvent_t grid_done = nullptr;
     // the plan's tables (bary_plan.h has their builders)
     unsigned *d_rowcode = nullptr, *d_kcode = nullptr;
     unsigned *d_rowcode_hi = nullptr, *d_kcode_hi = nullptr;   // fields 4..7 (wide plans only)
