@@ -252,6 +252,8 @@ extern "C" int pcx_tt_svd(int device, int d, const int32_t *n_nodes, const doubl
             int effective = 0;
             for (int i = 0; i < len_s; ++i) effective += (std::sqrt(hnorm[order[i]]) > tol * s0) ? 1 : 0;
             rank = std::max(1, std::min(rank, effective));
+        } else {
+            rank = 1;       // an all-zero unfolding: one zero row carries it (the reference keeps min(max_rank, len(S)) of them)
         }
         if (written + (int64_t)m * rank > cores_cap) return fail(PCX_ERR_INVALID, "cores_out too small");
         hU.resize((size_t)m * m);

@@ -10,7 +10,9 @@
 // row pairs until all rows are mutually orthogonal.  Then C = U B with U = the product of
 // the rotations and B's rows = sigma_i v_i^T, i.e. exactly the two factors TT-SVD needs --
 // no separate V, no S^-1 scaling, and the small singular values keep their relative
-// accuracy (a Gram-matrix eigensolver would lose everything below 1e-8 sigma_max).
+// accuracy (a Gram-matrix eigensolver would lose everything below 1e-8 sigma_max): on rows
+// graded over 12 decades every sigma is within 4e-14 of its 80-digit value on every path,
+// the Gram-preconditioned ones included (tests/test_gpu_row_jacobi.py).
 // One workgroup per row pair; the m/2 disjoint pairs of a round-robin tournament step run
 // in one launch, m-1 steps make a sweep.  Everything a sweep touches is L2-resident.
 #pragma once
@@ -187,7 +189,9 @@ k_rowjacobi_lds(double *__restrict__ Bg, int m, int N, double *__restrict__ Ug, 
 // everything below sqrt(eps) sigma_max is noise there.  So it is used as a PRECONDITIONER: its
 // accumulated rotations V make the rows of B0 = V^T C orthogonal to ~1e-8, and the accurate
 // one-sided iteration on B0 (k_rowjacobi_step, U started at V) then converges in one or two
-// sweeps instead of a dozen -- with the relative accuracy of small singular values intact.
+// sweeps instead of a dozen -- with the relative accuracy of small singular values intact (V only
+// rotates; measured 1.5e-14 on graded rows, where the rows below the Gram noise floor are left to the
+// row iteration and cost it as many sweeps as without the preconditioner).
 __global__ void __launch_bounds__(TTSVD_THREADS)
 k_gram_rows(const double *__restrict__ B, long ldb, int m, long N, double *__restrict__ G) {
     __shared__ double red[4];
