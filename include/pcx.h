@@ -437,11 +437,14 @@ int pcx_spline_calculus_batch(pcx_spline *h, int dim, const double *lo, const do
 /* One unfolding step of _tt_cross (:332-362 and :449-474): thin SVD of the m x c cross
  * matrix C (row-major), rank = max(1, min(cap, #{S > rel_thresh*S0}, min(m,c))), maxvol
  * rows of U[:, :rank] when m > rank, C_hat = U inv(U[piv]).  Outputs: chat (m x rank
- * row-major), pivots (rank), rank.  Runs on `device` (single-workgroup HIP kernels).  */
+ * row-major), pivots (rank), rank.  Runs on `device` (single-workgroup HIP kernels).
+ * The result does not depend on the scale of C (any finite FP64 magnitudes).  m <= 8192 and
+ * c <= 64, else PCX_ERR_UNSUPPORTED; an entry that is not finite is PCX_ERR_INVALID.      */
 int pcx_tt_cross_step(int device, const double *C, int m, int c, int cap, double rel_thresh,
                       double *chat, int64_t *pivots, int32_t *rank_out);
 
-/* _maxvol (:38-120) on a row-major m x r matrix; idx_out receives r row indices.      */
+/* _maxvol (:38-120) on a row-major m x r matrix; idx_out receives r row indices (m <= r:
+ * 0 .. m-1).  Same limits; an entry that is not finite is PCX_ERR_INVALID.              */
 int pcx_maxvol(int device, const double *A, int m, int r, double tol, int max_iters,
                int64_t *idx_out);
 

@@ -573,6 +573,15 @@ extern "C" int pcx_tt_reorder(int device, int d, const int32_t *n_nodes, const i
     PCX_API_END
 }
 
+// The dense steps take at most 8192 x 64 entries: checked on the host before the upload.  A NaN or an infinity would
+// come back as pivots and a rank like any others.
+static int require_finite(const char *what, const double *A, int m, int r) {
+    for (long f = 0; f < (long)m * r; ++f)
+        if (!std::isfinite(A[f]))
+            return fail(PCX_ERR_INVALID, "%s: entry (%ld, %ld) of the %d x %d matrix is not finite", what, f / r, f % r, m, r);
+    return PCX_OK;
+}
+
 extern "C" int pcx_maxvol(int device, const double *A, int m, int r, double tol, int max_iters,
                           int64_t *idx_out) {
     PCX_API_BEGIN
@@ -582,8 +591,9 @@ extern "C" int pcx_maxvol(int device, const double *A, int m, int r, double tol,
         return PCX_OK;
     }
     if (r > TTX_MAX_R || m > TTX_MAX_M) return fail(PCX_ERR_UNSUPPORTED, "maxvol: %d x %d exceeds %d x %d", m, r, TTX_MAX_M, TTX_MAX_R);
-    int rc = use_device(device);
+    int rc = require_finite("maxvol", A, m, r);
     if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
     DevBuf dA, dB, didx;
     if ((rc = dA.alloc((size_t)m * r * sizeof(double)))) return rc;
     if ((rc = dB.alloc((size_t)m * r * sizeof(double)))) return rc;
@@ -602,8 +612,9 @@ extern "C" int pcx_tt_cross_step(int device, const double *C, int m, int c, int 
     PCX_API_BEGIN
     if (!C || !chat || !pivots || !rank_out || m < 1 || c < 1 || cap < 1) return fail(PCX_ERR_INVALID, "bad argument");
     if (c > TTX_MAX_R || m > TTX_MAX_M) return fail(PCX_ERR_UNSUPPORTED, "cross step: %d x %d exceeds %d x %d", m, c, TTX_MAX_M, TTX_MAX_R);
-    int rc = use_device(device);
+    int rc = require_finite("cross step", C, m, c);  // the reference's SVD raises LinAlgError here
     if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
     DevBuf dC, dU, dB, dchat, dpiv, drank;
     if ((rc = dC.alloc((size_t)m * c * sizeof(double)))) return rc;
     if ((rc = dU.alloc((size_t)m * c * sizeof(double)))) return rc;

@@ -29,6 +29,12 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = __builtin_fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
 // (value, index) arg-max with ties resolved to the smallest index (np.argmax semantics).
 __device__ __forceinline__ void wave_argmax(double &v, long &i) {
 #pragma unroll
@@ -179,7 +185,15 @@ k_cross_step(const double *__restrict__ C, int m, int c, int cap, double rel_thr
     __shared__ int order[TTX_MAX_R];
     const int lane = threadIdx.x;
 
-    for (long f = lane; f < (long)m * c; f += TTX_THREADS) W[f] = C[f];
+    // W = C times the power of two that brings max|C| into [1, 2): exact, and C_hat, the pivots and the rank are
+    // homogeneous of degree 0 in C, so the squared norms and their products below neither overflow nor underflow
+    // whatever the scale of C (the host has checked that C is finite).  A zero C stays as it is.
+    double mx = 0.0;
+    for (long f = lane; f < (long)m * c; f += TTX_THREADS) mx = __builtin_fmax(mx, __builtin_fabs(C[f]));
+    mx = wave_max(mx);
+    int ex = 0;
+    if (mx > 0.0) { (void)__builtin_frexp(mx, &ex); ex = 1 - ex; }  // mx = f 2^e, f in [0.5, 1): scale by 2^(1 - e)
+    for (long f = lane; f < (long)m * c; f += TTX_THREADS) W[f] = __builtin_ldexp(C[f], ex);
     __syncthreads();
 
     // ---- one-sided Jacobi: rotate column pairs until mutually orthogonal
