@@ -282,6 +282,24 @@ int pcx_spline_eval_batch_dev(pcx_spline *h, const double *d_pts, int64_t N, con
                               double *d_out);
 int pcx_spline_eval_multi_batch_dev(pcx_spline *h, const double *d_pts, int64_t N,
                                     const int32_t *derivs, int m, double *d_out);
+/* The piecewise interpolant (or its derivative `deriv`, NULL = plain values) on the tensor-product grid
+ * x_0 x ... x x_{d-1}: out[i_0, ..., i_{d-1}] (C order, prod m_k doubles) = pcx_spline_eval_batch at
+ * (x_0[i_0], ..., x_{d-1}[i_{d-1}]).  m, axes_cat (always on the HOST) and their errors as for pcx_bary_eval_tensor_grid:
+ * an empty axis is PCX_ERR_INVALID and names the dimension, more than 2^40 grid points are PCX_ERR_UNSUPPORTED, a NULL
+ * handle or buffer is PCX_ERR_INVALID.  Axes may be unsorted, repeat values and leave the domain.
+ *   Routing: per dimension, the interval of a coordinate is the number of knots <= it (searchsorted side='right', clipped
+ *     to the last piece): a coordinate on a knot belongs to the right-hand piece, one outside the domain to the end piece,
+ *     which extrapolates, a NaN to the last piece.  There is no knot check for derivative specs (eval_batch has none).
+ *   Evaluation: a piece is live when every dimension has an axis entry in its interval.  Every live piece runs
+ *     pcx_bary_eval_tensor_grid_dev on the entries of its intervals (ascending position) into its block of a packed
+ *     staging buffer -- bit for bit what the piece's own grid evaluation returns --, on the stream or round-robin on the
+ *     handle's side streams, without a host synchronization in between; one kernel then copies every element from its
+ *     block to its place.  With a single live piece the piece writes the result itself.
+ * Every allocation of the handle precedes its first launch of the call.  The _dev form writes d_out in HBM, enqueues on
+ * `stream` (NULL = the handle's own) and returns without synchronizing.                                                */
+int pcx_spline_eval_tensor_grid(pcx_spline *h, const int32_t *deriv, const int32_t *m, const double *axes_cat, double *out);
+int pcx_spline_eval_tensor_grid_dev(pcx_spline *h, const int32_t *deriv, const int32_t *m, const double *axes_cat,
+                                    double *d_out, void *stream);
 
 /* ---- slider: sum of low-dimensional slides around a pivot -------------------- */
 /* State of ChebyshevSlider (slider.py:80-341): the slides are barycentric handles over the
@@ -317,6 +335,19 @@ int pcx_slider_box_batch(pcx_slider *h, const int32_t *flags, const double *lo, 
                          int64_t N, double *out);
 int pcx_slider_box_batch_dev(pcx_slider *h, const int32_t *flags, const double *lo, const double *hi, const double *d_rows,
                              int64_t N, double *d_out);
+/* The slider (or its derivative `deriv`, NULL = plain values) on the tensor-product grid x_0 x ... x x_{d-1}:
+ * out[i_0, ..., i_{d-1}] (C order, prod m_k doubles) = pcx_slider_eval_batch at (x_0[i_0], ..., x_{d-1}[i_{d-1}]).  m,
+ * axes_cat (always on the HOST) and the errors as for pcx_spline_eval_tensor_grid.
+ *   value:       every slide runs pcx_bary_eval_tensor_grid_dev on the axes of its own group (the group's order) into the
+ *                handle's scratch, G_s; one kernel writes r = pivot; r += G_s[i restricted to group s] - pivot, slides in
+ *                order -- the operations of pcx_slider_eval_batch in their order, G_s broadcast over the other dimensions;
+ *   derivative:  all differentiated dimensions in one slide -> that slide's derivative grid, broadcast by the same kernel
+ *                (no pivot terms); spread over more than one slide -> +0.0 everywhere (a memset).
+ * Every allocation of the handle precedes its first launch of the call.  The _dev form writes d_out in HBM, enqueues on
+ * `stream` (NULL = the handle's own) and returns without synchronizing.                                                */
+int pcx_slider_eval_tensor_grid(pcx_slider *h, const int32_t *deriv, const int32_t *m, const double *axes_cat, double *out);
+int pcx_slider_eval_tensor_grid_dev(pcx_slider *h, const int32_t *deriv, const int32_t *m, const double *axes_cat,
+                                    double *d_out, void *stream);
 
 /* ---- tensor-train interpolant ---------------------------------------------- */
 /* State of ChebyshevTT (tensor_train.py:1117-1138): Chebyshev COEFFICIENT cores

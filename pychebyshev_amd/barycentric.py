@@ -210,6 +210,59 @@ def _grid_axes(axes, num_dimensions: int):
     return out
 
 
+def _grid_out(out, shape):
+    """``eval_grid``'s ``out=`` as a ``DeviceArray`` of the grid's shape; ``ValueError`` names the first dimension that
+    differs.  Needs no device: a wrong ``out`` is refused before the model goes to one."""
+    from .device import as_device_array
+    dev_out = as_device_array(out)
+    if dev_out is None:
+        raise ValueError("out must be a DeviceArray (or None for a NumPy result)")
+    if dev_out.ndim != len(shape):
+        raise ValueError(f"out.shape={dev_out.shape} has {dev_out.ndim} dimensions, the grid {shape} has {len(shape)}")
+    for k, (have, want) in enumerate(zip(dev_out.shape, shape)):
+        if have != want:
+            raise ValueError(f"out.shape={dev_out.shape} does not match the grid {shape} at dimension {k}")
+    return dev_out
+
+
+def _grid_out_device(dev_out, device: int) -> None:
+    if dev_out.device != device:
+        raise ValueError(f"out lives on device {dev_out.device} but the model is on device {device}; "
+                         f"call to_device({dev_out.device}) on the model first")
+
+
+def _composite_eval_grid(owner, entry: str, axes, derivative_order, derivative_id, out):
+    """``eval_grid`` of the classes built out of barycentric handles (``ChebyshevSpline``, ``ChebyshevSlider``): the
+    contract of ``ChebyshevApproximation.eval_grid`` through ``<entry>`` / ``<entry>_dev`` of the C ABI.  ``owner._dev()``
+    gives the object that holds ``lib``, ``handle`` and ``device``."""
+    d = owner.num_dimensions
+    if derivative_order is None and derivative_id is None:
+        derivative_order = [0] * d
+    else:
+        derivative_order = owner._resolve_derivative_args(derivative_order, derivative_id)
+    if not owner._built:
+        raise RuntimeError("Call build() before eval_grid().")
+    ax = _grid_axes(axes, d)
+    spec = _lib.i32(derivative_order)
+    if spec.shape != (d,):
+        raise ValueError(f"derivative_order must have {d} entries")
+    shape = tuple(a.size for a in ax)
+    m = _lib.i32(shape)
+    cat = _lib.f64(np.concatenate(ax))
+    if out is None:
+        s = owner._dev()
+        res = np.empty(shape)
+        _lib.check(getattr(s.lib, entry)(s.handle, _lib.p_i32(spec), _lib.p_i32(m), _lib.p_f64(cat), _lib.p_f64(res)), s.lib)
+        return res
+    dev_out = _grid_out(out, shape)
+    s = owner._dev()
+    _grid_out_device(dev_out, s.device)
+    _lib.check(getattr(s.lib, entry + "_dev")(s.handle, _lib.p_i32(spec), _lib.p_i32(m), _lib.p_f64(cat),
+                                              ctypes.c_void_p(dev_out.ptr), None), s.lib)
+    _lib.check(s.lib.pcx_device_synchronize(s.device), s.lib)      # the handle's own stream: complete on return
+    return out
+
+
 class _DeviceModel:
     """Owner of one ``pcx_bary`` handle (freed on garbage collection)."""
 
@@ -633,19 +686,9 @@ class ChebyshevApproximation(ErgonomicsMixin, DerivativeIdMixin):
             _lib.check(model.lib.pcx_bary_eval_tensor_grid(model.handle, _lib.p_i32(spec), _lib.p_i32(m), _lib.p_f64(cat),
                                                           _lib.p_f64(res)), model.lib)
             return res
-        from .device import as_device_array
-        dev_out = as_device_array(out)
-        if dev_out is None:
-            raise ValueError("out must be a DeviceArray (or None for a NumPy result)")
-        if dev_out.ndim != len(shape):
-            raise ValueError(f"out.shape={dev_out.shape} has {dev_out.ndim} dimensions, the grid {shape} has {len(shape)}")
-        for k, (have, want) in enumerate(zip(dev_out.shape, shape)):
-            if have != want:
-                raise ValueError(f"out.shape={dev_out.shape} does not match the grid {shape} at dimension {k}")
+        dev_out = _grid_out(out, shape)
         model = self._model()
-        if dev_out.device != model.device:
-            raise ValueError(f"out lives on device {dev_out.device} but the model is on device {model.device}; "
-                             f"call to_device({dev_out.device}) on the model first")
+        _grid_out_device(dev_out, model.device)
         st = ctypes.c_void_p()
         _lib.check(model.lib.pcx_bary_stream(model.handle, ctypes.byref(st)), model.lib)
         _lib.check(model.lib.pcx_bary_eval_tensor_grid_dev(model.handle, _lib.p_i32(spec), _lib.p_i32(m), _lib.p_f64(cat),

@@ -20,4 +20,9 @@ struct pcx_slider {
     std::mutex mu;
     HostStage stage;                     // host-pointer batches
     Scratch s_cols, s_vals, s_partial;
+    // tensor-product grids (pcx_piecewise_grid.hip): the slides' own grids one behind the other in s_grid, the sum
+    // kernel's table in s_gridtab (uploaded from grid_tab_host), a host result in s_gridout; grid_done as in pcx_spline
+    Scratch s_grid, s_gridtab, s_gridout;
+    std::vector<long> grid_tab_host;
+    hipEvent_t grid_done = nullptr;
 };

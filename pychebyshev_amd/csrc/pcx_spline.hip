@@ -18,6 +18,8 @@ extern "C" int pcx_spline_destroy(pcx_spline *h) {
     h->stage.release();
     h->s_piece.release(); h->s_perm.release(); h->s_partial.release();
     h->s_models.release(); h->s_blk.release();
+    h->s_gridstage.release(); h->s_gridtab.release(); h->s_gridout.release();
+    if (h->grid_done) (void)hipEventDestroy(h->grid_done);
     if (h->pin_stage) (void)hipHostFree(h->pin_stage);
     for (int i = 0; i < pcx_spline::kSide; ++i) {
         if (h->side[i]) { (void)hipStreamSynchronize(h->side[i]); (void)hipStreamDestroy(h->side[i]); }
@@ -370,6 +372,8 @@ extern "C" int pcx_slider_destroy(pcx_slider *h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     h->stage.release();
     h->s_cols.release(); h->s_vals.release(); h->s_partial.release();
+    h->s_grid.release(); h->s_gridtab.release(); h->s_gridout.release();
+    if (h->grid_done) (void)hipEventDestroy(h->grid_done);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return PCX_OK;

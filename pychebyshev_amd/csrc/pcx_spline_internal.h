@@ -31,6 +31,12 @@ struct pcx_spline {
     Scratch s_models, s_blk;
     void *pin_stage = nullptr;
     size_t pin_cap = 0;
+    // tensor-product grids (pcx_piecewise_grid.hip): the pieces' blocks are staged in s_gridstage, the placement
+    // kernel's tables sit in s_gridtab (uploaded from grid_tab_host), a host result is staged in s_gridout; grid_done is
+    // recorded behind the placement of a call, and the next call waits for it before it touches any of them
+    Scratch s_gridstage, s_gridtab, s_gridout;
+    std::vector<long> grid_tab_host;
+    hipEvent_t grid_done = nullptr;
 };
 
 // pcx_spline.hip: one chunk of cnt device-resident points (cnt x d) through routing, bucketing and the per-piece

@@ -26,6 +26,11 @@ adds them in ``eval``'s order and solves every fibre on the device; the single c
 nodes and the host restatement of ``_calculus`` above.  ``pcx_slider_box_batch`` sums the slides' own per-row box
 integrals scaled by the row's box widths.
 
+``eval_grid`` (extension) evaluates a tensor-product grid as a broadcast sum: every slide evaluates the small grid of
+its own group of dimensions (``d_s`` mode products) and ``k_slider_grid_sum`` writes ``pivot + sum_s (G_s - pivot)`` over
+the whole grid in one pass, in ``eval``'s order of operations (``pcx_slider_eval_tensor_grid``); a derivative inside one
+slide is that slide's grid broadcast, one across slides is ``+0.0``.
+
 Out of scope in this tier: plotting.
 """
 from __future__ import annotations
@@ -237,6 +242,19 @@ class ChebyshevSlider(ErgonomicsMixin, DerivativeIdMixin):
         _lib.check(s.lib.pcx_slider_eval_multi_batch(s.handle, _lib.p_f64(pts), pts.shape[0], _lib.p_i32(specs),
                                                      specs.shape[0], _lib.p_f64(out)), s.lib)
         return out
+
+    def eval_grid(self, axes, derivative_order=None, *, derivative_id=None, out=None):
+        """The slider on the tensor-product grid ``axes[0] x ... x axes[d-1]`` (extension; what the reference's
+        ``plot_2d_surface`` and a risk ladder over a high-dimensional book evaluate point by point):
+        ``result[i_0, ..., i_{d-1}] = eval([axes[0][i_0], ...], derivative_order)``, shape ``(m_0, ..., m_{d-1})``.
+
+        ``axes``, ``derivative_order`` / ``derivative_id`` and ``out`` as in ``ChebyshevApproximation.eval_grid``.
+        Every slide depends on its own group of dimensions only: each evaluates the small grid of its group and one
+        kernel writes ``pivot + sum_s (G_s - pivot)``, slides in order, over the whole grid
+        (``pcx_slider_eval_tensor_grid``).  A derivative inside one slide is that slide's derivative grid, broadcast
+        over the other dimensions; one that spans two slides or more is ``+0.0`` everywhere."""
+        from .barycentric import _composite_eval_grid
+        return _composite_eval_grid(self, "pcx_slider_eval_tensor_grid", axes, derivative_order, derivative_id, out)
 
     # ---------------------------------------------------------------- algebra
     # Reference slider.py:1285-1390: slide by slide on the host, pivot_value combined the same way.  The in-place

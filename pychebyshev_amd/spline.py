@@ -23,7 +23,11 @@ the one-row batch, or, above 64 nodes in a piece, the pieces' own calls merged o
 that contain the value and slices each on the device; ``extrude`` repeats every piece's tensor on the host.  ``+``, ``-``, ``*`` and ``/`` combine the pieces' value tensors on the host.
 ``integrate`` contracts each piece on the device and sums the pieces along the integrated dimensions;
 ``integrate_batch`` is the box integral with another box per row: one ``pcx_bary_box_batch`` launch per piece on the
-rows whose box reaches it.  Not provided: auto_knots.
+rows whose box reaches it.  ``eval_grid`` (extension) evaluates a tensor-product grid without routing a single point:
+the intervals of the axis entries split the grid into one sub-grid per piece, every piece that holds a point runs its own
+grid evaluation (``d`` mode products) into its block of a packed staging buffer, and ``k_spline_grid_place`` copies the
+blocks into the result (``pcx_spline_eval_tensor_grid``; the planner is ``csrc/spline_grid_plan.h``).  Not provided:
+auto_knots.
 """
 from __future__ import annotations
 
@@ -426,6 +430,20 @@ class ChebyshevSpline(ErgonomicsMixin, DerivativeIdMixin):
         _lib.check(s.lib.pcx_spline_eval_multi_batch_dev(s.handle, ctypes.c_void_p(dev_pts.ptr), n, _lib.p_i32(specs), m,
                                                          ctypes.c_void_p(out.ptr)), s.lib)
         return out
+
+    def eval_grid(self, axes, derivative_order=None, *, derivative_id=None, out=None):
+        """The spline on the tensor-product grid ``axes[0] x ... x axes[d-1]`` (extension; what the reference's
+        ``plot_1d`` / ``plot_2d_surface`` and a risk ladder over a kinked payoff evaluate point by point):
+        ``result[i_0, ..., i_{d-1}] = eval_batch(meshgrid)[...]``, shape ``(m_0, ..., m_{d-1})`` -- ``eval_batch``'s
+        rule, not ``eval``'s: a coordinate on a knot belongs to the right-hand piece, one outside the domain to the end
+        piece, and a derivative spec is not checked against the knots.
+
+        ``axes``, ``derivative_order`` / ``derivative_id`` and ``out`` as in ``ChebyshevApproximation.eval_grid``.
+        Piece routing is separable per dimension, so the grid falls apart into one sub-grid per piece: every piece
+        that holds a grid point evaluates its own small tensor grid (``d`` mode products) and one kernel places the
+        blocks into the result (``pcx_spline_eval_tensor_grid``); no point is routed, counted or bucketed."""
+        from .barycentric import _composite_eval_grid
+        return _composite_eval_grid(self, "pcx_spline_eval_tensor_grid", axes, derivative_order, derivative_id, out)
 
     def piece_indices(self, points) -> np.ndarray:
         """Flat piece index of every point, computed on the device (diagnostic)."""
