@@ -464,6 +464,41 @@ int pcx_slider_calculus_batch(pcx_slider *h, int dim, const double *lo, const do
 int pcx_spline_calculus_batch(pcx_spline *h, int dim, const double *lo, const double *hi, const double *fixed, int64_t N,
                               int mode, double *roots_out, int32_t *counts_out, double *val_out, double *loc_out);
 
+/* ---- solutions of p = target along one dimension, a target per row ----------- */
+/* The entries above with `targets` (N host doubles, one per row) and a method:
+ *   method 0   all roots of p - targets[r]: the row's target is subtracted from its fibre on the device, one rounding per
+ *              value, and the solver of mode 0 runs on the result; roots_out / counts_out as in mode 0 (the spline's
+ *              widths and merge included), bit for bit what pcx_cheb1d_calculus returns on values - targets[:, None]
+ *   method 1   bracketed inversion, one lane per fibre: on the knots [lo, nodes..., hi] a segment brackets when the
+ *              value at its lower knot equals the target or p - target changes sign across it (a value equal to the
+ *              target at hi counts as one more).  status_out (N) = the number of bracketing segments: 0 not reached on
+ *              the knots (x NaN), 1 unique on the knots, > 1 not unique (x the lowest), -1 when the fibre or the target
+ *              is not finite or the fixed iteration cap was reached (x NaN).  x_out (N) = the knot itself where the
+ *              value equals the target there, else the root inside the lowest bracketing segment, found without leaving
+ *              it, down to adjacent doubles (to within 2^-10 eps max(|lo|, |hi|) where the root is closer to 0 than
+ *              2^-9 max(|lo|, |hi|)).  Two solutions between two neighbouring knots are not seen; method 0 finds
+ *              them.  A spline solves every piece along `dim` on its own interval and nodes: x is the lowest over the
+ *              pieces with status > 0, status the sum of the pieces' (a solution exactly on an interior knot is counted
+ *              by both pieces that find it), -1 when any piece is -1.
+ * The outputs of the other method may be NULL.  Checked before any launch, each PCX_ERR_INVALID: everything the
+ * calculus entries check, n outside [1, 64], a method other than 0 or 1, NULL targets with N > 0, NULL outputs of the
+ * method.  A target that is not finite is not an argument error: its row gets status -1 (method 1) or, its fibre no
+ * longer being finite, counts -1 (method 0).  N = 0 returns PCX_OK and touches no output.                             */
+int pcx_cheb1d_solve(int device, int n, double lo, double hi, const double *nodes, const double *weights,
+                     const double *values, const double *targets, int64_t N, int method, double *roots_out,
+                     int32_t *counts_out, double *x_out, int32_t *status_out);
+int pcx_bary_solve_batch(pcx_bary *h, int dim, const double *lo, const double *hi, const double *fixed,
+                         const double *targets, int64_t N, int method, double *roots_out, int32_t *counts_out,
+                         double *x_out, int32_t *status_out);
+int pcx_tt_solve_batch(pcx_tt *h, int dim, const double *fixed, const double *targets, int64_t N, int method,
+                       double *roots_out, int32_t *counts_out, double *x_out, int32_t *status_out);
+int pcx_slider_solve_batch(pcx_slider *h, int dim, const double *lo, const double *hi, const double *fixed,
+                           const double *targets, int64_t N, int method, double *roots_out, int32_t *counts_out,
+                           double *x_out, int32_t *status_out);
+int pcx_spline_solve_batch(pcx_spline *h, int dim, const double *lo, const double *hi, const double *fixed,
+                           const double *targets, int64_t N, int method, double *roots_out, int32_t *counts_out,
+                           double *x_out, int32_t *status_out);
+
 /* ---- TT-Cross build steps (tensor_train.py:123-540) ------------------------- */
 /* One unfolding step of _tt_cross (:332-362 and :449-474): thin SVD of the m x c cross
  * matrix C (row-major), rank = max(1, min(cap, #{S > rel_thresh*S0}, min(m,c))), maxvol

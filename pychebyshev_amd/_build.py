@@ -41,7 +41,7 @@ SOURCES = {
     "pcx_ttbuild.hip": HOST_H + ["ttcross_kernels.h", "ttsvd_kernels.h", "tt_round_kernels.h"],
     "pcx_tt_als.hip": HOST_H + ["tt_als_kernels.h"],
     "pcx_calculus.hip": BARY_H + ["pcx_slider_internal.h", "pcx_spline_internal.h", "gather_kernels.h",
-                         "calculus_kernels.h", "slider_calc_kernels.h", "spline_calc_kernels.h"],
+                         "calculus_kernels.h", "slider_calc_kernels.h", "spline_calc_kernels.h", "invert_kernels.h"],
     "pcx_comm.hip": [PCX_H],
 }
 OBJ_DIR = os.path.join(HERE, "_obj")

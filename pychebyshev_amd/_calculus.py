@@ -5,6 +5,10 @@ Every fibre of at most :data:`MAX_DEVICE_N` nodes is solved on the device (``pcx
 ``csrc/calculus_kernels.h``).  Longer fibres still come from the device, and the single calls then finish here with
 :func:`roots_1d` / :func:`optimize_1d`, NumPy's ``chebroots`` on the coefficients of
 ``ChebyshevApproximation._chebyshev_coefficients_1d``; the batch calls refuse them.
+
+With a target per row (``pcx_*_solve_batch``): ``roots(level=)`` / ``roots_batch(level=)`` subtract the row's level from
+its fibre on the device before the same solver, and ``invert_batch`` solves one bracketed scalar equation per fibre, a
+device lane each (``csrc/invert_kernels.h``); :func:`invert_rows` / :func:`invert_1d` restate that routine in NumPy.
 """
 from __future__ import annotations
 
@@ -73,6 +77,87 @@ def validate_batch_args(ndim: int, dim, fixed, domain, n_nodes) -> np.ndarray:
             r = int(bad[0])
             raise ValueError(f"Fixed value {rows[r, c]} for dim {k} outside domain [{lo}, {hi}] (row {r})")
     return rows
+
+
+def validate_targets(targets, N: int, name: str = "targets") -> np.ndarray:
+    """The ``(N,)`` float64 targets of an ``invert_batch`` call (a scalar serves every row), checked on the host before
+    any launch: one finite value per row."""
+    t = np.asarray(targets, dtype=np.float64)
+    if t.ndim == 0:
+        t = np.full(N, float(t))
+    if t.shape != (N,):
+        raise ValueError(f"{name} must be a scalar or have shape ({N},), got {t.shape}")
+    bad = np.nonzero(~np.isfinite(t))[0]
+    if bad.size:
+        r = int(bad[0])
+        raise ValueError(f"{name} must be finite, got {t[r]} (row {r})")
+    return np.ascontiguousarray(t)
+
+
+def validate_level(level, N: int):
+    """The ``level=`` keyword of ``roots`` / ``roots_batch``: None for ``None`` and for the scalar 0.0 (today's path,
+    the same launches and bits), else the ``(N,)`` finite float64 levels."""
+    if level is None:
+        return None
+    if np.ndim(level) == 0 and not isinstance(level, (bool, np.bool_)):
+        lv = float(level)
+        if lv == 0.0:
+            return None
+    return validate_targets(level, N, "level")
+
+
+def run_solve(call, lib, n: int, N: int, method: int, width: int | None = None):
+    """Run one ``pcx_*_solve_batch`` entry (``call(roots, counts, x, status)`` -> rc) and shape its outputs: method 0
+    ``(roots (N, max(n-1, 1)), counts)`` as :func:`run_batch`, method 1 ``(x (N,) float64, status (N,) int32)``."""
+    if method == 0:
+        W = max(n - 1, 1) if width is None else int(width)
+        roots, counts = np.empty((N, W)), np.empty(N, dtype=np.int32)
+        _lib.check(call(_lib.p_f64(roots), _lib.p_i32(counts), None, None), lib)
+        return roots, counts
+    x, status = np.empty(N), np.empty(N, dtype=np.int32)
+    _lib.check(call(None, None, _lib.p_f64(x), _lib.p_i32(status)), lib)
+    return x, status
+
+
+def _cheb1d_solve(values, targets, nodes, weights, domain, method: int, device):
+    lib = _lib.load()
+    v = _lib.f64(np.atleast_2d(values))
+    N, n = v.shape
+    t = _lib.f64(np.broadcast_to(np.asarray(targets, dtype=np.float64), (N,)))
+    nd, wt = _lib.f64(nodes), _lib.f64(weights)
+    dev = _lib.default_device() if device is None else int(device)
+
+    def call(r, c, x, s):
+        return lib.pcx_cheb1d_solve(dev, n, float(domain[0]), float(domain[1]), _lib.p_f64(nd), _lib.p_f64(wt),
+                                    _lib.p_f64(v), _lib.p_f64(t), N, method, r, c, x, s)
+    return run_solve(call, lib, n, N, method)
+
+
+def cheb1d_level_roots(values, levels, nodes, weights, domain, device: int | None = None):
+    """``pcx_cheb1d_solve``, method 0, on given fibres: ``(roots, counts)`` of ``values - levels[:, None]``, the
+    subtraction made on the device."""
+    return _cheb1d_solve(values, levels, nodes, weights, domain, 0, device)
+
+
+def cheb1d_invert(values, targets, nodes, weights, domain, device: int | None = None):
+    """``pcx_cheb1d_solve``, method 1, on given fibres: ``values`` (N, n) at the ascending ``nodes`` of ``domain``,
+    one target per row -> ``(x (N,), status (N,))`` as :func:`invert_1d` defines them."""
+    return _cheb1d_solve(values, targets, nodes, weights, domain, 1, device)
+
+
+def merge_inversions(x, status):
+    """Join the inversions of the pieces of a spline along one dimension (the NumPy restatement of
+    ``k_spline_invert_merge``): ``x`` and ``status`` are ``(P, N)``, piece by piece in order.  The lowest ``x`` of the
+    pieces with ``status > 0`` and the sum of their statuses; a -1 in any piece makes the row -1 and NaN; no piece
+    with a solution gives ``(NaN, 0)``."""
+    x, status = np.atleast_2d(np.asarray(x, dtype=float)), np.atleast_2d(np.asarray(status))
+    found = status > 0
+    out_s = np.where(found, status, 0).sum(axis=0).astype(np.int32)
+    with np.errstate(invalid="ignore"):
+        out_x = np.where(found, x, np.inf).min(axis=0)
+    out_x = np.where(out_s > 0, out_x, np.nan)
+    failed = (status < 0).any(axis=0)
+    return np.where(failed, np.nan, out_x), np.where(failed, np.int32(-1), out_s).astype(np.int32)
 
 
 def run_batch(call, lib, n: int, N: int, mode: int, width: int | None = None):
@@ -190,6 +275,135 @@ def optimize_1d(values, nodes, weights, diff, domain, mode: str = "min"):
     return float(vals[idx]), float(cand[idx])
 
 
+INVERT_MAX_ITERS = 192       # INV_MAX_ITERS of csrc/invert_kernels.h: 3 steps per halving, 63 halvings to the floor
+INVERT_FLOOR = 2.0 ** -10    # INV_FLOOR: the bracket stops at INVERT_FLOOR eps max(|lo|, |hi|)
+
+
+def _bary_rows(V, nodes, weights, x):
+    """p_r(x_r) for the rows of ``V`` (R, n): the barycentric formula as ``inv_eval`` forms it -- a sequential sum over
+    j = 0 .. n-1, the first node within 1e-14 gives its value.  Vectorised over rows only, so every row sees the
+    operations of the scalar routine in their order."""
+    R, n = V.shape
+    num, den = np.zeros(R), np.zeros(R)
+    exact = np.full(R, -1)
+    for j in range(n):
+        dx = x - nodes[j]
+        hit = np.abs(dx) < 1e-14
+        exact = np.where(hit & (exact < 0), j, exact)
+        t = weights[j] / np.where(hit, 1.0, dx)
+        num = np.where(hit, num, num + t * V[:, j])
+        den = np.where(hit, den, den + t)
+    return np.where(exact >= 0, V[np.arange(R), np.maximum(exact, 0)], num / den)
+
+
+def invert_rows(values, nodes, weights, domain, targets, return_iterations: bool = False):
+    """The NumPy restatement of ``inv_solve`` (``csrc/invert_kernels.h``) on the rows of ``values`` (R, n), one target
+    per row -> ``(x (R,) float64, status (R,) int32)``, and the evaluations each row spent inside its bracket when
+    ``return_iterations``.  Every row goes through the scalar routine's operations in their order (explicit sequential
+    sums; rows are independent lanes of the vector statements), so ``status`` and ``x`` are the device's.
+
+    Knots ``s_0 = lo, s_1 .. s_n`` the ascending nodes, ``s_(n+1) = hi``; ``g_i = p(s_i) - t`` (the values themselves
+    at the nodes).  Segment ``i`` brackets when ``g_i == 0`` or ``g_i`` and ``g_(i+1)`` have opposite signs; a
+    ``g_(n+1) == 0`` counts as one more.  ``status`` is the number of bracketing segments (0: the target is not
+    reached on the knots, ``x`` NaN; > 1: ``x`` is the lowest), -1 with ``x`` NaN when the fibre or the target is not
+    finite or the iteration cap :data:`INVERT_MAX_ITERS` was reached.  ``x = s_i`` exactly when ``g_i == 0``, else the
+    root inside the lowest bracketing segment: Illinois secant steps kept ``4 eps max(|a|, |b|)`` inside the bracket,
+    a midpoint when the bracket is narrower than twice that or two steps in a row failed to halve it, until
+    ``g(x) == 0`` or the bracket's ends are adjacent doubles (then the end with the smaller ``|g|``).  Stop and
+    distance carry the floor ``flo = INVERT_FLOOR eps max(|lo|, |hi|)``: the bracket also stops at ``b - a <= flo``, so
+    a root at or near 0 in a domain that contains 0 does not ask for a bracket down to the subnormals; a root with
+    ``|x| >= 2^-9 max(|lo|, |hi|)`` still ends at adjacent doubles.  A constant fibre equal to its target gives
+    ``status = n + 2`` and ``x = lo`` when the barycentric sums at the two ends return the constant itself (a power of
+    two or zero; another constant may round there, and status is then n to n + 2 with ``x = lo`` or the first node)."""
+    V = np.atleast_2d(np.asarray(values, dtype=float))
+    R, n = V.shape
+    nodes, weights = np.asarray(nodes, dtype=float), np.asarray(weights, dtype=float)
+    t = np.broadcast_to(np.asarray(targets, dtype=float), (R,)).copy()
+    lo, hi = float(domain[0]), float(domain[1])
+    eps = float(np.finfo(float).eps)
+    flo = INVERT_FLOOR * eps * max(abs(lo), abs(hi))
+    x_out = np.full(R, np.nan)
+    iters = np.zeros(R, dtype=np.int32)
+    with np.errstate(all="ignore"):
+        finite = np.isfinite(t) & np.isfinite(V).all(axis=1)
+        count = np.zeros(R, dtype=np.int32)
+        exact = np.zeros(R, dtype=bool)
+        a, b, ga, gb = np.zeros(R), np.zeros(R), np.zeros(R), np.zeros(R)
+        sp, gp = np.full(R, lo), _bary_rows(V, nodes, weights, np.full(R, lo)) - t
+        for i in range(n + 1):
+            sn = np.full(R, nodes[i] if i < n else hi)
+            gn = V[:, i] - t if i < n else _bary_rows(V, nodes, weights, np.full(R, hi)) - t
+            zero = gp == 0.0
+            br = zero | ((gp < 0.0) & (gn > 0.0)) | ((gp > 0.0) & (gn < 0.0))
+            first = br & (count == 0)
+            a, b, ga, gb = np.where(first, sp, a), np.where(first, sn, b), np.where(first, gp, ga), np.where(first, gn, gb)
+            exact = np.where(first, zero, exact)
+            count = count + br
+            sp, gp = sn, gn
+        endz = gp == 0.0
+        first = endz & (count == 0)
+        a = np.where(first, sp, a)
+        exact = np.where(first, True, exact)
+        count = count + endz
+        status = np.where(finite, count, -1).astype(np.int32)
+        found = finite & (count > 0)
+        x_out = np.where(found & exact, a, x_out)
+        idx = np.nonzero(found & ~exact)[0]
+        if idx.size:
+            Vi, ti = V[idx], t[idx]
+            a, b, ga, gb = a[idx], b[idx], ga[idx], gb[idx]
+            fa, fb = ga.copy(), gb.copy()
+            side, slow, creep = (np.zeros(idx.size, dtype=int) for _ in range(3))
+            live = np.ones(idx.size, dtype=bool)
+            xo, its = np.full(idx.size, np.nan), np.zeros(idx.size, dtype=np.int32)
+            for _ in range(INVERT_MAX_ITERS):
+                if not live.any():
+                    break
+                w = b - a
+                m = a + 0.5 * w
+                adj = live & (~((a < m) & (m < b)) | ~(w > flo))
+                xo = np.where(adj, np.where(np.abs(ga) <= np.abs(gb), a, b), xo)
+                live = live & ~adj
+                tol = np.ldexp(np.maximum(4.0 * eps * np.maximum(np.abs(a), np.abs(b)), flo), creep)
+                xc = b - fb * (w / (fb - fa))
+                bis = (slow >= 2) | ~(w > 2.0 * tol)
+                near_a, near_b = ~(xc > a + tol), ~(xc < b - tol)
+                xc = np.where(near_a, a + tol, xc)
+                near_b = near_b & ~near_a
+                xc = np.where(near_b, b - tol, xc)
+                inside = (a < xc) & (xc < b)
+                xn = np.where(bis | ~inside, m, xc)
+                pushed = np.where(bis | ~inside, 0, np.where(near_a, -1, np.where(near_b, 1, 0)))
+                slow = np.where(bis, 0, slow)
+                gx = _bary_rows(Vi, nodes, weights, xn) - ti
+                its = its + live
+                hit = live & (gx == 0.0)
+                xo = np.where(hit, xn, xo)
+                live = live & ~hit
+                left = live & ((gx < 0.0) == (ga < 0.0))
+                right = live & ~left
+                fb = np.where(left & (side == -1), fb * 0.5, fb)
+                fa = np.where(right & (side == 1), fa * 0.5, fa)
+                a, ga, fa = np.where(left, xn, a), np.where(left, gx, ga), np.where(left, gx, fa)
+                b, gb, fb = np.where(right, xn, b), np.where(right, gx, gb), np.where(right, gx, fb)
+                side = np.where(left, -1, np.where(right, 1, side))
+                crept = (left & (pushed == -1)) | (right & (pushed == 1))
+                creep = np.where(live, np.where(crept, creep + 1, np.where(pushed == 0, creep, 0)), creep)
+                slow = np.where(live, np.where((b - a) > 0.5 * w, slow + 1, 0), slow)
+            x_out[idx] = np.where(live, np.nan, xo)
+            status[idx] = np.where(live, -1, status[idx])
+            iters[idx] = its
+    if return_iterations:
+        return x_out, status, iters
+    return x_out, status
+
+
+def invert_1d(values, nodes, weights, domain, target):
+    """One fibre: ``(x, status)`` of :func:`invert_rows` as a float and an int."""
+    x, status = invert_rows(np.asarray(values, dtype=float)[None, :], nodes, weights, domain, [target])
+    return float(x[0]), int(status[0])
+
+
 def fibre_points(ndim: int, dim: int, row: np.ndarray, nodes) -> np.ndarray:
     """The n points ``(fixed..., x_j)`` of one fibre, columns in dimension order."""
     nodes = np.asarray(nodes, dtype=float)
@@ -209,6 +423,14 @@ def run_single(fibre_fn, batch_fn, n: int, mode: str, nodes, weights, diff, doma
     if mode == "roots":
         return roots_1d(values, domain)
     return optimize_1d(values, nodes, weights, diff, domain, mode)
+
+
+def run_single_level(fibre_fn, solve_fn, n: int, level: np.ndarray, domain):
+    """``roots(level=)`` as a single call: the one-row ``pcx_*_solve_batch`` (``solve_fn()``, method 0) up to
+    :data:`MAX_DEVICE_N` nodes, else the host restatement on the device-evaluated fibre minus the level."""
+    if n <= MAX_DEVICE_N:
+        return single_roots(*solve_fn())
+    return roots_1d(np.asarray(fibre_fn(), dtype=float) - float(level[0]), domain)
 
 
 # ---------------------------------------------------------------------------------------------- box integrals

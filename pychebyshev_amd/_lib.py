@@ -85,6 +85,9 @@ SIGNATURES = {
     "pcx_cheb1d_calculus": (_I, [_I, _I, _D, _D, c_f64p, c_f64p, c_f64p, c_f64p, _L, _I, c_f64p, c_i32p, c_f64p, c_f64p]),
     "pcx_bary_calculus_batch": (_I, [_V, _I, c_f64p, c_f64p, c_f64p, _L, _I, c_f64p, c_i32p, c_f64p, c_f64p]),
     "pcx_tt_calculus_batch": (_I, [_V, _I, c_f64p, _L, _I, c_f64p, c_i32p, c_f64p, c_f64p]),
+    "pcx_cheb1d_solve": (_I, [_I, _I, _D, _D, c_f64p, c_f64p, c_f64p, c_f64p, _L, _I, c_f64p, c_i32p, c_f64p, c_i32p]),
+    "pcx_bary_solve_batch": (_I, [_V, _I, c_f64p, c_f64p, c_f64p, c_f64p, _L, _I, c_f64p, c_i32p, c_f64p, c_i32p]),
+    "pcx_tt_solve_batch": (_I, [_V, _I, c_f64p, c_f64p, _L, _I, c_f64p, c_i32p, c_f64p, c_i32p]),
     "pcx_tensor_contract_axis": (_I, [_I, _I, c_i32p, c_f64p, _I, c_f64p, c_f64p]),
     "pcx_tensor_mode_product": (_I, [_I, _L, _I, _L, c_f64p, _I, c_f64p, c_f64p, _I]),
     "pcx_bary_eval_tensor_grid": (_I, [_V, c_i32p, c_i32p, c_f64p, c_f64p]),
@@ -109,6 +112,7 @@ SIGNATURES = {
     "pcx_spline_eval_batch_dev": (_I, [_V, _V, _L, c_i32p, _V]),
     "pcx_spline_eval_multi_batch_dev": (_I, [_V, _V, _L, c_i32p, _I, _V]),
     "pcx_spline_calculus_batch": (_I, [_V, _I, c_f64p, c_f64p, c_f64p, _L, _I, c_f64p, c_i32p, c_f64p, c_f64p]),
+    "pcx_spline_solve_batch": (_I, [_V, _I, c_f64p, c_f64p, c_f64p, c_f64p, _L, _I, c_f64p, c_i32p, c_f64p, c_i32p]),
     "pcx_spline_eval_tensor_grid": (_I, [_V, c_i32p, c_i32p, c_f64p, c_f64p]),
     "pcx_spline_eval_tensor_grid_dev": (_I, [_V, c_i32p, c_i32p, c_f64p, _V, _V]),
     "pcx_slider_eval_tensor_grid": (_I, [_V, c_i32p, c_i32p, c_f64p, c_f64p]),
@@ -119,6 +123,7 @@ SIGNATURES = {
     "pcx_slider_eval_multi_batch": (_I, [_V, c_f64p, _L, c_i32p, _I, c_f64p]),
     "pcx_slider_eval_multi_batch_dev": (_I, [_V, _V, _L, c_i32p, _I, _V]),
     "pcx_slider_calculus_batch": (_I, [_V, _I, c_f64p, c_f64p, c_f64p, _L, _I, c_f64p, c_i32p, c_f64p, c_f64p]),
+    "pcx_slider_solve_batch": (_I, [_V, _I, c_f64p, c_f64p, c_f64p, c_f64p, _L, _I, c_f64p, c_i32p, c_f64p, c_i32p]),
     "pcx_slider_box_batch": (_I, [_V, c_i32p, c_f64p, c_f64p, c_f64p, _L, c_f64p]),
     "pcx_slider_box_batch_dev": (_I, [_V, c_i32p, c_f64p, c_f64p, _V, _L, _V]),
     "pcx_tt_create": (_I, [_I, _I, c_i32p, c_i32p, c_f64p, c_f64p, c_f64p, c_i32p, c_vpp]),

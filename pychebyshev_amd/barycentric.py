@@ -1174,15 +1174,49 @@ class ChebyshevApproximation(ErgonomicsMixin, DerivativeIdMixin):
             lambda m: self._calculus_batch(dim, row, m), n, mode, self.nodes[dim], self.weights[dim],
             self.diff_matrices[dim], (self.domain[dim][0], self.domain[dim][1]))
 
-    def roots(self, dim=None, fixed=None) -> np.ndarray:
+    def _solve_batch(self, dim: int, rows: np.ndarray, targets: np.ndarray, method: int):
+        """``pcx_bary_solve_batch`` over validated rows and targets (see :func:`pychebyshev_amd._calculus.run_solve`)."""
+        from . import _calculus
+        m = self._model()
+        lo = _lib.f64([float(b[0]) for b in self.domain])
+        hi = _lib.f64([float(b[1]) for b in self.domain])
+        rows, targets = _lib.f64(rows), _lib.f64(targets)
+        N = rows.shape[0]
+
+        def call(r, c, x, s):
+            return m.lib.pcx_bary_solve_batch(m.handle, int(dim), _lib.p_f64(lo), _lib.p_f64(hi), _lib.p_f64(rows),
+                                              _lib.p_f64(targets), N, method, r, c, x, s)
+        return _calculus.run_solve(call, m.lib, int(self.n_nodes[dim]), N, method)
+
+    def _level_roots(self, dim, fixed, level: np.ndarray) -> np.ndarray:
+        from . import _calculus
+        if self.tensor_values is None:
+            raise RuntimeError("Call build() first")
+        d = self.num_dimensions
+        dim, params = _calculus.validate_calculus_args(d, dim, fixed, self.domain)
+        row = _calculus.fixed_row(d, dim, params)
+        return _calculus.run_single_level(
+            lambda: self.vectorized_eval_batch(_calculus.fibre_points(d, dim, row, self.nodes[dim]), [0] * d),
+            lambda: self._solve_batch(dim, row, level, 0), int(self.n_nodes[dim]), level,
+            (self.domain[dim][0], self.domain[dim][1]))
+
+    def roots(self, dim=None, fixed=None, *, level=0.0) -> np.ndarray:
         """Sorted real roots along ``dim`` with every other dimension fixed (``fixed = {dim_index: value}``) by the
         colleague-matrix method (reference barycentric.py:2277-2327, _calculus.py:198-244).  The fibre is evaluated
         and solved on the device; above 64 nodes the solve runs on the host (NumPy ``chebroots``).  A non-finite
         fibre raises ``numpy.linalg.LinAlgError``.  Unlike the reference, which clips from outside only, a root
         within ``1e-10`` (of the half-width) of an end of ``domain[dim]``, on either side of it, is returned as exactly
         that end; the batched forms and the critical points of :meth:`minimize` / :meth:`maximize` follow the same
-        rule."""
-        return self._calculus(dim, fixed, "roots")
+        rule.
+
+        ``level`` (keyword only, a finite scalar) asks for the solutions of ``p = level`` instead: the level is
+        subtracted from the fibre on the device, one rounding per value, before the same solver.  ``None`` or ``0.0``
+        is the call without a level, the same launches and bits."""
+        from . import _calculus
+        lv = _calculus.validate_level(level, 1)
+        if lv is None:
+            return self._calculus(dim, fixed, "roots")
+        return self._level_roots(dim, fixed, lv)
 
     def minimize(self, dim=None, fixed=None):
         """``(value, location)`` of the minimum along ``dim`` (reference barycentric.py:2329-2377): the roots of the
@@ -1200,13 +1234,39 @@ class ChebyshevApproximation(ErgonomicsMixin, DerivativeIdMixin):
             raise RuntimeError("Call build() first")
         return _calculus.validate_batch_args(self.num_dimensions, dim, fixed, self.domain, self.n_nodes)
 
-    def roots_batch(self, dim: int, fixed):
+    def roots_batch(self, dim: int, fixed, *, level=None):
         """Roots along ``dim`` for every row of ``fixed`` (host float64 ``(N, d-1)``: the other dimensions in
         increasing order), in one device pass (extension).  Returns ``(roots, counts)``: ``roots`` float64
         ``(N, max(n_dim-1, 1))`` ascending and NaN-padded, ``counts`` int32 ``(N,)``, -1 where the fibre was not finite
-        or the eigenvalue iteration failed.  At most 64 nodes along ``dim``."""
+        or the eigenvalue iteration failed.  At most 64 nodes along ``dim``.
+
+        ``level`` (keyword only, a finite scalar or an ``(N,)`` array, one level per row) asks for the solutions of ``p = level`` instead: the level is
+        subtracted from the fibre on the device, one rounding per value, before the same solver.  ``None`` or ``0.0``
+        is the call without a level, the same launches and bits."""
+        from . import _calculus
         rows = self._calculus_rows(dim, fixed)
-        return self._calculus_batch(int(dim), rows, 0)
+        lv = _calculus.validate_level(level, rows.shape[0])
+        if lv is None:
+            return self._calculus_batch(int(dim), rows, 0)
+        return self._solve_batch(int(dim), rows, lv, 0)
+
+    def invert_batch(self, dim: int, fixed, targets):
+        """The value of dimension ``dim`` at which the model equals each row's target (extension;
+        ``pcx_bary_solve_batch``, method 1): ``fixed`` as in :meth:`roots_batch`, ``targets`` a finite scalar or ``(N,)``
+        array.  Returns ``(x (N,) float64, status (N,) int32)``.  On the knots ``[lo, nodes..., hi]`` of the fibre
+        a segment brackets when the value at its lower knot equals the target or ``p - target`` changes sign across it;
+        ``status`` is the number of bracketing segments: ``0`` the target is not reached on the knots (``x`` NaN),
+        ``1`` unique on the knots, ``> 1`` not unique (``x`` is the lowest), ``-1`` the fibre is not finite or the
+        solver's fixed iteration cap was reached (``x`` NaN).  ``x`` is the knot itself where the value equals the
+        target there, else the root inside the lowest bracketing segment, down to adjacent doubles.  A constant fibre
+        equal to its target gives ``status = n + 2`` and ``x = lo`` when the sums at the two ends return the constant
+        itself (a power of two, zero), else n to n + 2.  A root closer to 0 than ``2^-9 max(|lo|, |hi|)`` is returned to
+        within ``2^-10 eps max(|lo|, |hi|)``, not to adjacent doubles.  Only crossings between knots are seen: two
+        solutions inside one node interval are invisible here, and ``roots_batch(level=)`` finds them.  At most 64
+        nodes along ``dim``.  One device lane solves one row (``csrc/invert_kernels.h``)."""
+        from . import _calculus
+        rows = self._calculus_rows(dim, fixed)
+        return self._solve_batch(int(dim), rows, _calculus.validate_targets(targets, rows.shape[0]), 1)
 
     def minimize_batch(self, dim: int, fixed):
         """``(values, locations)``, float64 ``(N,)``, of the minimum along ``dim`` for every row of ``fixed``

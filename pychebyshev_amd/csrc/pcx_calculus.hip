@@ -15,12 +15,18 @@
 // fibre points of all pieces go through the spline's own chunk evaluation (spline_eval_chunk: route, bucket, the pieces'
 // barycentric kernels), one launch solves the rows x P fibres (k_cheb1d_calculus_pieces, the same calc_row) and
 // k_spline_calc_merge joins the pieces of every row (spline_calc_kernels.h).
+//
+// The pcx_*_solve_batch entries run the same pipelines with a target per row (SolveReq): method 0 subtracts the row's
+// level from its fibre in HBM (k_calc_level, between the evaluation and the same solver launch: all roots at the level),
+// method 1 replaces the eigenvalue solver by the lane-per-fibre bracketed inversion of invert_kernels.h.  The
+// pcx_*_calculus_batch entries pass no request and launch exactly what they launched before.
 
 #include "pcx_slider_internal.h"
 #include "pcx_spline_internal.h"
 #include "calculus_kernels.h"
 #include "slider_calc_kernels.h"
 #include "spline_calc_kernels.h"
+#include "invert_kernels.h"
 
 // rows per pass of the expand / evaluate / solve pipeline: at most this many fibre points in flight
 static const long kCalcChunkPoints = 1L << 21;
@@ -77,6 +83,97 @@ static int calc_launch(const CalcArgs &a, long rows, hipStream_t st) {
     return PCX_OK;
 }
 
+// What a pcx_*_solve_batch entry asks for on top of the shared pipeline; the calculus entries pass none.
+struct SolveReq {
+    const double *targets;    // N levels (method 0) or targets (method 1), host
+    int method;               // 0 all roots at the level (outputs as mode 0), 1 bracketed inversion
+    double *x_out;            // N (method 1)
+    int32_t *status_out;      // N (method 1)
+};
+
+static int solve_check(int n, const SolveReq &sq, int64_t N, double lo, double hi, double *roots_out, int32_t *counts_out) {
+    if (n < 1 || n > PCX_INV_MAX_N)
+        return fail(PCX_ERR_INVALID, "n=%d outside [1, %d]: the device solvers take fibres of at most %d nodes", n,
+                    PCX_INV_MAX_N, PCX_INV_MAX_N);
+    if (sq.method < 0 || sq.method > 1) return fail(PCX_ERR_INVALID, "method=%d (0 roots at a level, 1 inversion)", sq.method);
+    if (N < 0) return fail(PCX_ERR_INVALID, "N=%lld < 0", (long long)N);
+    if (!(lo < hi)) return fail(PCX_ERR_INVALID, "domain: lo must be < hi");
+    if (N > 0 && !sq.targets) return fail(PCX_ERR_INVALID, "targets is NULL");
+    if (sq.method == 0 && !counts_out) return fail(PCX_ERR_INVALID, "counts_out is NULL");
+    if (sq.method == 0 && !roots_out) return fail(PCX_ERR_INVALID, "roots_out is NULL");
+    if (sq.method == 1 && (!sq.x_out || !sq.status_out)) return fail(PCX_ERR_INVALID, "x_out / status_out is NULL");
+    return PCX_OK;
+}
+
+// the argument check of an entry: calc_check without a request, solve_check with one
+static int calc_check_req(int n, int mode, int64_t N, double lo, double hi, const double *diff, double *roots_out,
+                          int32_t *counts_out, double *val_out, double *loc_out, const SolveReq *sq) {
+    if (sq) return solve_check(n, *sq, N, lo, hi, roots_out, counts_out);
+    return calc_check(n, mode, N, lo, hi, diff, roots_out, counts_out, val_out, loc_out);
+}
+
+// device side of a request: the targets of all N rows, and the outputs of method 1
+struct SolveDev {
+    DevBuf targets, x, status;
+    bool invert = false;
+    int alloc(const SolveReq *sq, long N) {
+        if (!sq) return PCX_OK;
+        invert = sq->method == 1;
+        int rc = targets.alloc((size_t)N * sizeof(double));
+        if (!rc && invert) rc = x.alloc((size_t)N * sizeof(double));
+        if (!rc && invert) rc = status.alloc((size_t)N * sizeof(int32_t));
+        return rc;
+    }
+    int upload(const SolveReq *sq, long N, hipStream_t st) {
+        if (sq) HIP_TRY(hipMemcpyAsync(targets.p, sq->targets, (size_t)N * sizeof(double), hipMemcpyHostToDevice, st));
+        return PCX_OK;
+    }
+    int download(const SolveReq *sq, long N, hipStream_t st) {
+        HIP_TRY(hipMemcpyAsync(sq->x_out, x.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(sq->status_out, status.p, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return PCX_OK;
+    }
+};
+
+// launch KERNEL<NP> with NP the fibre-length class of the inversion's LDS tile
+#define INV_DISPATCH(n, KERNEL, grid, st, ...)                                                   \
+    do {                                                                                         \
+        if ((n) <= 16) hipLaunchKernelGGL(KERNEL<16>, grid, dim3(64), 0, st, __VA_ARGS__);        \
+        else if ((n) <= 32) hipLaunchKernelGGL(KERNEL<32>, grid, dim3(64), 0, st, __VA_ARGS__);   \
+        else hipLaunchKernelGGL(KERNEL<64>, grid, dim3(64), 0, st, __VA_ARGS__);                  \
+    } while (0)
+
+// k_cheb1d_invert over a.rows fibres (pointers already offset to the first row): one lane per fibre, 64 per workgroup
+static int inv_launch(const InvArgs &a, hipStream_t st) {
+    if (a.rows <= 0) return PCX_OK;
+    const long blocks = (a.rows + 63) / 64;
+    if (blocks > 0x7fffffffL) return fail(PCX_ERR_UNSUPPORTED, "too many rows for one launch");
+    INV_DISPATCH(a.n, k_cheb1d_invert, dim3((unsigned)blocks), st, a);
+    HIP_TRY(hipGetLastError());
+    return PCX_OK;
+}
+
+// One pass of `rows` fibres of a request (vals and the outputs of `c` already offset to the pass, r0 its first row):
+// the inversion, or the level subtracted in place and the root solver
+static int solve_pass(const CalcArgs &c, double *vals, long rows, long r0, SolveDev &sd, hipStream_t st) {
+    const double *t = sd.targets.as<double>() + r0;
+    if (sd.invert) {
+        InvArgs ia{};
+        ia.n = c.n; ia.rows = rows; ia.lo = c.lo; ia.hi = c.hi; ia.nodes = c.nodes; ia.wts = c.wts;
+        ia.vals = vals; ia.targets = t;
+        ia.x = sd.x.as<double>() + r0;
+        ia.status = sd.status.as<int32_t>() + r0;
+        ia.iters = nullptr;
+        return inv_launch(ia, st);
+    }
+    const long total = rows * c.n;
+    hipLaunchKernelGGL(k_calc_level, dim3((unsigned)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, st, vals, t, rows,
+                       c.n);
+    HIP_TRY(hipGetLastError());
+    return calc_launch(c, rows, st);
+}
+
 // fixed rows (N x (d - 1), the columns of every dimension but `dim` in increasing order) inside [lo, hi] of their
 // dimensions; NaN passes, as in the reference's comparisons
 static int calc_check_fixed(const double *fixed, int64_t N, int d, int dim, const double *lo, const double *hi) {
@@ -95,17 +192,21 @@ static int calc_check_fixed(const double *fixed, int64_t N, int d, int dim, cons
 // The pipeline of the handle entries: per pass of rows, expand -> evaluate (eval(d_pts, points, d_vals)) -> solve.
 template <typename Eval>
 static int calc_fibres(int d, int dim, int mode, const double *fixed, int64_t N, CalcArgs a, hipStream_t st, Eval eval,
-                       double *roots_out, int32_t *counts_out, double *val_out, double *loc_out) {
+                       double *roots_out, int32_t *counts_out, double *val_out, double *loc_out,
+                       const SolveReq *sq = nullptr) {
     const int n = a.n;
     const long chunk = std::max<long>(1, std::min<long>(N, kCalcChunkPoints / n));
     DevBuf d_fixed, d_pts, d_vals;
     CalcDevOut out;
+    SolveDev sd;
     int rc = d_fixed.alloc((size_t)N * (d - 1) * sizeof(double));
     if (!rc) rc = d_pts.alloc((size_t)chunk * n * d * sizeof(double));
     if (!rc) rc = d_vals.alloc((size_t)chunk * n * sizeof(double));
-    if (!rc) rc = out.alloc(mode, N, a.W);
+    if (!rc) rc = sd.alloc(sq, N);
+    if (!rc && !sd.invert) rc = out.alloc(mode, N, a.W);
     if (rc) return rc;
     if (d > 1) HIP_TRY(hipMemcpyAsync(d_fixed.p, fixed, (size_t)N * (d - 1) * sizeof(double), hipMemcpyHostToDevice, st));
+    if ((rc = sd.upload(sq, N, st))) return rc;
     for (long r0 = 0; r0 < N; r0 += chunk) {
         const long rows = std::min<long>(chunk, N - r0);
         const long total = rows * n * d;
@@ -116,11 +217,14 @@ static int calc_fibres(int d, int dim, int mode, const double *fixed, int64_t N,
         if ((rc = eval(d_pts.as<double>(), rows * n, d_vals.as<double>()))) return rc;
         CalcArgs c = a;
         c.vals = d_vals.as<double>();
-        c.counts = out.counts.as<int32_t>() + r0;
-        if (mode == 0) c.roots = out.roots.as<double>() + (size_t)r0 * a.W;
-        else { c.val = out.val.as<double>() + r0; c.loc = out.loc.as<double>() + r0; }
-        if ((rc = calc_launch(c, rows, st))) return rc;
+        if (!sd.invert) {                                      // the inversion has its own outputs (SolveDev)
+            c.counts = out.counts.as<int32_t>() + r0;
+            if (mode == 0) c.roots = out.roots.as<double>() + (size_t)r0 * a.W;
+            else { c.val = out.val.as<double>() + r0; c.loc = out.loc.as<double>() + r0; }
+        }
+        if ((rc = sq ? solve_pass(c, d_vals.as<double>(), rows, r0, sd, st) : calc_launch(c, rows, st))) return rc;
     }
+    if (sd.invert) return sd.download(sq, N, st);
     return out.download(mode, N, a.W, roots_out, counts_out, val_out, loc_out, st);
 }
 
@@ -155,15 +259,49 @@ extern "C" int pcx_cheb1d_calculus(int device, int n, double lo, double hi, cons
     PCX_API_END
 }
 
-extern "C" int pcx_bary_calculus_batch(pcx_bary *h, int dim, const double *lo, const double *hi, const double *fixed,
-                                       int64_t N, int mode, double *roots_out, int32_t *counts_out, double *val_out,
-                                       double *loc_out) {
+// pcx_cheb1d_calculus with a target per row: method 0 solves values - targets[:, None] for all its roots, method 1 inverts
+extern "C" int pcx_cheb1d_solve(int device, int n, double lo, double hi, const double *nodes, const double *weights,
+                                const double *values, const double *targets, int64_t N, int method, double *roots_out,
+                                int32_t *counts_out, double *x_out, int32_t *status_out) {
     PCX_API_BEGIN
+    const SolveReq sq{targets, method, x_out, status_out};
+    int rc = solve_check(n, sq, N, lo, hi, roots_out, counts_out);
+    if (rc) return rc;
+    if (!nodes || !weights || (N > 0 && !values)) return fail(PCX_ERR_INVALID, "NULL argument");
+    if (N == 0) return PCX_OK;
+    if ((rc = use_device(device))) return rc;
+    const int W = std::max(n - 1, 1);
+    DevBuf d_grid, d_vals;                                     // nodes, weights in one buffer
+    CalcDevOut out;
+    SolveDev sd;
+    rc = d_grid.alloc((size_t)2 * n * sizeof(double));
+    if (!rc) rc = d_vals.alloc((size_t)N * n * sizeof(double));
+    if (!rc) rc = sd.alloc(&sq, N);
+    if (!rc && !sd.invert) rc = out.alloc(0, N, W);
+    if (rc) return rc;
+    double *g = d_grid.as<double>();
+    HIP_TRY(hipMemcpy(g, nodes, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(g + n, weights, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_vals.p, values, (size_t)N * n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(sd.targets.p, targets, (size_t)N * sizeof(double), hipMemcpyHostToDevice));
+    CalcArgs a{};
+    a.n = n; a.mode = 0; a.W = W; a.lo = lo; a.hi = hi;
+    a.nodes = g; a.wts = g + n; a.diff = nullptr; a.vals = d_vals.as<double>();
+    a.counts = out.counts.as<int32_t>();
+    a.roots = out.roots.as<double>();
+    if ((rc = solve_pass(a, d_vals.as<double>(), (long)N, 0, sd, nullptr))) return rc;
+    if (sd.invert) return sd.download(&sq, (long)N, nullptr);
+    return out.download(0, (long)N, W, roots_out, counts_out, nullptr, nullptr, nullptr);
+    PCX_API_END
+}
+
+static int bary_calc_impl(pcx_bary *h, int dim, const double *lo, const double *hi, const double *fixed, int64_t N, int mode,
+                          double *roots_out, int32_t *counts_out, double *val_out, double *loc_out, const SolveReq *sq) {
     if (!h || !lo || !hi) return fail(PCX_ERR_INVALID, "NULL argument");
     const int d = h->dims.d;
     if (dim < 0 || dim >= d) return fail(PCX_ERR_INVALID, "dim %d out of range [0, %d]", dim, d - 1);
     const int n = h->dims.n[dim];
-    int rc = calc_check(n, mode, N, lo[dim], hi[dim], h->d_diff, roots_out, counts_out, val_out, loc_out);
+    int rc = calc_check_req(n, mode, N, lo[dim], hi[dim], h->d_diff, roots_out, counts_out, val_out, loc_out, sq);
     if (!rc) rc = calc_check_fixed(fixed, N, d, dim, lo, hi);
     if (rc) return rc;
     if (N == 0) return PCX_OK;
@@ -180,13 +318,28 @@ extern "C" int pcx_bary_calculus_batch(pcx_bary *h, int dim, const double *lo, c
     auto eval = [&](const double *d_pts, long npts, double *d_vals) {
         return bary_launch(h, &dt, 1, dt->slot, d_pts, npts, d_vals, 1, 0, h->stream, &h->s_partial);
     };
-    return calc_fibres(d, dim, mode, fixed, N, a, h->stream, eval, roots_out, counts_out, val_out, loc_out);
+    return calc_fibres(d, dim, mode, fixed, N, a, h->stream, eval, roots_out, counts_out, val_out, loc_out, sq);
+}
+
+extern "C" int pcx_bary_calculus_batch(pcx_bary *h, int dim, const double *lo, const double *hi, const double *fixed,
+                                       int64_t N, int mode, double *roots_out, int32_t *counts_out, double *val_out,
+                                       double *loc_out) {
+    PCX_API_BEGIN
+    return bary_calc_impl(h, dim, lo, hi, fixed, N, mode, roots_out, counts_out, val_out, loc_out, nullptr);
     PCX_API_END
 }
 
-extern "C" int pcx_tt_calculus_batch(pcx_tt *h, int dim, const double *fixed, int64_t N, int mode, double *roots_out,
-                                     int32_t *counts_out, double *val_out, double *loc_out) {
+extern "C" int pcx_bary_solve_batch(pcx_bary *h, int dim, const double *lo, const double *hi, const double *fixed,
+                                    const double *targets, int64_t N, int method, double *roots_out, int32_t *counts_out,
+                                    double *x_out, int32_t *status_out) {
     PCX_API_BEGIN
+    const SolveReq sq{targets, method, x_out, status_out};
+    return bary_calc_impl(h, dim, lo, hi, fixed, N, 0, roots_out, counts_out, nullptr, nullptr, &sq);
+    PCX_API_END
+}
+
+static int tt_calc_impl(pcx_tt *h, int dim, const double *fixed, int64_t N, int mode, double *roots_out, int32_t *counts_out,
+                        double *val_out, double *loc_out, const SolveReq *sq) {
     int device = 0;
     TTDims dims{};
     hipStream_t st = nullptr;
@@ -226,7 +379,7 @@ extern "C" int pcx_tt_calculus_batch(pcx_tt *h, int dim, const double *fixed, in
         }
         D[(size_t)i * n + i] = -s;
     }
-    rc = calc_check(n, mode, N, lo[dim], hi[dim], D, roots_out, counts_out, val_out, loc_out);
+    rc = calc_check_req(n, mode, N, lo[dim], hi[dim], D, roots_out, counts_out, val_out, loc_out, sq);
     if (!rc) rc = calc_check_fixed(fixed, N, d, dim, lo, hi);
     if (rc) return rc;
     if (N == 0) return PCX_OK;
@@ -242,9 +395,23 @@ extern "C" int pcx_tt_calculus_batch(pcx_tt *h, int dim, const double *fixed, in
     auto eval = [&](const double *d_pts, long npts, double *d_vals) {
         return pcx_tt_eval_batch_dev(h, d_pts, npts, d_vals, (void *)st);   // points in the user's column order
     };
-    rc = calc_fibres(d, dim, mode, fixed, N, a, st, eval, roots_out, counts_out, val_out, loc_out);
+    rc = calc_fibres(d, dim, mode, fixed, N, a, st, eval, roots_out, counts_out, val_out, loc_out, sq);
     (void)hipStreamSynchronize(st);                            // d_grid is freed on return
     return rc;
+}
+
+extern "C" int pcx_tt_calculus_batch(pcx_tt *h, int dim, const double *fixed, int64_t N, int mode, double *roots_out,
+                                     int32_t *counts_out, double *val_out, double *loc_out) {
+    PCX_API_BEGIN
+    return tt_calc_impl(h, dim, fixed, N, mode, roots_out, counts_out, val_out, loc_out, nullptr);
+    PCX_API_END
+}
+
+extern "C" int pcx_tt_solve_batch(pcx_tt *h, int dim, const double *fixed, const double *targets, int64_t N, int method,
+                                  double *roots_out, int32_t *counts_out, double *x_out, int32_t *status_out) {
+    PCX_API_BEGIN
+    const SolveReq sq{targets, method, x_out, status_out};
+    return tt_calc_impl(h, dim, fixed, N, 0, roots_out, counts_out, nullptr, nullptr, &sq);
     PCX_API_END
 }
 
@@ -257,10 +424,9 @@ static SliderCols slider_fixed_cols(const int *dims, int nc, int dim) {
     return c;
 }
 
-extern "C" int pcx_slider_calculus_batch(pcx_slider *h, int dim, const double *lo, const double *hi, const double *fixed,
-                                         int64_t N, int mode, double *roots_out, int32_t *counts_out, double *val_out,
-                                         double *loc_out) {
-    PCX_API_BEGIN
+static int slider_calc_impl(pcx_slider *h, int dim, const double *lo, const double *hi, const double *fixed, int64_t N,
+                            int mode, double *roots_out, int32_t *counts_out, double *val_out, double *loc_out,
+                            const SolveReq *sq) {
     if (!h || !lo || !hi) return fail(PCX_ERR_INVALID, "NULL argument");
     const int d = h->d;
     if (dim < 0 || dim >= d) return fail(PCX_ERR_INVALID, "dim %d out of range [0, %d]", dim, d - 1);
@@ -271,7 +437,7 @@ extern "C" int pcx_slider_calculus_batch(pcx_slider *h, int dim, const double *l
     while (oc.col[lk] != dim) ++lk;
     const int g = oc.nc;
     const int n = po->dims.n[lk];
-    int rc = calc_check(n, mode, N, lo[dim], hi[dim], po->d_diff, roots_out, counts_out, val_out, loc_out);
+    int rc = calc_check_req(n, mode, N, lo[dim], hi[dim], po->d_diff, roots_out, counts_out, val_out, loc_out, sq);
     if (!rc) rc = calc_check_fixed(fixed, N, d, dim, lo, hi);
     if (rc) return rc;
     if (N == 0) return PCX_OK;
@@ -290,13 +456,16 @@ extern "C" int pcx_slider_calculus_batch(pcx_slider *h, int dim, const double *l
     const size_t cols_doubles = std::max<size_t>((size_t)chunk * h->max_cols, own_cols + (g > 1 ? (size_t)chunk * n * g : 0));
     DevBuf d_fixed, d_vals;
     CalcDevOut out;
+    SolveDev sd;
     rc = h->s_cols.reserve(cols_doubles * sizeof(double));
     if (!rc) rc = h->s_vals.reserve((size_t)chunk * ns * sizeof(double));
     if (!rc) rc = d_fixed.alloc((size_t)N * (d - 1) * sizeof(double));
     if (!rc) rc = d_vals.alloc((size_t)chunk * n * sizeof(double));
-    if (!rc) rc = out.alloc(mode, N, a.W);
+    if (!rc) rc = sd.alloc(sq, N);
+    if (!rc && !sd.invert) rc = out.alloc(mode, N, a.W);
     if (rc) return rc;
     if (d > 1) HIP_TRY(hipMemcpyAsync(d_fixed.p, fixed, (size_t)N * (d - 1) * sizeof(double), hipMemcpyHostToDevice, st));
+    if ((rc = sd.upload(sq, N, st))) return rc;
     double *cols = (double *)h->s_cols.ptr, *svals = (double *)h->s_vals.ptr, *vals = d_vals.as<double>();
     for (long r0 = 0; r0 < N; r0 += chunk) {
         const long rows = std::min<long>(chunk, N - r0);
@@ -345,19 +514,37 @@ extern "C" int pcx_slider_calculus_batch(pcx_slider *h, int dim, const double *l
         }
         CalcArgs c = a;
         c.vals = vals;
-        c.counts = out.counts.as<int32_t>() + r0;
-        if (mode == 0) c.roots = out.roots.as<double>() + (size_t)r0 * a.W;
-        else { c.val = out.val.as<double>() + r0; c.loc = out.loc.as<double>() + r0; }
-        if ((rc = calc_launch(c, rows, st))) return rc;
+        if (!sd.invert) {                                      // the inversion has its own outputs (SolveDev)
+            c.counts = out.counts.as<int32_t>() + r0;
+            if (mode == 0) c.roots = out.roots.as<double>() + (size_t)r0 * a.W;
+            else { c.val = out.val.as<double>() + r0; c.loc = out.loc.as<double>() + r0; }
+        }
+        if ((rc = sq ? solve_pass(c, vals, rows, r0, sd, st) : calc_launch(c, rows, st))) return rc;
     }
+    if (sd.invert) return sd.download(sq, N, st);
     return out.download(mode, N, a.W, roots_out, counts_out, val_out, loc_out, st);
-    PCX_API_END
 }
 
-extern "C" int pcx_spline_calculus_batch(pcx_spline *h, int dim, const double *lo, const double *hi, const double *fixed,
+extern "C" int pcx_slider_calculus_batch(pcx_slider *h, int dim, const double *lo, const double *hi, const double *fixed,
                                          int64_t N, int mode, double *roots_out, int32_t *counts_out, double *val_out,
                                          double *loc_out) {
     PCX_API_BEGIN
+    return slider_calc_impl(h, dim, lo, hi, fixed, N, mode, roots_out, counts_out, val_out, loc_out, nullptr);
+    PCX_API_END
+}
+
+extern "C" int pcx_slider_solve_batch(pcx_slider *h, int dim, const double *lo, const double *hi, const double *fixed,
+                                      const double *targets, int64_t N, int method, double *roots_out, int32_t *counts_out,
+                                      double *x_out, int32_t *status_out) {
+    PCX_API_BEGIN
+    const SolveReq sq{targets, method, x_out, status_out};
+    return slider_calc_impl(h, dim, lo, hi, fixed, N, 0, roots_out, counts_out, nullptr, nullptr, &sq);
+    PCX_API_END
+}
+
+static int spline_calc_impl(pcx_spline *h, int dim, const double *lo, const double *hi, const double *fixed, int64_t N,
+                            int mode, double *roots_out, int32_t *counts_out, double *val_out, double *loc_out,
+                            const SolveReq *sq) {
     if (!h || !lo || !hi) return fail(PCX_ERR_INVALID, "NULL argument");
     const int d = h->sd.d;
     if (dim < 0 || dim >= d) return fail(PCX_ERR_INVALID, "dim %d out of range [0, %d]", dim, d - 1);
@@ -380,7 +567,7 @@ extern "C" int pcx_spline_calculus_batch(pcx_spline *h, int dim, const double *l
         e.diff = pc->d_diff + pc->doff[dim];
         e.voff = F;
         e.roff = Wtot;
-        int rc = calc_check(e.n, mode, N, e.lo, e.hi, pc->d_diff, roots_out, counts_out, val_out, loc_out);
+        int rc = calc_check_req(e.n, mode, N, e.lo, e.hi, pc->d_diff, roots_out, counts_out, val_out, loc_out, sq);
         if (rc) return rc;
         F += e.n;
         Wtot += e.W;
@@ -402,15 +589,18 @@ extern "C" int pcx_spline_calculus_batch(pcx_spline *h, int dim, const double *l
     if (chunk * F > kChunkPoints) return fail(PCX_ERR_UNSUPPORTED, "%ld fibre points per row: at most %lld", F, (long long)kChunkPoints);
     DevBuf d_tab, d_fixed, d_pts, d_vals, p_roots, p_counts, p_val, p_loc;
     CalcDevOut out;
+    SolveDev sd;
+    const bool invert = sq && sq->method == 1;                 // p_val / p_counts then hold the pieces' x / status
     rc = d_tab.alloc((size_t)P * sizeof(SplineCalcPiece));
+    if (!rc) rc = sd.alloc(sq, N);
     if (!rc) rc = d_fixed.alloc((size_t)N * (d - 1) * sizeof(double));
     if (!rc) rc = d_pts.alloc((size_t)chunk * F * d * sizeof(double));
     if (!rc) rc = d_vals.alloc((size_t)chunk * F * sizeof(double));
-    if (!rc) rc = p_roots.alloc(mode == 0 ? (size_t)chunk * Wtot * sizeof(double) : 0);
+    if (!rc) rc = p_roots.alloc(mode == 0 && !invert ? (size_t)chunk * Wtot * sizeof(double) : 0);
     if (!rc) rc = p_counts.alloc((size_t)chunk * P * sizeof(int32_t));
-    if (!rc) rc = p_val.alloc(mode != 0 ? (size_t)chunk * P * sizeof(double) : 0);
+    if (!rc) rc = p_val.alloc(mode != 0 || invert ? (size_t)chunk * P * sizeof(double) : 0);
     if (!rc) rc = p_loc.alloc(mode != 0 ? (size_t)chunk * P * sizeof(double) : 0);
-    if (!rc) rc = out.alloc(mode, N, (int)Wtot);
+    if (!rc && !invert) rc = out.alloc(mode, N, (int)Wtot);
     if (rc) return rc;
     // the table once per call, with a blocking copy: `tab` (pageable) has left the host when it returns
     HIP_TRY(hipMemcpy(d_tab.p, tab.data(), (size_t)P * sizeof(SplineCalcPiece), hipMemcpyHostToDevice));
@@ -427,6 +617,7 @@ extern "C" int pcx_spline_calculus_batch(pcx_spline *h, int dim, const double *l
         (void)hipStreamSynchronize(st);
         return code;
     };
+    if ((rc = sd.upload(sq, N, st))) return finish(rc);
     for (long r0 = 0; r0 < N; r0 += chunk) {
         const long rows = std::min<long>(chunk, N - r0);
         const unsigned bx = (unsigned)std::min<long>((rows * nmax * d + 255) / 256, 4096);
@@ -434,6 +625,23 @@ extern "C" int pcx_spline_calculus_batch(pcx_spline *h, int dim, const double *l
                            d_fixed.as<double>() + (size_t)r0 * (d - 1), rows, d, dim, dt, d_pts.as<double>());
         if (hipGetLastError() != hipSuccess) return finish(fail(PCX_ERR_HIP, "k_spline_calc_expand launch failed"));
         if ((rc = spline_eval_chunk(h, d_pts.as<double>(), rows * F, nullptr, 1, d_vals.as<double>()))) return finish(rc);
+        if (invert) {                                          // a lane per (row, piece) fibre, then the lowest piece
+            const dim3 grid((unsigned)((rows + 63) / 64), (unsigned)P);
+            INV_DISPATCH(nmax, k_cheb1d_invert_pieces, grid, st, dt, rows, (const double *)d_vals.as<double>(),
+                         (const double *)sd.targets.as<double>() + r0, p_val.as<double>(), p_counts.as<int32_t>());
+            if (hipGetLastError() != hipSuccess) return finish(fail(PCX_ERR_HIP, "k_cheb1d_invert_pieces launch failed"));
+            hipLaunchKernelGGL(k_spline_invert_merge, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, P, rows,
+                               (const double *)p_val.as<double>(), (const int32_t *)p_counts.as<int32_t>(),
+                               sd.x.as<double>() + r0, sd.status.as<int32_t>() + r0);
+            if (hipGetLastError() != hipSuccess) return finish(fail(PCX_ERR_HIP, "k_spline_invert_merge launch failed"));
+            continue;
+        }
+        if (sq) {                                              // roots at a level: every (row, piece) fibre minus its row's
+            const unsigned lx = (unsigned)std::min<long>((rows * nmax + 255) / 256, 4096);
+            hipLaunchKernelGGL(k_spline_calc_level, dim3(lx, (unsigned)P), dim3(256), 0, st, dt, d_vals.as<double>(),
+                               (const double *)sd.targets.as<double>() + r0, rows);
+            if (hipGetLastError() != hipSuccess) return finish(fail(PCX_ERR_HIP, "k_spline_calc_level launch failed"));
+        }
         const unsigned fibres = (unsigned)(rows * P);
         if (m <= 16) hipLaunchKernelGGL(k_cheb1d_calculus_pieces<16>, dim3(fibres), dim3(64), 0, st, dt, rows, mode, po);
         else if (m <= 32) hipLaunchKernelGGL(k_cheb1d_calculus_pieces<32>, dim3(fibres), dim3(64), 0, st, dt, rows, mode, po);
@@ -445,6 +653,23 @@ extern "C" int pcx_spline_calculus_batch(pcx_spline *h, int dim, const double *l
                            mode != 0 ? out.loc.as<double>() + r0 : nullptr);
         if (hipGetLastError() != hipSuccess) return finish(fail(PCX_ERR_HIP, "k_spline_calc_merge launch failed"));
     }
+    if (invert) return finish(sd.download(sq, N, st));
     return finish(out.download(mode, N, (int)Wtot, roots_out, counts_out, val_out, loc_out, st));
+}
+
+extern "C" int pcx_spline_calculus_batch(pcx_spline *h, int dim, const double *lo, const double *hi, const double *fixed,
+                                         int64_t N, int mode, double *roots_out, int32_t *counts_out, double *val_out,
+                                         double *loc_out) {
+    PCX_API_BEGIN
+    return spline_calc_impl(h, dim, lo, hi, fixed, N, mode, roots_out, counts_out, val_out, loc_out, nullptr);
+    PCX_API_END
+}
+
+extern "C" int pcx_spline_solve_batch(pcx_spline *h, int dim, const double *lo, const double *hi, const double *fixed,
+                                      const double *targets, int64_t N, int method, double *roots_out, int32_t *counts_out,
+                                      double *x_out, int32_t *status_out) {
+    PCX_API_BEGIN
+    const SolveReq sq{targets, method, x_out, status_out};
+    return spline_calc_impl(h, dim, lo, hi, fixed, N, 0, roots_out, counts_out, nullptr, nullptr, &sq);
     PCX_API_END
 }

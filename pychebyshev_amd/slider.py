@@ -556,14 +556,45 @@ class ChebyshevSlider(ErgonomicsMixin, DerivativeIdMixin):
             lambda m: self._calculus_batch(dim, row, m), int(self.n_nodes[dim]), mode, nodes, weights, diff,
             (self.domain[dim][0], self.domain[dim][1]))
 
-    def roots(self, dim=None, fixed=None) -> np.ndarray:
+    def _solve_batch(self, dim: int, rows: np.ndarray, targets: np.ndarray, method: int):
+        """``pcx_slider_solve_batch`` over validated rows and targets (see :func:`pychebyshev_amd._calculus.run_solve`)."""
+        s = self._dev()
+        lo, hi = self._domain_arrays()
+        rows, targets = _lib.f64(rows), _lib.f64(targets)
+        N = rows.shape[0]
+
+        def call(r, c, x, st):
+            return s.lib.pcx_slider_solve_batch(s.handle, int(dim), _lib.p_f64(lo), _lib.p_f64(hi), _lib.p_f64(rows),
+                                                _lib.p_f64(targets), N, method, r, c, x, st)
+        return _calculus.run_solve(call, s.lib, int(self.n_nodes[dim]), N, method)
+
+    def _level_roots(self, dim, fixed, level: np.ndarray) -> np.ndarray:
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        d = self.num_dimensions
+        dim, params = _calculus.validate_calculus_args(d, dim, fixed, self.domain)
+        row = _calculus.fixed_row(d, dim, params)
+        nodes = self._owner_grid(dim)[0]
+        return _calculus.run_single_level(
+            lambda: self.eval_batch(_calculus.fibre_points(d, dim, row, nodes), [0] * d),
+            lambda: self._solve_batch(dim, row, level, 0), int(self.n_nodes[dim]), level,
+            (self.domain[dim][0], self.domain[dim][1]))
+
+    def roots(self, dim=None, fixed=None, *, level=0.0) -> np.ndarray:
         """Sorted real roots along ``dim`` with every other dimension fixed (``fixed = {dim_index: value}``;
         reference slider.py:1178-1224, which slices to one dimension and re-interpolates at the nodes).  The fibre is
         formed and solved on the device; above 64 nodes the solve runs on the host (NumPy ``chebroots``).  A
         non-finite fibre raises ``numpy.linalg.LinAlgError``.  A root within ``1e-10`` (of the half-width) of an end
         of ``domain[dim]``, on either side of it, is returned as exactly that end, and so is a critical point of
-        :meth:`minimize` / :meth:`maximize` (the reference clips from outside only)."""
-        return self._calculus(dim, fixed, "roots")
+        :meth:`minimize` / :meth:`maximize` (the reference clips from outside only).
+
+        ``level`` (keyword only, a finite scalar) asks for the solutions of ``p = level`` instead: the level is
+        subtracted from the fibre on the device, one rounding per value, before the same solver.  ``None`` or ``0.0``
+        is the call without a level, the same launches and bits."""
+        lv = _calculus.validate_level(level, 1)
+        if lv is None:
+            return self._calculus(dim, fixed, "roots")
+        return self._level_roots(dim, fixed, lv)
 
     def minimize(self, dim=None, fixed=None):
         """``(value, location)`` of the minimum along ``dim`` (reference slider.py:1226-1264)."""
@@ -578,12 +609,36 @@ class ChebyshevSlider(ErgonomicsMixin, DerivativeIdMixin):
             raise RuntimeError("Call build() first")
         return _calculus.validate_batch_args(self.num_dimensions, dim, fixed, self.domain, self.n_nodes)
 
-    def roots_batch(self, dim: int, fixed):
+    def roots_batch(self, dim: int, fixed, *, level=None):
         """Roots along ``dim`` for every row of ``fixed`` (host float64 ``(N, d-1)``: the other dimensions in
         increasing order), in one device pass (extension).  Returns ``(roots, counts)`` as
-        :meth:`ChebyshevApproximation.roots_batch`.  At most 64 nodes along ``dim``."""
+        :meth:`ChebyshevApproximation.roots_batch`.  At most 64 nodes along ``dim``.
+
+        ``level`` (keyword only, a finite scalar or an ``(N,)`` array, one level per row) asks for the solutions of ``p = level`` instead: the level is
+        subtracted from the fibre on the device, one rounding per value, before the same solver.  ``None`` or ``0.0``
+        is the call without a level, the same launches and bits."""
         rows = self._calculus_rows(dim, fixed)
-        return self._calculus_batch(int(dim), rows, 0)
+        lv = _calculus.validate_level(level, rows.shape[0])
+        if lv is None:
+            return self._calculus_batch(int(dim), rows, 0)
+        return self._solve_batch(int(dim), rows, lv, 0)
+
+    def invert_batch(self, dim: int, fixed, targets):
+        """The value of dimension ``dim`` at which the model equals each row's target (extension;
+        ``pcx_slider_solve_batch``, method 1): ``fixed`` as in :meth:`roots_batch`, ``targets`` a finite scalar or ``(N,)``
+        array.  Returns ``(x (N,) float64, status (N,) int32)``.  On the knots ``[lo, nodes..., hi]`` of the fibre
+        a segment brackets when the value at its lower knot equals the target or ``p - target`` changes sign across it;
+        ``status`` is the number of bracketing segments: ``0`` the target is not reached on the knots (``x`` NaN),
+        ``1`` unique on the knots, ``> 1`` not unique (``x`` is the lowest), ``-1`` the fibre is not finite or the
+        solver's fixed iteration cap was reached (``x`` NaN).  ``x`` is the knot itself where the value equals the
+        target there, else the root inside the lowest bracketing segment, down to adjacent doubles.  A constant fibre
+        equal to its target gives ``status = n + 2`` and ``x = lo`` when the sums at the two ends return the constant
+        itself (a power of two, zero), else n to n + 2.  A root closer to 0 than ``2^-9 max(|lo|, |hi|)`` is returned to
+        within ``2^-10 eps max(|lo|, |hi|)``, not to adjacent doubles.  Only crossings between knots are seen: two
+        solutions inside one node interval are invisible here, and ``roots_batch(level=)`` finds them.  At most 64
+        nodes along ``dim``.  One device lane solves one row (``csrc/invert_kernels.h``)."""
+        rows = self._calculus_rows(dim, fixed)
+        return self._solve_batch(int(dim), rows, _calculus.validate_targets(targets, rows.shape[0]), 1)
 
     def minimize_batch(self, dim: int, fixed):
         """``(values, locations)``, float64 ``(N,)``, of the minimum along ``dim`` for every row of ``fixed``

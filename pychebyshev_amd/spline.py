@@ -534,14 +534,48 @@ class ChebyshevSpline(ErgonomicsMixin, DerivativeIdMixin):
             return _calculus.merge_pieces("roots", [p.roots(dim, sub) for p in pieces], self.domain[dim])
         return _calculus.merge_pieces(mode, [(p.minimize if mode == "min" else p.maximize)(dim, sub) for p in pieces])
 
-    def roots(self, dim=None, fixed=None) -> np.ndarray:
+    def _solve_batch(self, dim: int, rows: np.ndarray, targets: np.ndarray, method: int):
+        """``pcx_spline_solve_batch`` over validated rows and targets (see :func:`pychebyshev_amd._calculus.run_solve`)."""
+        from . import _calculus
+        counts = self._dim_counts(dim)
+        s = self._dev()
+        lo = _lib.f64([float(b[0]) for b in self.domain])
+        hi = _lib.f64([float(b[1]) for b in self.domain])
+        rows, targets = _lib.f64(rows), _lib.f64(targets)
+        N = rows.shape[0]
+
+        def call(r, c, x, st):
+            return s.lib.pcx_spline_solve_batch(s.handle, int(dim), _lib.p_f64(lo), _lib.p_f64(hi), _lib.p_f64(rows),
+                                                _lib.p_f64(targets), N, method, r, c, x, st)
+        return _calculus.run_solve(call, s.lib, max(counts), N, method, width=sum(max(n - 1, 1) for n in counts))
+
+    def _level_roots(self, dim, fixed, level: np.ndarray) -> np.ndarray:
+        """As :meth:`_calculus` for the roots at a level: the one-row batch, or every piece on its own and the host
+        merge."""
+        from . import _calculus
+        dim, pieces, sub = self._calculus_pieces(dim, fixed)
+        counts = self._dim_counts(dim)
+        if counts is not None and max(counts) <= _calculus.MAX_DEVICE_N:
+            row = _calculus.fixed_row(self.num_dimensions, dim, list((sub or {}).items()))
+            return _calculus.single_roots(*self._solve_batch(dim, row, level, 0))
+        return _calculus.merge_pieces("roots", [p.roots(dim, sub, level=float(level[0])) for p in pieces], self.domain[dim])
+
+    def roots(self, dim=None, fixed=None, *, level=0.0) -> np.ndarray:
         """Sorted roots along ``dim`` (reference spline.py:1762-1820): every piece along ``dim`` is solved on its own
         interval, the roots are concatenated in piece order and near-duplicates at the knots (``1e-10 (|domain[dim]| +
         1)``) dropped -- in one device call (the one-row :meth:`roots_batch`) up to 64 nodes per piece.  A root within
         ``1e-10`` (of the half-width) of an end of its piece's interval, on either side of it, is returned as exactly
         that end, a knot included, and so is a critical point of :meth:`minimize` / :meth:`maximize` (the reference
-        clips from outside only)."""
-        return self._calculus(dim, fixed, "roots")
+        clips from outside only).
+
+        ``level`` (keyword only, a finite scalar) asks for the solutions of ``p = level`` instead: the level is
+        subtracted from the fibre on the device, one rounding per value, before the same solver.  ``None`` or ``0.0``
+        is the call without a level, the same launches and bits.  Every piece's fibre takes the level."""
+        from . import _calculus
+        lv = _calculus.validate_level(level, 1)
+        if lv is None:
+            return self._calculus(dim, fixed, "roots")
+        return self._level_roots(dim, fixed, lv)
 
     def minimize(self, dim=None, fixed=None):
         """``(value, location)`` of the minimum along ``dim`` over the pieces in order, strictly smaller wins
@@ -563,15 +597,44 @@ class ChebyshevSpline(ErgonomicsMixin, DerivativeIdMixin):
                              f"the batched solver needs one grid per interval (the single-row calls handle this)")
         return rows
 
-    def roots_batch(self, dim: int, fixed):
+    def roots_batch(self, dim: int, fixed, *, level=None):
         """Roots along ``dim`` for every row of ``fixed`` (host float64 ``(N, d-1)``: the other dimensions in increasing
         order) in one device pass (extension; ``pcx_spline_calculus_batch``): the fibre points of every piece along
         ``dim`` go through the spline's own evaluation, one launch solves all rows and pieces, a last kernel merges the
         pieces of a row as :meth:`roots` does.  Returns ``(roots, counts)``: ``roots`` float64 ``(N, W)`` with ``W`` the
         sum of ``max(n_j - 1, 1)`` over the pieces along ``dim``, ascending and NaN-padded; ``counts`` int32 ``(N,)``,
-        -1 where a piece's fibre was not finite or its eigenvalue iteration failed.  At most 64 nodes per piece."""
+        -1 where a piece's fibre was not finite or its eigenvalue iteration failed.  At most 64 nodes per piece.
+
+        ``level`` (keyword only, a finite scalar or an ``(N,)`` array, one level per row) asks for the solutions of ``p = level`` instead: the level is
+        subtracted from the fibre on the device, one rounding per value, before the same solver.  ``None`` or ``0.0``
+        is the call without a level, the same launches and bits.  Every ``(row, piece)`` fibre takes its row's level."""
+        from . import _calculus
         rows = self._calculus_rows(dim, fixed)
-        return self._calculus_batch(int(dim), rows, 0)
+        lv = _calculus.validate_level(level, rows.shape[0])
+        if lv is None:
+            return self._calculus_batch(int(dim), rows, 0)
+        return self._solve_batch(int(dim), rows, lv, 0)
+
+    def invert_batch(self, dim: int, fixed, targets):
+        """The value of dimension ``dim`` at which the model equals each row's target (extension;
+        ``pcx_spline_solve_batch``, method 1): ``fixed`` as in :meth:`roots_batch`, ``targets`` a finite scalar or ``(N,)``
+        array.  Returns ``(x (N,) float64, status (N,) int32)``.  Every piece along ``dim`` is solved as its own fibre on its own interval and
+        nodes; ``x`` is the lowest over the pieces with ``status > 0`` and ``status`` the sum of the pieces' statuses, so
+        a solution exactly on an interior knot is counted by both pieces that find it; a ``-1`` in any piece makes the
+        row ``-1``.  Per piece: On the knots ``[lo, nodes..., hi]`` of the fibre
+        a segment brackets when the value at its lower knot equals the target or ``p - target`` changes sign across it;
+        ``status`` is the number of bracketing segments: ``0`` the target is not reached on the knots (``x`` NaN),
+        ``1`` unique on the knots, ``> 1`` not unique (``x`` is the lowest), ``-1`` the fibre is not finite or the
+        solver's fixed iteration cap was reached (``x`` NaN).  ``x`` is the knot itself where the value equals the
+        target there, else the root inside the lowest bracketing segment, down to adjacent doubles.  A constant fibre
+        equal to its target gives ``status = n + 2`` and ``x = lo`` when the sums at the two ends return the constant
+        itself (a power of two, zero), else n to n + 2.  A root closer to 0 than ``2^-9 max(|lo|, |hi|)`` is returned to
+        within ``2^-10 eps max(|lo|, |hi|)``, not to adjacent doubles.  Only crossings between knots are seen: two
+        solutions inside one node interval are invisible here, and ``roots_batch(level=)`` finds them.  At most 64
+        nodes along ``dim``.  One device lane solves one row (``csrc/invert_kernels.h``)."""
+        from . import _calculus
+        rows = self._calculus_rows(dim, fixed)
+        return self._solve_batch(int(dim), rows, _calculus.validate_targets(targets, rows.shape[0]), 1)
 
     def minimize_batch(self, dim: int, fixed):
         """``(values, locations)``, float64 ``(N,)``, of the minimum along ``dim`` for every row of ``fixed``

@@ -1085,13 +1085,47 @@ class ChebyshevTT(ErgonomicsMixin):
             lambda: self.eval_batch(_calculus.fibre_points(d, dim, row, nodes)),
             lambda m: self._calculus_batch(dim, row, m), n, mode, nodes, weights, diff, (a, b))
 
-    def roots(self, dim=None, fixed=None) -> np.ndarray:
+    def _solve_batch(self, dim: int, rows: np.ndarray, targets: np.ndarray, method: int):
+        """``pcx_tt_solve_batch`` over validated rows and targets (see :func:`pychebyshev_amd._calculus.run_solve`)."""
+        from . import _calculus
+        t = self._dev()
+        rows, targets = _lib.f64(rows), _lib.f64(targets)
+        N = rows.shape[0]
+
+        def call(r, c, x, s):
+            return t.lib.pcx_tt_solve_batch(t.handle, int(dim), _lib.p_f64(rows), _lib.p_f64(targets), N, method, r, c, x, s)
+        return _calculus.run_solve(call, t.lib, int(self.n_nodes[self._dim_order.index(dim)]), N, method)
+
+    def _level_roots(self, dim, fixed, level: np.ndarray) -> np.ndarray:
+        from . import _calculus
+        from .barycentric import chebyshev_nodes
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        d = self.num_dimensions
+        udom = self._user_frame_domain()
+        dim, params = _calculus.validate_calculus_args(d, dim, fixed, udom)
+        row = _calculus.fixed_row(d, dim, params)
+        n = int(self.n_nodes[self._dim_order.index(dim)])
+        a, b = udom[dim]
+        return _calculus.run_single_level(
+            lambda: self.eval_batch(_calculus.fibre_points(d, dim, row, chebyshev_nodes(a, b, n))),
+            lambda: self._solve_batch(dim, row, level, 0), n, level, (a, b))
+
+    def roots(self, dim=None, fixed=None, *, level=0.0) -> np.ndarray:
         """Sorted roots along user dimension ``dim`` with the others fixed (reference tensor_train.py:1749-1790): the
         fibre is the TT's values at the nodes of ``dim``, evaluated and solved on the device (above 64 nodes the
         solve runs on the host).  ``dim`` and ``fixed`` are in the user's frame.  A root within ``1e-10`` (of the
         half-width) of an end of the domain along ``dim``, on either side of it, is returned as exactly that end, and so
-        is a critical point of :meth:`minimize` / :meth:`maximize` (the reference clips from outside only)."""
-        return self._calculus(dim, fixed, "roots")
+        is a critical point of :meth:`minimize` / :meth:`maximize` (the reference clips from outside only).
+
+        ``level`` (keyword only, a finite scalar) asks for the solutions of ``p = level`` instead: the level is
+        subtracted from the fibre on the device, one rounding per value, before the same solver.  ``None`` or ``0.0``
+        is the call without a level, the same launches and bits."""
+        from . import _calculus
+        lv = _calculus.validate_level(level, 1)
+        if lv is None:
+            return self._calculus(dim, fixed, "roots")
+        return self._level_roots(dim, fixed, lv)
 
     def minimize(self, dim=None, fixed=None):
         """``(value, location)`` of the minimum along user dimension ``dim`` (reference tensor_train.py:1792-1831)."""
@@ -1108,11 +1142,37 @@ class ChebyshevTT(ErgonomicsMixin):
         user_n = [self.n_nodes[self._dim_order.index(u)] for u in range(self.num_dimensions)]
         return _calculus.validate_batch_args(self.num_dimensions, dim, fixed, self._user_frame_domain(), user_n)
 
-    def roots_batch(self, dim: int, fixed):
+    def roots_batch(self, dim: int, fixed, *, level=None):
         """Roots along user dimension ``dim`` for every row of ``fixed`` (extension; as
-        ``ChebyshevApproximation.roots_batch``, columns = the other user dimensions in increasing order)."""
+        ``ChebyshevApproximation.roots_batch``, columns = the other user dimensions in increasing order).
+
+        ``level`` (keyword only, a finite scalar or an ``(N,)`` array, one level per row) asks for the solutions of ``p = level`` instead: the level is
+        subtracted from the fibre on the device, one rounding per value, before the same solver.  ``None`` or ``0.0``
+        is the call without a level, the same launches and bits."""
+        from . import _calculus
         rows = self._calculus_rows(dim, fixed)
-        return self._calculus_batch(int(dim), rows, 0)
+        lv = _calculus.validate_level(level, rows.shape[0])
+        if lv is None:
+            return self._calculus_batch(int(dim), rows, 0)
+        return self._solve_batch(int(dim), rows, lv, 0)
+
+    def invert_batch(self, dim: int, fixed, targets):
+        """The value of dimension ``dim`` at which the model equals each row's target (extension;
+        ``pcx_tt_solve_batch``, method 1): ``fixed`` as in :meth:`roots_batch`, ``targets`` a finite scalar or ``(N,)``
+        array.  Returns ``(x (N,) float64, status (N,) int32)``.  ``dim`` and the columns of ``fixed`` are in the user's frame.  On the knots ``[lo, nodes..., hi]`` of the fibre
+        a segment brackets when the value at its lower knot equals the target or ``p - target`` changes sign across it;
+        ``status`` is the number of bracketing segments: ``0`` the target is not reached on the knots (``x`` NaN),
+        ``1`` unique on the knots, ``> 1`` not unique (``x`` is the lowest), ``-1`` the fibre is not finite or the
+        solver's fixed iteration cap was reached (``x`` NaN).  ``x`` is the knot itself where the value equals the
+        target there, else the root inside the lowest bracketing segment, down to adjacent doubles.  A constant fibre
+        equal to its target gives ``status = n + 2`` and ``x = lo`` when the sums at the two ends return the constant
+        itself (a power of two, zero), else n to n + 2.  A root closer to 0 than ``2^-9 max(|lo|, |hi|)`` is returned to
+        within ``2^-10 eps max(|lo|, |hi|)``, not to adjacent doubles.  Only crossings between knots are seen: two
+        solutions inside one node interval are invisible here, and ``roots_batch(level=)`` finds them.  At most 64
+        nodes along ``dim``.  One device lane solves one row (``csrc/invert_kernels.h``)."""
+        from . import _calculus
+        rows = self._calculus_rows(dim, fixed)
+        return self._solve_batch(int(dim), rows, _calculus.validate_targets(targets, rows.shape[0]), 1)
 
     def minimize_batch(self, dim: int, fixed):
         """``(values, locations)`` of the minimum along user dimension ``dim`` for every row of ``fixed``."""
