@@ -42,6 +42,7 @@ extern "C" {
 #define PCX_ERR_HIP (-3)         /* a HIP runtime call failed                        */
 #define PCX_ERR_UNSUPPORTED (-4) /* valid request outside what the kernels cover     */
 #define PCX_ERR_NOMEM (-5)
+#define PCX_ERR_INTERNAL (-6)    /* a self-check of the library failed (diagnostic entry points) */
 
 #define PCX_MAX_DIMS 16
 
@@ -587,6 +588,28 @@ int pcx_tt_als(int device, int d, const int32_t *n_nodes, const int32_t *ranks, 
                const double *target, double tolerance, int max_iter, int32_t *ranks_out, double *cores_out,
                int64_t cores_cap, int64_t *cores_len, int32_t *iters_out, double *rel_change_out,
                double *grid_residual_out);
+
+/* Diagnostic: the dense steps of pcx_tt_als / pcx_tt_orth one at a time (tests/test_gpu_als_steps.py).  Host pointers,
+ * the null stream; each is an upload, one call of the internal step and a download.
+ *
+ * One contraction.  side 0: out (r x R) = small^T big with small = Q (K x r), big = P (K x R); side 1: out (R x r) =
+ * big small^T with small = C (r x K), big = P (R x K); all row-major.  form 0: the dispatch pcx_tt_als uses (MFMA from
+ * rank 16 on, or from PCX_TT_ALS_MFMA_MIN); 1: the VALU form of this rank (4, 8, 12 accumulators, above 12 sixteen,
+ * tiled over the rank); 2: the MFMA form (one 16-row tile up to rank 16, two above, tiled over the rank).  *form_used
+ * = 1 or 2.  The device output starts as a NaN pattern and is followed by 256 doubles of it: an element the kernel
+ * did not write comes back NaN, a disturbed tail is PCX_ERR_INTERNAL.  1 <= r <= 256 (above: PCX_ERR_UNSUPPORTED),
+ * K >= 1, R >= 1, K R <= PCX_TT_ALS_MAX_GRID (above: PCX_ERR_UNSUPPORTED).                                          */
+int pcx_tt_als_project(int device, int side, int form, const double *small, const double *big, double *out, int K,
+                       int r, int64_t R, int32_t *form_used);
+
+/* Diagnostic: the Householder QR of A (m x c row-major, c <= 256, m c <= PCX_TT_ALS_MAX_GRID, else
+ * PCX_ERR_UNSUPPORTED): Q (m x p) and R (p x c), p = min(m, c).  Q does not depend on the scale of A and R follows it
+ * exactly, for any finite FP64 magnitudes.                                                                          */
+int pcx_tt_als_qr(int device, const double *A, int64_t m, int c, double *Q, double *R);
+
+/* Diagnostic: out4 = |tnew - tprev|^2, |tprev|^2, |tnew - target|^2, |target|^2 over G elements
+ * (1 <= G <= PCX_TT_ALS_MAX_GRID), the convergence sums of one outer iteration.  The squares are not scaled.        */
+int pcx_tt_als_norms(int device, const double *tnew, const double *tprev, const double *target, int64_t G, double *out4);
 
 /* A sequence of adjacent swaps of storage axes (reference _algebra.py::_tt_swap_adjacent, driven by
  * ChebyshevTT.reorder): swap s exchanges axes swaps[s] and swaps[s] + 1 by one truncated SVD of the

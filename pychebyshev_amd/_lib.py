@@ -20,6 +20,7 @@ PCX_ERR_NO_DEVICE = -2
 PCX_ERR_HIP = -3
 PCX_ERR_UNSUPPORTED = -4
 PCX_ERR_NOMEM = -5
+PCX_ERR_INTERNAL = -6
 
 
 class PcxLibraryError(RuntimeError):
@@ -148,6 +149,9 @@ SIGNATURES = {
     "pcx_tt_reorder": (_I, [_I, _I, c_i32p, c_i32p, c_f64p, _I, c_i32p, _I, _D, c_i32p, c_i32p, c_f64p, _L, c_i64p, c_i32p]),
     "pcx_tt_orth": (_I, [_I, _I, c_i32p, c_i32p, c_f64p, _I, _I, c_i32p, c_f64p, _L, c_i64p]),
     "pcx_tt_als": (_I, [_I, _I, c_i32p, c_i32p, c_f64p, c_f64p, _D, _I, c_i32p, c_f64p, _L, c_i64p, c_i32p, c_f64p, c_f64p]),
+    "pcx_tt_als_project": (_I, [_I, _I, _I, c_f64p, c_f64p, c_f64p, _I, _I, _L, c_i32p]),
+    "pcx_tt_als_qr": (_I, [_I, c_f64p, _L, _I, c_f64p, c_f64p]),
+    "pcx_tt_als_norms": (_I, [_I, c_f64p, c_f64p, c_f64p, _L, c_f64p]),
     "pcx_comm_unique_id": (_I, [_V]),
     "pcx_comm_create": (_I, [_I, _I, _I, _V, c_vpp]),
     "pcx_comm_destroy": (_I, [_V]),

@@ -33,8 +33,9 @@ unsigned blocks_for(long total) {
 
 // The rank from which the contractions run on the matrix cores: 16, one full tile, as in the evaluation kernels.
 // Measured (profiles/tt_completion_probe.txt) the MFMA form is already level with the VALU form at rank 4 and 12 - 27 %
-// ahead of it at ranks 8 - 12 per outer iteration, so the switch can move down; the whole suite has only run with it at
-// 16 so far.  PCX_TT_ALS_MFMA_MIN moves it (that is how the probe runs either form at every rank).
+// ahead of it at ranks 8 - 12 per outer iteration, so the switch can move down.  Both forms are tested at every rank
+// class through pcx_tt_als_project (tests/test_gpu_als_steps.py).  PCX_TT_ALS_MFMA_MIN moves the switch (that is how
+// the probe runs either form at every rank).
 int mfma_min_rank() {
     static const int v = [] {
         const char *e = getenv("PCX_TT_ALS_MFMA_MIN");
@@ -87,10 +88,22 @@ int download(AlsTT &t, int32_t *ranks_out, double *cores_out, int64_t cap, int64
     return PCX_OK;
 }
 
+// The form a contraction of rank r runs in.  form 0: the rule of the sweeps, MFMA from mfma_min_rank() on; 1: VALU; 2:
+// MFMA (the diagnostic entry point asks for either at any rank).
+enum { TTA_FORM_AUTO = 0, TTA_FORM_VALU = 1, TTA_FORM_MFMA = 2 };
+
+int pick_form(int form, int r) {
+    if (form == TTA_FORM_AUTO) return r >= mfma_min_rank() ? TTA_FORM_MFMA : TTA_FORM_VALU;
+    return form;
+}
+
 // out (rp x R) = Q^T P, Q (K x rp), P (K x R)
-int left_project(const double *Q, const double *P, double *out, int K, int rp, long R) {
+int left_project(const double *Q, const double *P, double *out, int K, int rp, long R, int form = TTA_FORM_AUTO,
+                 int *form_used = nullptr) {
     const unsigned bx = (unsigned)((R + TTA_THREADS - 1) / TTA_THREADS);
-    if (rp >= mfma_min_rank()) {
+    form = pick_form(form, rp);
+    if (form_used) *form_used = form;
+    if (form == TTA_FORM_MFMA) {
         if (rp <= 16) hipLaunchKernelGGL(k_tta_left_mfma<1>, dim3(bx, 1), dim3(TTA_THREADS), 0, 0, Q, P, out, K, rp, R);
         else hipLaunchKernelGGL(k_tta_left_mfma<2>, dim3(bx, (unsigned)((rp + 31) / 32)), dim3(TTA_THREADS), 0, 0, Q, P, out, K, rp, R);
     } else if (rp <= 4) {
@@ -107,9 +120,12 @@ int left_project(const double *Q, const double *P, double *out, int K, int rp, l
 }
 
 // out (R x r) = P C^T, P (R x K), C (r x K)
-int right_project(const double *P, const double *C, double *out, long R, int K, int r) {
+int right_project(const double *P, const double *C, double *out, long R, int K, int r, int form = TTA_FORM_AUTO,
+                  int *form_used = nullptr) {
     const unsigned bx = (unsigned)((R + TTA_THREADS - 1) / TTA_THREADS);
-    if (r >= mfma_min_rank()) {
+    form = pick_form(form, r);
+    if (form_used) *form_used = form;
+    if (form == TTA_FORM_MFMA) {
         if (r <= 16) hipLaunchKernelGGL(k_tta_right_mfma<1>, dim3(bx, 1), dim3(TTA_THREADS), 0, 0, P, C, out, R, K, r);
         else hipLaunchKernelGGL(k_tta_right_mfma<2>, dim3(bx, (unsigned)((r + 31) / 32)), dim3(TTA_THREADS), 0, 0, P, C, out, R, K, r);
     } else if (r <= 4) {
@@ -405,5 +421,87 @@ extern "C" int pcx_tt_als(int device, int d, const int32_t *n_nodes, const int32
     *iters_out = iters;
     *grid_residual_out = residual_of(sums);
     return download(t, ranks_out, cores_out, cores_cap, cores_len);
+    PCX_API_END
+}
+
+// ---------------------------------------------------------------------------------
+// diagnostic entry points: one dense step each (include/pcx.h)
+// ---------------------------------------------------------------------------------
+#define TTA_GUARD_DOUBLES 256
+
+extern "C" int pcx_tt_als_project(int device, int side, int form, const double *small, const double *big, double *out,
+                                  int K, int r, int64_t R, int32_t *form_used) {
+    PCX_API_BEGIN
+    if (!small || !big || !out || !form_used) return fail(PCX_ERR_INVALID, "TT projection: NULL buffer");
+    if (side != 0 && side != 1) return fail(PCX_ERR_INVALID, "TT projection: side must be 0 (left) or 1 (right), got %d", side);
+    if (form < TTA_FORM_AUTO || form > TTA_FORM_MFMA) return fail(PCX_ERR_INVALID, "TT projection: form must be 0, 1 or 2, got %d", form);
+    if (K < 1 || r < 1 || R < 1) return fail(PCX_ERR_INVALID, "TT projection: K = %d, r = %d, R = %lld", K, r, (long long)R);
+    if (r > TTA_MAX_RANK) return fail(PCX_ERR_UNSUPPORTED, "TT projection: rank %d exceeds %d", r, TTA_MAX_RANK);
+    if (R > PCX_TT_ALS_MAX_GRID / K)
+        return fail(PCX_ERR_UNSUPPORTED, "TT projection: K R exceeds %lld elements", (long long)PCX_TT_ALS_MAX_GRID);
+    int rc = use_device(device);
+    if (rc) return rc;
+    const size_t nsmall = (size_t)K * r, nbig = (size_t)K * R, nout = (size_t)r * R;
+    DevBuf ds, db, dout;
+    if ((rc = ds.alloc(nsmall * sizeof(double)))) return rc;
+    if ((rc = db.alloc(nbig * sizeof(double)))) return rc;
+    if ((rc = dout.alloc((nout + TTA_GUARD_DOUBLES) * sizeof(double)))) return rc;
+    HIP_TRY(hipMemcpy(ds.p, small, nsmall * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(db.p, big, nbig * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(dout.p, 0xFF, (nout + TTA_GUARD_DOUBLES) * sizeof(double)));      // all bits set: a NaN
+    int used = 0;
+    if (side == 0) rc = left_project(ds.as<double>(), db.as<double>(), dout.as<double>(), K, r, (long)R, form, &used);
+    else rc = right_project(db.as<double>(), ds.as<double>(), dout.as<double>(), (long)R, K, r, form, &used);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    uint64_t guard[TTA_GUARD_DOUBLES];
+    HIP_TRY(hipMemcpy(guard, dout.as<double>() + nout, sizeof(guard), hipMemcpyDeviceToHost));
+    for (int i = 0; i < TTA_GUARD_DOUBLES; ++i)
+        if (guard[i] != ~(uint64_t)0)
+            return fail(PCX_ERR_INTERNAL, "TT projection: the kernel wrote %d doubles past its output (side %d, form %d, K = %d, r = %d, R = %lld)",
+                        i, side, used, K, r, (long long)R);
+    HIP_TRY(hipMemcpy(out, dout.p, nout * sizeof(double), hipMemcpyDeviceToHost));
+    *form_used = used;
+    return PCX_OK;
+    PCX_API_END
+}
+
+extern "C" int pcx_tt_als_qr(int device, const double *A, int64_t m, int c, double *Q, double *R) {
+    PCX_API_BEGIN
+    if (!A || !Q || !R) return fail(PCX_ERR_INVALID, "TT QR: NULL buffer");
+    if (m < 1 || c < 1) return fail(PCX_ERR_INVALID, "TT QR: shape (%lld, %d)", (long long)m, c);
+    if (c > TTA_MAX_RANK) return fail(PCX_ERR_UNSUPPORTED, "TT QR: %d columns exceed %d", c, TTA_MAX_RANK);
+    if (m > PCX_TT_ALS_MAX_GRID / c) return fail(PCX_ERR_UNSUPPORTED, "TT QR: m c exceeds %lld elements", (long long)PCX_TT_ALS_MAX_GRID);
+    int rc = use_device(device);
+    if (rc) return rc;
+    DevBuf dA, dQ, dR;
+    AlsWork w;
+    int p = 0;
+    if ((rc = dA.alloc((size_t)m * c * sizeof(double)))) return rc;
+    HIP_TRY(hipMemcpy(dA.p, A, (size_t)m * c * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = qr(dA.as<double>(), (long)m, c, w, dQ, dR, &p))) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(Q, dQ.p, (size_t)m * p * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(R, dR.p, (size_t)p * c * sizeof(double), hipMemcpyDeviceToHost));
+    return PCX_OK;
+    PCX_API_END
+}
+
+extern "C" int pcx_tt_als_norms(int device, const double *tnew, const double *tprev, const double *target, int64_t G,
+                                double *out4) {
+    PCX_API_BEGIN
+    if (!tnew || !tprev || !target || !out4) return fail(PCX_ERR_INVALID, "TT norms: NULL buffer");
+    if (G < 1) return fail(PCX_ERR_INVALID, "TT norms: G = %lld", (long long)G);
+    if (G > PCX_TT_ALS_MAX_GRID) return fail(PCX_ERR_UNSUPPORTED, "TT norms: G exceeds %lld", (long long)PCX_TT_ALS_MAX_GRID);
+    int rc = use_device(device);
+    if (rc) return rc;
+    DevBuf d[3];
+    const double *src[3] = {tnew, tprev, target};
+    for (int i = 0; i < 3; ++i) {
+        if ((rc = d[i].alloc((size_t)G * sizeof(double)))) return rc;
+        HIP_TRY(hipMemcpy(d[i].p, src[i], (size_t)G * sizeof(double), hipMemcpyHostToDevice));
+    }
+    AlsWork w;
+    return norms(d[0].as<double>(), d[1].as<double>(), d[2].as<double>(), (long)G, w, out4);
     PCX_API_END
 }

@@ -187,6 +187,8 @@ k_tta_transpose(const double *__restrict__ in, long rows, long cols, double *__r
 // R (p x c) upper triangular, p = min(m, c).  Columns are taken in their own order, no pivoting.  A column that is
 // zero below its diagonal takes the identity reflector (LAPACK's tau = 0), so Q stays orthonormal whatever the rank of
 // A.  The reflectors live below the diagonal of A (v_j = 1 implied) until Q is formed from them, last to first.
+// Each column's norm is taken on the column times a power of two, so Q does not depend on the scale of A and R follows
+// it exactly, for any finite FP64 magnitudes (tests/test_gpu_als_steps.py, 2^-900 .. 2^900).
 // Threads are 8 row groups x 32 columns: a column's inner product is 8 partial sums over interleaved rows, added in
 // row-group order.
 // ---------------------------------------------------------------------------------
@@ -225,9 +227,23 @@ k_tta_householder(double *__restrict__ A, long m, int c, double *__restrict__ Q,
     const int t = threadIdx.x;
     const int p = (int)(m < (long)c ? m : (long)c);
     for (int j = 0; j < p; ++j) {
+        // the column from the diagonal down times 2^-ex, ex the exponent of its largest magnitude: the squares can
+        // neither overflow nor vanish together, and a power of two changes no bit of tau, of v or (undone) of beta
+        double mx = 0.0;
+        for (long i = j + t; i < m; i += TTA_THREADS) mx = fmax(mx, fabs(A[i * c + j]));
+        s_red[t] = mx;
+        __syncthreads();
+        for (int h = TTA_THREADS / 2; h > 0; h >>= 1) {
+            if (t < h) s_red[t] = fmax(s_red[t], s_red[t + h]);
+            __syncthreads();
+        }
+        mx = s_red[0];
+        const int ex = (mx > 0.0 && mx < INFINITY) ? max(ilogb(mx), -1022) : 0;     // 2^1022 is the largest 2^-ex
+        const double down = scalbn(1.0, -ex);
+        __syncthreads();
         double s = 0.0;
         for (long i = j + 1 + t; i < m; i += TTA_THREADS) {
-            const double a = A[i * c + j];
+            const double a = A[i * c + j] * down;
             s = __builtin_fma(a, a, s);
         }
         s_red[t] = s;
@@ -237,12 +253,13 @@ k_tta_householder(double *__restrict__ A, long m, int c, double *__restrict__ Q,
             __syncthreads();
         }
         if (t == 0) {
-            const double sigma = s_red[0], alpha = A[(long)j * c + j];
-            double tau = 0.0, scale = 0.0, beta = alpha;
+            const double sigma = s_red[0], alpha = A[(long)j * c + j] * down;
+            double tau = 0.0, scale = 0.0, beta = A[(long)j * c + j];
             if (sigma != 0.0) {
-                beta = -copysign(sqrt(__builtin_fma(alpha, alpha, sigma)), alpha);
-                tau = (beta - alpha) / beta;
-                scale = 1.0 / (alpha - beta);
+                const double b = -copysign(sqrt(__builtin_fma(alpha, alpha, sigma)), alpha);
+                tau = (b - alpha) / b;
+                scale = 1.0 / (alpha - b);
+                beta = scalbn(b, ex);
             }
             s_tau[j] = tau;
             s_sc[0] = scale;
@@ -252,7 +269,7 @@ k_tta_householder(double *__restrict__ A, long m, int c, double *__restrict__ Q,
         const double tau = s_tau[j];
         if (tau != 0.0) {                                  // uniform over the workgroup
             const double scale = s_sc[0];
-            for (long i = j + 1 + t; i < m; i += TTA_THREADS) A[i * c + j] *= scale;
+            for (long i = j + 1 + t; i < m; i += TTA_THREADS) A[i * c + j] = A[i * c + j] * down * scale;
             __syncthreads();
             tta_reflect(A, c, j, tau, A, c, j + 1, c, m, s_part);
             if (t == 0) A[(long)j * c + j] = s_sc[1];

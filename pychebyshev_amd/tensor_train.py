@@ -95,6 +95,50 @@ def _maxvol(A: np.ndarray, tol: float = 1.05, max_iters: int = 100) -> np.ndarra
     return idx.astype(np.intp)
 
 
+def _als_project(side: int, small: np.ndarray, big: np.ndarray, form: int = 0):
+    """One contraction of the completion sweeps on the device (diagnostic, ``pcx_tt_als_project``).  side 0:
+    ``small.T @ big`` with small (K, r), big (K, R); side 1: ``big @ small.T`` with small (r, K), big (R, K).
+    form 0 is the sweeps' dispatch, 1 the VALU form, 2 the MFMA form.  Returns (out, form_used)."""
+    lib = _lib.load()
+    small, big = _lib.f64(small), _lib.f64(big)
+    if side == 0:
+        (K, r), (K2, R) = small.shape, big.shape
+        out = np.empty((r, R))
+    else:
+        (r, K), (R, K2) = small.shape, big.shape
+        out = np.empty((R, r))
+    if K != K2:
+        raise ValueError(f"contraction lengths differ: {K} and {K2}")
+    used = ctypes.c_int32(0)
+    _lib.check(lib.pcx_tt_als_project(_device(), int(side), int(form), _lib.p_f64(small), _lib.p_f64(big), _lib.p_f64(out),
+                                      K, r, R, ctypes.byref(used)), lib)
+    return out, int(used.value)
+
+
+def _als_qr(A: np.ndarray):
+    """The Householder QR of the completion sweeps and of ``orth_left`` / ``orth_right`` on the device (diagnostic,
+    ``pcx_tt_als_qr``): (Q (m, p), R (p, c)), p = min(m, c)."""
+    lib = _lib.load()
+    A = _lib.f64(A)
+    m, c = A.shape
+    p = min(m, c)
+    Q, R = np.empty((m, p)), np.empty((p, c))
+    _lib.check(lib.pcx_tt_als_qr(_device(), _lib.p_f64(A), m, c, _lib.p_f64(Q), _lib.p_f64(R)), lib)
+    return Q, R
+
+
+def _als_norms(tnew: np.ndarray, tprev: np.ndarray, target: np.ndarray) -> np.ndarray:
+    """The four convergence sums of one outer iteration on the device (diagnostic, ``pcx_tt_als_norms``):
+    |new - prev|^2, |prev|^2, |new - target|^2, |target|^2."""
+    lib = _lib.load()
+    a, b, c = (_lib.f64(x).ravel() for x in (tnew, tprev, target))
+    if not a.size == b.size == c.size:
+        raise ValueError("the three tensors differ in size")
+    out = np.empty(4)
+    _lib.check(lib.pcx_tt_als_norms(_device(), _lib.p_f64(a), _lib.p_f64(b), _lib.p_f64(c), a.size, _lib.p_f64(out)), lib)
+    return out
+
+
 def _value_core_to_coeff_core(value_core: np.ndarray) -> np.ndarray:
     """Values at type-I nodes -> Chebyshev coefficients along axis 1
     (reference tensor_train.py:997-1016), DCT-II evaluated on the device."""

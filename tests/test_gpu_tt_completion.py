@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 from numpy.polynomial.chebyshev import chebpts1
 
+from als_steps import dense as _dense, lapack_sweep as _lapack_sweep, numpy_als as _numpy_als
 from conftest import assert_parity, golden
 
 from pychebyshev_amd import ChebyshevTT
@@ -104,46 +105,6 @@ def test_max_iter_zero_runs_no_sweep(g23):
 
 
 # ------------------------------------------------------------------ independent of the reference
-def _numpy_als(cores, T, iters):
-    """ALS in projection form: orthogonalise right to left, then carry the projected target along both half sweeps."""
-    cores, n, d = [c.copy() for c in cores], T.shape, len(cores)
-    for k in range(d - 1, 0, -1):
-        r0, nk, r1 = cores[k].shape
-        Q, R = np.linalg.qr(cores[k].reshape(r0, -1).T)
-        cores[k], cores[k - 1] = Q.T.reshape(-1, nk, r1), np.einsum("anb,cb->anc", cores[k - 1], R)
-    for _ in range(iters):
-        P = T.reshape(1, -1)
-        for k in range(d):
-            rl = P.shape[0]
-            C = X = P.reshape(rl * n[k], -1)
-            for j in range(d - 1, k, -1):
-                Cj = cores[j].reshape(cores[j].shape[0], -1)
-                C = C.reshape(-1, Cj.shape[1]) @ Cj.T
-            cores[k] = C.reshape(rl, n[k], -1)
-            if k < d - 1:
-                Q, _ = np.linalg.qr(C.reshape(rl * n[k], -1))
-                cores[k], P = Q.reshape(rl, n[k], -1), Q.T @ X
-        S = T.reshape(-1, 1)
-        for k in range(d - 1, -1, -1):
-            rr = S.shape[1]
-            C = X = S.reshape(-1, n[k] * rr)
-            for j in range(k):
-                Qj = cores[j].reshape(-1, cores[j].shape[2])
-                C = Qj.T @ C.reshape(Qj.shape[0], -1)
-            cores[k] = C.reshape(-1, n[k], rr)
-            if k > 0:
-                Q, _ = np.linalg.qr(C.reshape(-1, n[k] * rr).T)
-                cores[k], S = Q.T.reshape(-1, n[k], rr), X @ Q
-    return cores
-
-
-def _dense(cores):
-    out = cores[0]
-    for c in cores[1:]:
-        out = np.einsum("...i,ijk->...jk", out, c)
-    return out[0, ..., 0]
-
-
 def _smooth_target(n, domain):
     grids = [np.sort(0.5 * (a + b) + 0.5 * (b - a) * chebpts1(nk)) for (a, b), nk in zip(domain, n)]
     mesh = np.meshgrid(*grids, indexing="ij")
@@ -205,25 +166,6 @@ def _rank_deficient_cores():
 def _orth_models(g):
     cores, domain = _rank_deficient_cores()
     return {"M16": ([g[f"M16_start_core{k}"] for k in range(4)], g["M16_domain"].tolist()), "deficient": (cores, domain)}
-
-
-def _lapack_sweep(cores, side, position):
-    """The reference's sweep in NumPy; per orthogonalised core (m, max|Q^T Q - I| of LAPACK's factor)."""
-    cores, figures = [c.copy() for c in cores], {}
-    d = len(cores)
-    order = range(position) if side == "left" else range(d - 1, position, -1)
-    for k in order:
-        r0, nk, r1 = cores[k].shape
-        if side == "left":
-            Q, R = np.linalg.qr(cores[k].reshape(r0 * nk, r1))
-            cores[k + 1] = np.einsum("ij,jpk->ipk", R, cores[k + 1])
-            m = r0 * nk
-        else:
-            Q, R = np.linalg.qr(cores[k].reshape(r0, nk * r1).T)
-            cores[k - 1] = np.einsum("ipk,jk->ipj", cores[k - 1], R)
-            m = nk * r1
-        figures[k] = (m, float(np.max(np.abs(Q.T @ Q - np.eye(Q.shape[1])))), Q.shape[1])
-    return figures
 
 
 @pytest.mark.parametrize("side", ["left", "right"])

@@ -103,6 +103,9 @@ def test_build_method_als_still_raises():
 def test_abi_table_has_the_two_entry_points():
     assert len(_lib.SIGNATURES["pcx_tt_orth"][1]) == 11
     assert len(_lib.SIGNATURES["pcx_tt_als"][1]) == 15
+    assert len(_lib.SIGNATURES["pcx_tt_als_project"][1]) == 10
+    assert len(_lib.SIGNATURES["pcx_tt_als_qr"][1]) == 6
+    assert len(_lib.SIGNATURES["pcx_tt_als_norms"][1]) == 6
 
 
 @pytest.mark.parametrize("tag", SMALL)
