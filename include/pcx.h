@@ -259,6 +259,30 @@ int pcx_bary_box_batch_dev(pcx_bary *h, const int32_t *flags, const double *lo, 
 /* The form a box call takes now: [0] 1 = MFMA form, 0 = rows form; [1] k-steps per row tile; [2] seed columns R;
  * [3] 1 = wide codes (more than four head or tail dimensions).  [1] .. [3] are 0 for the rows form. */
 int pcx_bary_box_info(pcx_bary *h, int32_t *info_out /* 4 ints */);
+/* Ladders, batched: out[r * m + x] = the interpolant (its derivative `deriv`: d orders as pcx_bary_eval_batch takes them,
+ * NULL = the values) at the point whose coordinate along `dim` is the x-th value of row r and whose other coordinates
+ * are fixed[r * (d - 1) + ...], the dimensions but dim in increasing order.  xs_per_row = 0: the m values of xs are shared
+ * by all rows; 1: xs is N x m.  The row's fibre F[j] = sum over the other dimensions of T . (their normalised barycentric
+ * weights, the one-hot rule within 1e-14 of a node included) is formed once, on the spec's derived tensor, and the
+ * ladder is its 1-D barycentric interpolant: a value within 1e-14 of a node of dim returns F at that node itself, so
+ * xs = the nodes of dim gives the fibre.  Neither fixed nor xs is checked against a domain; a NaN in fixed makes the row
+ * NaN, a NaN in xs its own cell.  A NULL handle or pointer, dim outside [0, d), m < 0, N < 0, xs_per_row outside {0, 1}
+ * and a derivative order outside [0, 8] are PCX_ERR_INVALID before any launch; N = 0 or m = 0 returns PCX_OK after these
+ * checks without a launch.  Handles with at least two dimensions, at most 64 nodes along dim and tables within 64 KB
+ * of LDS run v_mfma_f64_16x16x4_f64 on an image of the tensor with dim innermost, packed on the first call per
+ * (deriv, dim) and kept with the derived tensor (k_bary_ladder_mfma); every other handle, and every handle after
+ * pcx_bary_set_kernel(h, 1), runs the any-shape form on the plain tensor (k_bary_ladder_rows).  One workgroup per block
+ * of rows: a row's result depends neither on the batch nor on m.  The host form stages d - 1 (+ m when xs is per row,
+ * at least 1) doubles per row in passes of max(1, 2^20 / max(that width, m)) rows through the driver the evaluation
+ * entries share.  The _dev form takes device rows, device xs when they are per row (HOST xs when shared: it then
+ * returns after its kernel has finished) and device results, and queues on `stream` (NULL: the handle's). */
+int pcx_bary_ladder_batch(pcx_bary *h, int dim, const int32_t *deriv, const double *fixed, int64_t N, const double *xs,
+                          int m, int xs_per_row, double *out);
+int pcx_bary_ladder_batch_dev(pcx_bary *h, int dim, const int32_t *deriv, const double *d_fixed, int64_t N,
+                              const double *xs, int m, int xs_per_row, double *d_out, void *stream);
+/* The form a ladder along dim takes now: [0] 1 = MFMA form, 0 = rows form; [1] k-steps per block of 16 rows; [2] column
+ * tiles of 16 fibre nodes.  [1] and [2] are 0 for the rows form. */
+int pcx_bary_ladder_info(pcx_bary *h, int dim, int32_t *info_out /* 3 ints */);
 
 /* ---- piecewise (spline) interpolant ---------------------------------------- */
 /* ChebyshevSpline (spline.py:35-700): per-dimension sorted interior knots (concatenated)
@@ -389,6 +413,15 @@ int pcx_tt_stream(pcx_tt *h, void **stream);
 int pcx_tt_box_batch(pcx_tt *h, const int32_t *integrated, const double *rows, int64_t N, double *out);
 int pcx_tt_box_batch_dev(pcx_tt *h, const int32_t *integrated, const double *d_rows, int64_t N, double *d_out,
                          void *stream);
+/* Ladders, batched, as pcx_bary_ladder_batch[_dev] without a derivative spec: out[r * m + x] = the model at the point
+ * whose coordinate along `dim` (the USER's dimension order, as the columns of fixed) is the x-th value of row r.  The
+ * row's left and right chains and the n Chebyshev coefficients of its restriction to dim are formed once; each value is
+ * then that series by the evaluation's recurrence.  Arguments, checks and staging as there.  Models with a lane-per-point
+ * image (ranks <= 16, n <= 16) run one row per lane, every other model one row per wave on the plain cores. */
+int pcx_tt_ladder_batch(pcx_tt *h, int dim, const double *fixed, int64_t N, const double *xs, int m, int xs_per_row,
+                        double *out);
+int pcx_tt_ladder_batch_dev(pcx_tt *h, int dim, const double *d_fixed, int64_t N, const double *xs, int m, int xs_per_row,
+                            double *d_out, void *stream);
 /* Analytic derivatives, batched: out[p * m + s] = the partial derivative of the interpolant with the orders of spec s at
  * point p.  Arguments as pcx_tt_eval_multi_batch[_dev]: derivs = m x d orders (0, 1 or 2; anything else is
  * PCX_ERR_INVALID, "... not supported ...") in the USER's dimension order, out is N x m.  One chain per (point, spec)

@@ -27,6 +27,7 @@ SOURCES = {
     "pcx_bary_seed1.hip": BARY_H + ["bary_kernels.h", "bary_mfma_launch.h"],
     "pcx_bary_seed2.hip": BARY_H + ["bary_kernels.h", "bary_mfma_launch.h"],
     "pcx_bary_box.hip": BARY_H + ["bary_kernels.h", "bary_box_kernels.h"],
+    "pcx_bary_ladder.hip": BARY_H + ["bary_kernels.h", "bary_ladder_kernels.h"],
     "pcx_bary_grid.hip": BARY_H + ["bary_grid_kernels.h", "bary_weights.h"],
     "pcx_bary_kfold.hip": BARY_H + ["bary_kfold_kernels.h"],
     "pcx_mode_product.hip": BARY_H + ["grid_plan.h", "mode_product_kernels.h"],
@@ -38,6 +39,7 @@ SOURCES = {
     "pcx_tt.hip": HOST_H + ["tt_kernels.h", "tt_lpp_kernels.h", "tt_fd_kernels.h"],
     "pcx_tt_box.hip": HOST_H + ["tt_lpp_kernels.h", "tt_box_kernels.h"],
     "pcx_tt_deriv.hip": HOST_H + ["tt_lpp_kernels.h", "tt_box_kernels.h", "tt_deriv_kernels.h"],
+    "pcx_tt_ladder.hip": HOST_H + ["tt_lpp_kernels.h", "tt_ladder_kernels.h"],
     "pcx_ttbuild.hip": HOST_H + ["ttcross_kernels.h", "ttsvd_kernels.h", "tt_round_kernels.h"],
     "pcx_tt_als.hip": HOST_H + ["tt_als_kernels.h"],
     "pcx_calculus.hip": BARY_H + ["pcx_slider_internal.h", "pcx_spline_internal.h", "gather_kernels.h",

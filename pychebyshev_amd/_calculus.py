@@ -79,6 +79,120 @@ def validate_batch_args(ndim: int, dim, fixed, domain, n_nodes) -> np.ndarray:
     return rows
 
 
+def validate_fibre_args(ndim: int, dim, fixed, domain):
+    """:func:`validate_batch_args` for the calls that need no solver (``ladder_batch`` / ``fibre_batch``): the same
+    checks and messages without the 64-node cap along ``dim``.  NaN passes the domain check (it makes its row NaN).
+    ``fixed`` may be a device array: its shape is checked here, its values are not (they would have to come to the
+    host first); it is returned as the ``DeviceArray``."""
+    from .device import as_device_array
+    if isinstance(dim, bool) or not isinstance(dim, (int, np.integer)):
+        raise TypeError(f"dim must be an int, got {type(dim).__name__}")
+    if dim < 0 or dim >= ndim:
+        raise ValueError(f"dim {dim} out of range [0, {ndim - 1}]")
+    dev = as_device_array(fixed)
+    if dev is not None:
+        if dev.ndim != 2 or dev.shape[1] != ndim - 1:
+            raise ValueError(f"fixed must have shape (N, {ndim - 1}), got {dev.shape}")
+        return dev
+    rows = np.ascontiguousarray(np.asarray(fixed, dtype=np.float64))
+    if ndim == 1 and rows.ndim == 1 and rows.size == 0:
+        rows = rows.reshape(0, 0)
+    if rows.ndim != 2 or rows.shape[1] != ndim - 1:
+        raise ValueError(f"fixed must have shape (N, {ndim - 1}), got {rows.shape}")
+    others = [k for k in range(ndim) if k != dim]
+    for c, k in enumerate(others):
+        lo, hi = domain[k]
+        bad = np.nonzero((rows[:, c] < lo) | (rows[:, c] > hi))[0]
+        if bad.size:
+            r = int(bad[0])
+            raise ValueError(f"Fixed value {rows[r, c]} for dim {k} outside domain [{lo}, {hi}] (row {r})")
+    return rows
+
+
+def validate_ladder_xs(xs, N: int):
+    """The values of a ladder: ``(xs, m, per_row)``.  Shape ``(m,)`` (a scalar counts as ``(1,)``) is shared by all rows
+    and comes back as a host array; ``(N, m)`` is one set per row, a host array or a ``DeviceArray``.  The values are not
+    checked: points outside the domain extrapolate, as in evaluation, and a NaN gives NaN in its own cell."""
+    from .device import as_device_array
+    dev = as_device_array(xs)
+    if dev is not None:
+        if dev.ndim == 2 and dev.shape[0] == N:
+            return dev, dev.shape[1], True
+        if dev.ndim == 1:
+            return np.ascontiguousarray(dev.to_host()), dev.shape[0], False       # shared values enter from the host
+        raise ValueError(f"xs must have shape (m,) or ({N}, m), got {dev.shape}")
+    arr = np.asarray(xs, dtype=np.float64)
+    if arr.ndim == 0:
+        arr = arr.reshape(1)
+    if arr.ndim == 1:
+        return np.ascontiguousarray(arr), arr.shape[0], False
+    if arr.ndim == 2 and arr.shape[0] == N:
+        return np.ascontiguousarray(arr), arr.shape[1], True
+    raise ValueError(f"xs must have shape (m,) or ({N}, m), got {arr.shape}")
+
+
+def validate_ladder_out(out, shape):
+    """``out=`` of a ladder call: ``None``, a ``DeviceArray`` or a C-contiguous float64 NumPy array of the result's shape.
+    Returns ``(host_out, dev_out)``, at most one of them set.  Needs no device."""
+    from .device import as_device_array
+    if out is None:
+        return None, None
+    if isinstance(out, np.ndarray):
+        if out.dtype != np.float64:
+            raise ValueError(f"out must be float64, got {out.dtype}")
+        if out.shape != tuple(shape):
+            raise ValueError(f"out.shape={out.shape} does not match the result {tuple(shape)}")
+        if not out.flags.c_contiguous:
+            raise ValueError("out must be C-contiguous")
+        return out, None
+    dev = as_device_array(out)
+    if dev is None:
+        raise ValueError("out must be a DeviceArray, a float64 NumPy array or None")
+    if dev.shape != tuple(shape):
+        raise ValueError(f"out.shape={dev.shape} does not match the result {tuple(shape)}")
+    return None, dev
+
+
+def run_ladder(lib, device: int, stream, call_host, call_dev, rows, xs, m: int, per_row: bool, out):
+    """Drive one ``pcx_*_ladder_batch`` / ``_dev`` pair over validated arguments.  ``call_host(fixed, N, xs, m, per_row,
+    out)`` and ``call_dev(d_fixed, N, xs, m, per_row, d_out, stream)`` return the entry's code.  All-host arguments go
+    through the host entry; a device array among ``rows``, a per-row ``xs`` or ``out`` sends the call through the device
+    entry, host pieces uploaded first.  The result is ``out`` when given, a ``DeviceArray`` (complete on return) when
+    ``rows`` is one, else a NumPy array."""
+    import ctypes
+
+    from .device import DeviceArray, is_device_array
+    N = rows.shape[0]
+    host_out, dev_out = validate_ladder_out(out, (N, m))
+    rows_dev, xs_dev = is_device_array(rows), per_row and is_device_array(xs)
+    for name, arr in (("fixed", rows if rows_dev else None), ("xs", xs if xs_dev else None), ("out", dev_out)):
+        if arr is not None and arr.size and arr.device != device:
+            raise ValueError(f"{name} lives on device {arr.device} but the model is on device {device}; "
+                             f"call to_device({arr.device}) on the model first")
+    if not (rows_dev or xs_dev or dev_out is not None):
+        res = np.empty((N, m)) if host_out is None else host_out
+        if N and m:
+            _lib.check(call_host(_lib.p_f64(rows), N, _lib.p_f64(xs), m, 1 if per_row else 0, _lib.p_f64(res)), lib)
+        return res
+    res = DeviceArray.empty((N, m), device) if dev_out is None else dev_out
+    if N and m:
+        d_rows = rows if rows_dev else DeviceArray.from_host(rows, device)
+        if per_row:
+            d_xs = xs if xs_dev else DeviceArray.from_host(xs, device)
+            xs_arg = ctypes.c_void_p(d_xs.ptr)
+        else:
+            xs_arg = xs.ctypes.data_as(ctypes.c_void_p)
+        _lib.check(call_dev(ctypes.c_void_p(d_rows.ptr), N, xs_arg, m, 1 if per_row else 0, ctypes.c_void_p(res.ptr), stream), lib)
+        _lib.check(lib.pcx_stream_synchronize(stream), lib)
+    if host_out is not None:
+        if res.size:
+            host_out[...] = res.to_host()
+        return host_out
+    if dev_out is not None:
+        return out
+    return res if rows_dev else res.to_host()
+
+
 def validate_targets(targets, N: int, name: str = "targets") -> np.ndarray:
     """The ``(N,)`` float64 targets of an ``invert_batch`` call (a scalar serves every row), checked on the host before
     any launch: one finite value per row."""

@@ -105,6 +105,11 @@ SIGNATURES = {
     "pcx_bary_box_batch": (_I, [_V, c_i32p, c_f64p, c_f64p, c_f64p, _L, c_f64p]),
     "pcx_bary_box_batch_dev": (_I, [_V, c_i32p, c_f64p, c_f64p, _V, _L, _V, _V]),
     "pcx_bary_box_info": (_I, [_V, c_i32p]),
+    "pcx_bary_ladder_batch": (_I, [_V, _I, c_i32p, c_f64p, _L, c_f64p, _I, _I, c_f64p]),
+    "pcx_bary_ladder_batch_dev": (_I, [_V, _I, c_i32p, _V, _L, _V, _I, _I, _V, _V]),
+    "pcx_bary_ladder_info": (_I, [_V, _I, c_i32p]),
+    "pcx_tt_ladder_batch": (_I, [_V, _I, c_f64p, _L, c_f64p, _I, _I, c_f64p]),
+    "pcx_tt_ladder_batch_dev": (_I, [_V, _I, _V, _L, _V, _I, _I, _V, _V]),
     "pcx_spline_create": (_I, [_I, _I, c_i32p, c_f64p, c_vpp, _I, c_vpp]),
     "pcx_spline_destroy": (_I, [_V]),
     "pcx_spline_eval_batch": (_I, [_V, c_f64p, _L, c_i32p, c_f64p]),

@@ -1281,6 +1281,61 @@ class ChebyshevApproximation(ErgonomicsMixin, DerivativeIdMixin):
         val, loc, _ = self._calculus_batch(int(dim), rows, 2)
         return val, loc
 
+    def ladder_batch(self, dim: int, fixed, xs, derivative_order=None, *, derivative_id=None, out=None):
+        """The model along ``dim`` at ``m`` values for every row of ``fixed`` (extension; a spot or vol ladder, a
+        bump-and-revalue explain): ``result[r, x] = vectorized_eval(point, derivative_order)`` at the point whose
+        coordinate along ``dim`` is the row's x-th value and whose other coordinates are ``fixed[r]``, shape ``(N, m)``.
+
+        ``fixed``: ``(N, d-1)``, the other dimensions in increasing order as :meth:`roots_batch` takes them (no limit on
+        the nodes along ``dim``); a value outside its dimension's domain raises ``ValueError`` before any device call,
+        a NaN makes its row NaN.  ``xs``: ``(m,)`` shared by all rows or ``(N, m)`` per row; not checked against the
+        domain (points outside extrapolate, as in evaluation), a NaN gives NaN in its own cell; ``m = 0`` returns
+        ``(N, 0)`` without a launch.  ``derivative_order`` / ``derivative_id`` as in ``vectorized_eval``: the ladder is
+        taken on the spec's derived tensor, so a derivative along ``dim`` uses the differentiation passes evaluation
+        uses.
+
+        The row's restriction to ``dim`` (its fibre at the nodes, :meth:`fibre_batch`) is contracted once
+        (``pcx_bary_ladder_batch``: one ``v_mfma_f64_16x16x4_f64`` contraction per 16 rows, or the any-shape form) and
+        the ``m`` values are its 1-D barycentric interpolant, where ``vectorized_eval_batch`` on the ``N m`` points
+        contracts the tensor ``m`` times per row.  A value within 1e-14 of a node returns the fibre's value there.
+
+        ``fixed`` and a per-row ``xs`` may be device arrays (device rows are not checked against the domain).  With a
+        device ``fixed`` the result is a :class:`~pychebyshev_amd.device.DeviceArray`, complete on return.  ``out=``
+        takes a ``DeviceArray`` or a C-contiguous float64 NumPy array of shape ``(N, m)``; it is filled and returned."""
+        from . import _calculus
+        if derivative_order is None and derivative_id is None:
+            derivative_order = [0] * self.num_dimensions
+        else:
+            derivative_order = self._resolve_derivative_args(derivative_order, derivative_id)
+        if self.tensor_values is None:
+            raise RuntimeError("Call build() first")
+        rows = _calculus.validate_fibre_args(self.num_dimensions, dim, fixed, self.domain)
+        spec = self._check_orders(derivative_order)
+        xv, m, per_row = _calculus.validate_ladder_xs(xs, rows.shape[0])
+        _calculus.validate_ladder_out(out, (rows.shape[0], m))         # refused before the model goes to a device
+        model = self._model()
+        st = ctypes.c_void_p()
+        _lib.check(model.lib.pcx_bary_stream(model.handle, ctypes.byref(st)), model.lib)
+        lib, h, dim = model.lib, model.handle, int(dim)
+        return _calculus.run_ladder(
+            lib, model.device, st,
+            lambda f, N, x, mm, pr, o: lib.pcx_bary_ladder_batch(h, dim, _lib.p_i32(spec), f, N, x, mm, pr, o),
+            lambda f, N, x, mm, pr, o, s: lib.pcx_bary_ladder_batch_dev(h, dim, _lib.p_i32(spec), f, N, x, mm, pr, o, s),
+            rows, xv, m, per_row, out)
+
+    def fibre_batch(self, dim: int, fixed, derivative_order=None, *, derivative_id=None, out=None):
+        """Every row's restriction to ``dim`` at that dimension's own nodes, ``(N, n_dim)``: :meth:`ladder_batch` at
+        ``self.nodes[dim]`` (ascending), bit for bit -- the fibre the calculus batches expand into ``n_dim`` point
+        evaluations, from one contraction per row."""
+        if self.tensor_values is None:
+            raise RuntimeError("Call build() first")
+        if isinstance(dim, bool) or not isinstance(dim, (int, np.integer)):
+            raise TypeError(f"dim must be an int, got {type(dim).__name__}")
+        if dim < 0 or dim >= self.num_dimensions:
+            raise ValueError(f"dim {dim} out of range [0, {self.num_dimensions - 1}]")
+        return self.ladder_batch(dim, fixed, np.asarray(self.nodes[dim], dtype=float), derivative_order,
+                                 derivative_id=derivative_id, out=out)
+
     def fast_eval(self, point, derivative_order=None, *, derivative_id=None) -> float:
         """Deprecated alias kept for drop-in compatibility (reference :789-869): same value as
         :meth:`vectorized_eval`, which it asks callers to use instead."""

@@ -20,8 +20,10 @@ struct DerivedTensor {
     double **slot = nullptr;  // device table with the single entry `frag` (kernel's frag_tab)
     double *frag_g0 = nullptr;   // slab packing for dim-0 group launches (n0 * tps * (KS * 64 + 16 R) doubles), built on first use
     double **slot_g0 = nullptr;  // device table with the single entry `frag_g0`
+    double *ladder[PCX_MAX_DIMS] = {};   // ladder B images by dimension (bary_ladder_kernels.h), each packed on first use
     uint64_t last_use = 0;    // handle clock at the last request (least-recently-used eviction)
     void free_all() {
+        for (double *&img : ladder) { if (img) (void)hipFree(img); img = nullptr; }
         if (plain) (void)hipFree(plain);
         if (frag) (void)hipFree(frag);
         if (slot) (void)hipFree(slot);

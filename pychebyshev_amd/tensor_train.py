@@ -1200,6 +1200,50 @@ class ChebyshevTT(ErgonomicsMixin):
             return self._calculus_batch(int(dim), rows, 0)
         return self._solve_batch(int(dim), rows, lv, 0)
 
+    def ladder_batch(self, dim: int, fixed, xs, *, out=None):
+        """The model along user dimension ``dim`` at ``m`` values for every row of ``fixed`` (extension; as
+        ``ChebyshevApproximation.ladder_batch``): ``result[r, x] = eval(point)`` at the point whose coordinate along
+        ``dim`` is the row's x-th value and whose other coordinates are ``fixed[r]`` (``(N, d-1)``, the other user
+        dimensions in increasing order), shape ``(N, m)``.  ``xs`` is ``(m,)`` shared or ``(N, m)`` per row and is not
+        checked against the domain; ``fixed`` is (``ValueError`` before any device call); NaN in ``fixed`` makes its
+        row NaN, in ``xs`` its own cell.  ``fixed``, a per-row ``xs`` and ``out=`` may be device arrays, as there.
+
+        The row's left and right chains and the ``n`` Chebyshev coefficients of its restriction to ``dim`` are formed
+        once (``pcx_tt_ladder_batch``), each value is then that series: about one evaluation per row plus ``n`` FMAs
+        per value, where ``eval_batch`` on the ``N m`` points walks the whole train ``m`` times per row.
+
+        The call takes no derivative spec: a Greek ladder is ``tt.differentiate(spec).ladder_batch(...)``."""
+        from . import _calculus
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        rows = _calculus.validate_fibre_args(self.num_dimensions, dim, fixed, self._user_frame_domain())
+        xv, m, per_row = _calculus.validate_ladder_xs(xs, rows.shape[0])
+        _calculus.validate_ladder_out(out, (rows.shape[0], m))
+        t = self._dev()
+        st = ctypes.c_void_p()
+        _lib.check(t.lib.pcx_tt_stream(t.handle, ctypes.byref(st)), t.lib)
+        lib, h, dim = t.lib, t.handle, int(dim)
+        return _calculus.run_ladder(
+            lib, t.device, st,
+            lambda f, N, x, mm, pr, o: lib.pcx_tt_ladder_batch(h, dim, f, N, x, mm, pr, o),
+            lambda f, N, x, mm, pr, o, s: lib.pcx_tt_ladder_batch_dev(h, dim, f, N, x, mm, pr, o, s),
+            rows, xv, m, per_row, out)
+
+    def fibre_batch(self, dim: int, fixed, *, out=None):
+        """Every row's restriction to user dimension ``dim`` at that dimension's ascending nodes (the grid
+        :meth:`nodes` gives), ``(N, n_dim)``: :meth:`ladder_batch` at those nodes, bit for bit.  No derivative spec:
+        ``tt.differentiate(spec).fibre_batch(...)``."""
+        from .barycentric import chebyshev_nodes
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        if isinstance(dim, bool) or not isinstance(dim, (int, np.integer)):
+            raise TypeError(f"dim must be an int, got {type(dim).__name__}")
+        if dim < 0 or dim >= self.num_dimensions:
+            raise ValueError(f"dim {dim} out of range [0, {self.num_dimensions - 1}]")
+        pos = self._dim_order.index(int(dim))
+        a, b = self.domain[pos]
+        return self.ladder_batch(dim, fixed, chebyshev_nodes(a, b, int(self.n_nodes[pos])), out=out)
+
     def invert_batch(self, dim: int, fixed, targets):
         """The value of dimension ``dim`` at which the model equals each row's target (extension;
         ``pcx_tt_solve_batch``, method 1): ``fixed`` as in :meth:`roots_batch`, ``targets`` a finite scalar or ``(N,)``
