@@ -325,6 +325,26 @@ int pcx_spline_eval_multi_batch_dev(pcx_spline *h, const double *d_pts, int64_t 
 int pcx_spline_eval_tensor_grid(pcx_spline *h, const int32_t *deriv, const int32_t *m, const double *axes_cat, double *out);
 int pcx_spline_eval_tensor_grid_dev(pcx_spline *h, const int32_t *deriv, const int32_t *m, const double *axes_cat,
                                     double *d_out, void *stream);
+/* Ladders, batched: out[r * m + x] = pcx_spline_eval_batch (spec `deriv`, NULL = the values) at the point whose
+ * coordinate along `dim` is the x-th value of row r and whose other coordinates are fixed[r * (d - 1) + ...].  Arguments,
+ * checks (a NULL handle or pointer, dim outside [0, d), m < 0, N < 0, xs_per_row outside {0, 1}, an order outside [0, 8]:
+ * PCX_ERR_INVALID before any launch; N = 0 or m = 0: PCX_OK after them) and host staging as pcx_bary_ladder_batch.
+ *   Routing: pcx_spline_eval_tensor_grid's rule per dimension (knots <= x counted, clipped; a knot belongs to the
+ *     right-hand piece, outside the domain to the end piece, NaN to the last piece; no knot check for derivative specs).
+ *     fixed[r] selects the row's cross-section (the piece index in every dimension but dim), each value the index along dim.
+ *   Evaluation: rows are bucketed by cross-section; every piece (non-empty cross-section, live index j along dim) runs its
+ *     own ladder (pcx_bary_ladder_batch_dev's launch) on the bucket's rows at its own nodes along dim, which gives the
+ *     bucket's fibres; one kernel then interpolates every cell on the fibre of the piece its value falls into, by the dense
+ *     ladder's 1-D rule: out[r * m + x] is bit for bit what that piece's own ladder gives for the row and value.  An index
+ *     along dim is live when a value of the call falls into it (found on the host; with device per-row xs all are live).
+ *     Pieces that share an index along dim must share the node count there (else PCX_ERR_INVALID); more than 65535 pieces
+ *     along dim are PCX_ERR_UNSUPPORTED.  Rows go in chunks of 2^21 / (sum of the live node counts along dim).
+ * The _dev form takes device rows, device xs when they are per row (HOST xs when shared) and device results; the work
+ * runs on the handle's stream and side streams and is complete on return (`stream` may be NULL and is not used). */
+int pcx_spline_ladder_batch(pcx_spline *h, int dim, const int32_t *deriv, const double *fixed, int64_t N, const double *xs,
+                            int m, int xs_per_row, double *out);
+int pcx_spline_ladder_batch_dev(pcx_spline *h, int dim, const int32_t *deriv, const double *d_fixed, int64_t N,
+                                const double *xs, int m, int xs_per_row, double *d_out, void *stream);
 
 /* ---- slider: sum of low-dimensional slides around a pivot -------------------- */
 /* State of ChebyshevSlider (slider.py:80-341): the slides are barycentric handles over the
@@ -373,6 +393,21 @@ int pcx_slider_box_batch_dev(pcx_slider *h, const int32_t *flags, const double *
 int pcx_slider_eval_tensor_grid(pcx_slider *h, const int32_t *deriv, const int32_t *m, const double *axes_cat, double *out);
 int pcx_slider_eval_tensor_grid_dev(pcx_slider *h, const int32_t *deriv, const int32_t *m, const double *axes_cat,
                                     double *d_out, void *stream);
+/* Ladders, batched: out[r * m + x] = pcx_slider_eval_batch (spec `deriv`, NULL = the values) at the point whose coordinate
+ * along `dim` is the x-th value of row r and whose other coordinates are fixed[r * (d - 1) + ...].  Arguments, checks and
+ * host staging as pcx_spline_ladder_batch.
+ *   value:       every slide but the owner of dim is evaluated once per row; the owner runs its own ladder
+ *                (pcx_bary_ladder_batch_dev's launch) along dim's place in its group, at the row's coordinates of the
+ *                group's other dimensions, into the result, and one kernel forms r = pivot; r += v_s - pivot, slides in
+ *                order, in place.  A one-dimensional owner with shared xs runs its ladder for ONE row (its fibre is its
+ *                tensor: the same m values for every row) and the kernel broadcasts it.
+ *   derivative:  inside the owner -> the owner's derivative ladder alone; inside another slide -> that slide's derivative
+ *                at the row, at every value (xs is not read); spread over more than one slide -> +0.0 everywhere.
+ * Rows go in chunks of 2^21 / m.  The _dev form as pcx_spline_ladder_batch_dev: on the handle's stream, complete on return. */
+int pcx_slider_ladder_batch(pcx_slider *h, int dim, const int32_t *deriv, const double *fixed, int64_t N, const double *xs,
+                            int m, int xs_per_row, double *out);
+int pcx_slider_ladder_batch_dev(pcx_slider *h, int dim, const int32_t *deriv, const double *d_fixed, int64_t N,
+                                const double *xs, int m, int xs_per_row, double *d_out, void *stream);
 
 /* ---- tensor-train interpolant ---------------------------------------------- */
 /* State of ChebyshevTT (tensor_train.py:1117-1138): Chebyshev COEFFICIENT cores

@@ -35,6 +35,8 @@ SOURCES = {
                        "route_kernels.h"],
     "pcx_piecewise_grid.hip": BARY_H + ["pcx_slider_internal.h", "pcx_spline_internal.h", "gather_kernels.h",
                                "spline_grid_plan.h", "piecewise_grid_kernels.h"],
+    "pcx_piecewise_ladder.hip": BARY_H + ["pcx_slider_internal.h", "pcx_spline_internal.h", "gather_kernels.h",
+                                 "bary_kernels.h", "bary_ladder_kernels.h", "piecewise_ladder_kernels.h"],
     "pcx_slider_box.hip": BARY_H + ["pcx_slider_internal.h", "gather_kernels.h", "slider_calc_kernels.h"],
     "pcx_tt.hip": HOST_H + ["tt_kernels.h", "tt_lpp_kernels.h", "tt_fd_kernels.h"],
     "pcx_tt_box.hip": HOST_H + ["tt_lpp_kernels.h", "tt_box_kernels.h"],

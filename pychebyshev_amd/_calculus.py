@@ -193,6 +193,35 @@ def run_ladder(lib, device: int, stream, call_host, call_dev, rows, xs, m: int, 
     return res if rows_dev else res.to_host()
 
 
+def composite_ladder(model, entry: str, dim, fixed, xs, derivative_order, derivative_id, out):
+    """``ladder_batch`` of a class built out of barycentric handles (``ChebyshevSpline``, ``ChebyshevSlider``): the
+    arguments, checks and messages of ``ChebyshevApproximation.ladder_batch``, every one of them before the model goes to
+    a device, then ``entry`` / ``entry + "_dev"`` through :func:`run_ladder`."""
+    import ctypes
+    d = model.num_dimensions
+    if derivative_order is None and derivative_id is None:
+        derivative_order = [0] * d
+    else:
+        derivative_order = model._resolve_derivative_args(derivative_order, derivative_id)
+    if not model._built:
+        raise RuntimeError("Call build() first")
+    rows = validate_fibre_args(d, dim, fixed, model.domain)
+    arr = np.asarray(derivative_order)
+    if arr.shape != (d,):
+        raise ValueError(f"derivative_order must have {d} entries, got {list(np.shape(derivative_order))}")
+    spec = _lib.i32(arr)
+    xv, m, per_row = validate_ladder_xs(xs, rows.shape[0])
+    validate_ladder_out(out, (rows.shape[0], m))
+    s = model._dev()
+    lib, h, dim = s.lib, s.handle, int(dim)
+    host, dev = getattr(lib, entry), getattr(lib, entry + "_dev")
+    return run_ladder(
+        lib, s.device, ctypes.c_void_p(),                      # the composite entries run on their handle's streams
+        lambda f, N, x, mm, pr, o: host(h, dim, _lib.p_i32(spec), f, N, x, mm, pr, o),
+        lambda f, N, x, mm, pr, o, st: dev(h, dim, _lib.p_i32(spec), f, N, x, mm, pr, o, st),
+        rows, xv, m, per_row, out)
+
+
 def validate_targets(targets, N: int, name: str = "targets") -> np.ndarray:
     """The ``(N,)`` float64 targets of an ``invert_batch`` call (a scalar serves every row), checked on the host before
     any launch: one finite value per row."""

@@ -110,6 +110,10 @@ SIGNATURES = {
     "pcx_bary_ladder_info": (_I, [_V, _I, c_i32p]),
     "pcx_tt_ladder_batch": (_I, [_V, _I, c_f64p, _L, c_f64p, _I, _I, c_f64p]),
     "pcx_tt_ladder_batch_dev": (_I, [_V, _I, _V, _L, _V, _I, _I, _V, _V]),
+    "pcx_spline_ladder_batch": (_I, [_V, _I, c_i32p, c_f64p, _L, c_f64p, _I, _I, c_f64p]),
+    "pcx_spline_ladder_batch_dev": (_I, [_V, _I, c_i32p, _V, _L, _V, _I, _I, _V, _V]),
+    "pcx_slider_ladder_batch": (_I, [_V, _I, c_i32p, c_f64p, _L, c_f64p, _I, _I, c_f64p]),
+    "pcx_slider_ladder_batch_dev": (_I, [_V, _I, c_i32p, _V, _L, _V, _I, _I, _V, _V]),
     "pcx_spline_create": (_I, [_I, _I, c_i32p, c_f64p, c_vpp, _I, c_vpp]),
     "pcx_spline_destroy": (_I, [_V]),
     "pcx_spline_eval_batch": (_I, [_V, c_f64p, _L, c_i32p, c_f64p]),

@@ -128,6 +128,14 @@ PCX_HIDDEN int bary_launch_grid(pcx_bary *h, const double *const *frag_tab, int 
 PCX_DECLARE_SEED_LAUNCHERS(1)
 PCX_DECLARE_SEED_LAUNCHERS(2)
 
+// pcx_bary_ladder.hip (BaryLadder: bary_ladder_kernels.h): the contraction plan of a ladder along `dim`, and N
+// device-resident rows queued on st -- row r reads fixed[r * fstride + i] and xs[r * xstride + x], out is N x m dense.
+// The launch's caller holds h->mu.
+struct BaryLadder;
+PCX_HIDDEN int bary_ladder_plan(const pcx_bary *h, int dim, BaryLadder *lp);
+PCX_HIDDEN int bary_ladder_launch(pcx_bary *h, const BaryLadder &lp, const int32_t *deriv, const double *d_fixed, long fstride,
+                                  const double *d_xs, long xstride, int m, long N, double *d_out, hipStream_t st);
+
 // pcx_bary.hip
 PCX_HIDDEN int bary_get_tensor(pcx_bary *h, const int32_t *deriv, DerivedTensor **out);
 PCX_HIDDEN int bary_spec_tensors(pcx_bary *h, const int32_t *derivs, int m, std::vector<DerivedTensor *> &dts,

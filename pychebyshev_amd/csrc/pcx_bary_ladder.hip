@@ -17,7 +17,7 @@ static size_t ladder_mfma_lds(const BaryLadder &lp) {
 // at least one other dimension, at most 64 nodes along dim (four column tiles of accumulators), a low part of the
 // trailing other dimensions while it stays within 256 entries (at least the last one), and a wave's tables within 64 KB
 // of LDS.  pcx_bary_set_kernel(h, 1) forces the rows form.
-static int bary_ladder_plan(const pcx_bary *h, int dim, BaryLadder *lp) {
+PCX_HIDDEN int bary_ladder_plan(const pcx_bary *h, int dim, BaryLadder *lp) {
     const BaryDims &dims = h->dims;
     const int d = dims.d;
     if (dim < 0 || dim >= d) return fail(PCX_ERR_INVALID, "dim %d out of range [0, %d]", dim, d - 1);
@@ -77,8 +77,8 @@ static int bary_ladder_image(pcx_bary *h, DerivedTensor *dt, const BaryLadder &l
 }
 
 // N device-resident rows, queued on st: row r reads fixed[r * fstride + i] and xs[r * xstride + x].  Caller holds h->mu.
-static int bary_ladder_launch(pcx_bary *h, const BaryLadder &lp, const int32_t *deriv, const double *d_fixed, long fstride,
-                              const double *d_xs, long xstride, int m, long N, double *d_out, hipStream_t st) {
+PCX_HIDDEN int bary_ladder_launch(pcx_bary *h, const BaryLadder &lp, const int32_t *deriv, const double *d_fixed, long fstride,
+                                  const double *d_xs, long xstride, int m, long N, double *d_out, hipStream_t st) {
     if (N == 0 || m == 0) return PCX_OK;
     DerivedTensor *dt = nullptr;
     h->call_mark = h->clock;

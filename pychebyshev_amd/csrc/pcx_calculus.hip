@@ -415,15 +415,6 @@ extern "C" int pcx_tt_solve_batch(pcx_tt *h, int dim, const double *fixed, const
     PCX_API_END
 }
 
-// Columns of the (d - 1)-wide fixed rows (every dimension but `dim`, increasing) that hold the dimensions `dims[0 .. nc)`.
-static SliderCols slider_fixed_cols(const int *dims, int nc, int dim) {
-    SliderCols c;
-    c.nc = nc;
-    for (int k = 0; k < PCX_MAX_DIMS; ++k) c.col[k] = 0;
-    for (int k = 0; k < nc; ++k) c.col[k] = dims[k] < dim ? dims[k] : dims[k] - 1;
-    return c;
-}
-
 static int slider_calc_impl(pcx_slider *h, int dim, const double *lo, const double *hi, const double *fixed, int64_t N,
                             int mode, double *roots_out, int32_t *counts_out, double *val_out, double *loc_out,
                             const SolveReq *sq) {

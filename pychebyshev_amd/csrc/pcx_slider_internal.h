@@ -25,4 +25,15 @@ struct pcx_slider {
     Scratch s_grid, s_gridtab, s_gridout;
     std::vector<long> grid_tab_host;
     hipEvent_t grid_done = nullptr;
+    // ladders (pcx_piecewise_ladder.hip): shared xs, a one-dimensional owner's shared ladder
+    Scratch s_ladder[2];
 };
+
+// Columns of the (d - 1)-wide fixed rows (every dimension but `dim`, increasing) that hold the dimensions `dims[0 .. nc)`.
+static SliderCols slider_fixed_cols(const int *dims, int nc, int dim) {
+    SliderCols c;
+    c.nc = nc;
+    for (int k = 0; k < PCX_MAX_DIMS; ++k) c.col[k] = 0;
+    for (int k = 0; k < nc; ++k) c.col[k] = dims[k] < dim ? dims[k] : dims[k] - 1;
+    return c;
+}

@@ -19,6 +19,7 @@ extern "C" int pcx_spline_destroy(pcx_spline *h) {
     h->s_piece.release(); h->s_perm.release(); h->s_partial.release();
     h->s_models.release(); h->s_blk.release();
     h->s_gridstage.release(); h->s_gridtab.release(); h->s_gridout.release();
+    for (Scratch &sc : h->s_ladder) sc.release();
     if (h->grid_done) (void)hipEventDestroy(h->grid_done);
     if (h->pin_stage) (void)hipHostFree(h->pin_stage);
     for (int i = 0; i < pcx_spline::kSide; ++i) {
@@ -97,6 +98,26 @@ extern "C" int pcx_spline_create(int device, int d, const int32_t *n_knots, cons
     PCX_API_END
 }
 
+// The second half of bucketing: h->s_piece holds a key in [0, n_keys) per item and h->d_counts their histogram (both queued
+// on h->stream).  Returns the per-key counts/offsets on the host and leaves the bucket permutation in h->s_perm
+// (reserved by the caller).  n_keys <= h->n_pieces.  Caller holds h->mu.
+PCX_HIDDEN int spline_scatter_keys(pcx_spline *h, long cnt, int n_keys, int lds_hist, std::vector<int> &counts,
+                                   std::vector<int> &offsets) {
+    int *piece = (int *)h->s_piece.ptr, *perm = (int *)h->s_perm.ptr;
+    const unsigned blocks = (unsigned)((cnt + PCX_SPLINE_BLOCK_POINTS - 1) / PCX_SPLINE_BLOCK_POINTS);
+    counts.assign(n_keys, 0);
+    HIP_TRY(hipMemcpyAsync(counts.data(), h->d_counts, (size_t)n_keys * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    offsets.assign(n_keys, 0);
+    int acc = 0;
+    for (int i = 0; i < n_keys; ++i) { offsets[i] = acc; acc += counts[i]; }
+    HIP_TRY(hipMemcpyAsync(h->d_counts, offsets.data(), (size_t)n_keys * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_spline_scatter, dim3(blocks), dim3(256), 0, h->stream, piece, cnt, h->d_counts, perm, n_keys, lds_hist);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->stream));   // `offsets` (pageable) must stay valid until copied
+    return PCX_OK;
+}
+
 // Route + bucket cnt device-resident points; returns the per-piece counts/offsets on the host
 // and leaves the bucket permutation in h->s_perm.  Caller holds h->mu.
 static int spline_bucket(pcx_spline *h, const double *dp, long cnt, std::vector<int> &counts,
@@ -105,24 +126,14 @@ static int spline_bucket(pcx_spline *h, const double *dp, long cnt, std::vector<
     if (rc) return rc;
     rc = h->s_perm.reserve((size_t)cnt * sizeof(int));
     if (rc) return rc;
-    int *piece = (int *)h->s_piece.ptr, *perm = (int *)h->s_perm.ptr;
+    int *piece = (int *)h->s_piece.ptr;
     HIP_TRY(hipMemsetAsync(h->d_counts, 0, (size_t)h->n_pieces * sizeof(int), h->stream));
     const unsigned blocks = (unsigned)((cnt + PCX_SPLINE_BLOCK_POINTS - 1) / PCX_SPLINE_BLOCK_POINTS);
     const int lds_hist = h->lds_hist;
     hipLaunchKernelGGL(k_spline_piece_id, dim3(blocks), dim3(256), 0, h->stream, h->sd, h->d_knots, dp, cnt, piece, h->d_counts,
                        h->n_pieces, lds_hist);
     HIP_TRY(hipGetLastError());
-    counts.assign(h->n_pieces, 0);
-    HIP_TRY(hipMemcpyAsync(counts.data(), h->d_counts, (size_t)h->n_pieces * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    offsets.assign(h->n_pieces, 0);
-    int acc = 0;
-    for (int i = 0; i < h->n_pieces; ++i) { offsets[i] = acc; acc += counts[i]; }
-    HIP_TRY(hipMemcpyAsync(h->d_counts, offsets.data(), (size_t)h->n_pieces * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_spline_scatter, dim3(blocks), dim3(256), 0, h->stream, piece, cnt, h->d_counts, perm, h->n_pieces, lds_hist);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->stream));   // `offsets` (pageable) must stay valid until copied
-    return PCX_OK;
+    return spline_scatter_keys(h, cnt, h->n_pieces, lds_hist, counts, offsets);
 }
 
 
@@ -373,6 +384,7 @@ extern "C" int pcx_slider_destroy(pcx_slider *h) {
     h->stage.release();
     h->s_cols.release(); h->s_vals.release(); h->s_partial.release();
     h->s_grid.release(); h->s_gridtab.release(); h->s_gridout.release();
+    for (Scratch &sc : h->s_ladder) sc.release();
     if (h->grid_done) (void)hipEventDestroy(h->grid_done);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;

@@ -37,9 +37,17 @@ struct pcx_spline {
     Scratch s_gridstage, s_gridtab, s_gridout;
     std::vector<long> grid_tab_host;
     hipEvent_t grid_done = nullptr;
+    // ladders (pcx_piecewise_ladder.hip): the per-index table, the rows in bucket order, their slots, the fibres, shared xs
+    Scratch s_ladder[5];
 };
 
 // pcx_spline.hip: one chunk of cnt device-resident points (cnt x d) through routing, bucketing and the per-piece
 // launches on h->stream, m specs (derivs NULL: the values), results into dout (cnt x m) in point order; the launches are
 // queued, not awaited.  Caller holds h->mu.
 PCX_HIDDEN int spline_eval_chunk(pcx_spline *h, const double *dp, long cnt, const int32_t *derivs, int m, double *dout);
+// pcx_spline.hip: the second half of bucketing, for keys somebody else wrote (pcx_piecewise_ladder.hip buckets rows by
+// cross-section).  h->s_piece holds cnt keys in [0, n_keys), h->d_counts their histogram, both queued on h->stream;
+// h->s_perm is reserved.  Returns counts / offsets on the host and the permutation in h->s_perm, complete.  n_keys <=
+// h->n_pieces; lds_hist as in the handle.  Caller holds h->mu.
+PCX_HIDDEN int spline_scatter_keys(pcx_spline *h, long cnt, int n_keys, int lds_hist, std::vector<int> &counts,
+                                   std::vector<int> &offsets);

@@ -653,6 +653,38 @@ class ChebyshevSlider(ErgonomicsMixin, DerivativeIdMixin):
         val, loc, _ = self._calculus_batch(int(dim), rows, 2)
         return val, loc
 
+    def ladder_batch(self, dim: int, fixed, xs, derivative_order=None, *, derivative_id=None, out=None):
+        """The slider along ``dim`` at ``m`` values for every row of ``fixed`` (extension; a spot or vol ladder over a
+        wide book): ``result[r, x] = eval(point, derivative_order)`` at the point whose coordinate along ``dim`` is the
+        row's x-th value and whose other coordinates are ``fixed[r]``, shape ``(N, m)``.
+
+        ``fixed``, ``xs``, ``derivative_order`` / ``derivative_id``, ``out`` and device arrays exactly as in
+        ``ChebyshevApproximation.ladder_batch``: host ``fixed`` outside its domain raises ``ValueError`` before any
+        device call, ``xs`` is never checked, a NaN in ``xs`` gives NaN in its own cell; ``m = 0`` returns ``(N, 0)``
+        without a launch.
+
+        Only the slide that owns ``dim`` varies along a ladder (``pcx_slider_ladder_batch``): it runs its own
+        ``ladder_batch`` launch, one contraction per row; every other slide is evaluated once per row, not ``m`` times,
+        and one kernel forms ``pivot + sum_s (v_s - pivot)``, slides in order, so the result is bit for bit the host
+        composition of the slides' own ``ladder_batch`` / ``vectorized_eval_batch`` results.  A NaN in ``fixed`` makes
+        its row NaN.  Derivatives follow :meth:`eval`: a spec inside the owner slide is the owner's derivative ladder
+        alone (a NaN among the other slides' coordinates then does not show); one inside another slide is that slide's
+        derivative at the row, at every value (``xs`` is then not read: a NaN there does not show); one that spans two
+        slides or more is ``+0.0`` everywhere."""
+        return _calculus.composite_ladder(self, "pcx_slider_ladder_batch", dim, fixed, xs, derivative_order, derivative_id, out)
+
+    def fibre_batch(self, dim: int, fixed, derivative_order=None, *, derivative_id=None, out=None):
+        """Every row's restriction to ``dim`` at that dimension's own nodes, ``(N, n_dim)``: :meth:`ladder_batch` at the
+        nodes of the slide that owns ``dim`` (ascending), bit for bit."""
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        if isinstance(dim, bool) or not isinstance(dim, (int, np.integer)):
+            raise TypeError(f"dim must be an int, got {type(dim).__name__}")
+        if dim < 0 or dim >= self.num_dimensions:
+            raise ValueError(f"dim {dim} out of range [0, {self.num_dimensions - 1}]")
+        return self.ladder_batch(dim, fixed, np.asarray(self._owner_grid(int(dim))[0], dtype=float), derivative_order,
+                                 derivative_id=derivative_id, out=out)
+
     # ---------------------------------------------------------------- misc
     @property
     def total_build_evals(self) -> int:

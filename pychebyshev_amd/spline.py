@@ -649,6 +649,42 @@ class ChebyshevSpline(ErgonomicsMixin, DerivativeIdMixin):
         val, loc, _ = self._calculus_batch(int(dim), rows, 2)
         return val, loc
 
+    def ladder_batch(self, dim: int, fixed, xs, derivative_order=None, *, derivative_id=None, out=None):
+        """The spline along ``dim`` at ``m`` values for every row of ``fixed`` (extension; a spot ladder over a kinked
+        payoff): ``result[r, x] = eval_batch(point, derivative_order)`` at the point whose coordinate along ``dim`` is the
+        row's x-th value and whose other coordinates are ``fixed[r]``, shape ``(N, m)`` -- ``eval_batch``'s rule, not
+        ``eval``'s, as in :meth:`eval_grid`: a coordinate on a knot belongs to the right-hand piece, one outside the
+        domain to the end piece, a NaN to the last piece, and a derivative spec is not checked against the knots.
+
+        ``fixed``, ``xs``, ``derivative_order`` / ``derivative_id``, ``out`` and device arrays exactly as in
+        ``ChebyshevApproximation.ladder_batch``: host ``fixed`` outside its domain raises ``ValueError`` before any
+        device call, ``xs`` is never checked, a NaN in ``xs`` gives NaN in its own cell, a NaN in ``fixed`` its row;
+        ``m = 0`` returns ``(N, 0)`` without a launch.
+
+        Rows, not points, are routed (``pcx_spline_ladder_batch``): ``fixed[r]`` selects the row's piece index in every
+        dimension but ``dim``, the rows are bucketed by that cross-section, every piece of a non-empty cross-section
+        whose interval along ``dim`` holds a value of the call contracts its fibres once per row (its own
+        ``ladder_batch`` launch at its own nodes), and one kernel interpolates each cell on the fibre of the piece its
+        value falls into.  ``result[r, x]`` is bit for bit what that piece's own ``ladder_batch`` gives for the row and
+        value, and depends neither on the batch, nor on ``m``, nor on whether ``xs`` is shared.  Pieces that share an
+        interval of ``dim`` must have the same node count there."""
+        from . import _calculus
+        return _calculus.composite_ladder(self, "pcx_spline_ladder_batch", dim, fixed, xs, derivative_order, derivative_id, out)
+
+    def fibre_batch(self, dim: int, fixed, derivative_order=None, *, derivative_id=None, out=None):
+        """Every row's fibres along ``dim``, ``(N, sum_j n_j)``: the fibres of the pieces along ``dim`` in piece order,
+        nodes ascending -- the values the calculus batches expand into points, from one contraction per row and piece.
+        Type-1 nodes never sit on a knot, so this is :meth:`ladder_batch` at the concatenated nodes, bit for bit."""
+        if not self._built:
+            raise RuntimeError("Call build() first")
+        if isinstance(dim, bool) or not isinstance(dim, (int, np.integer)):
+            raise TypeError(f"dim must be an int, got {type(dim).__name__}")
+        if dim < 0 or dim >= self.num_dimensions:
+            raise ValueError(f"dim {dim} out of range [0, {self.num_dimensions - 1}]")
+        stride = int(np.prod(self._shape[dim + 1:], dtype=int))
+        nodes = np.concatenate([np.asarray(self._pieces[j * stride].nodes[dim], dtype=float) for j in range(self._shape[dim])])
+        return self.ladder_batch(dim, fixed, nodes, derivative_order, derivative_id=derivative_id, out=out)
+
     # ---------------------------------------------------------------- extrude / slice
     def _reshaped(self, pieces, domain, knots, n_nodes) -> "ChebyshevSpline":
         """A built spline over other dimensions than this one's: ``function=None``, no device handle yet, the form of
