@@ -1,6 +1,7 @@
-"""Arithmetic on interpolants: the operand checks shared by the operators of the four classes, the
-block-diagonal stacking of two tensor trains, and the device calls that round a tensor train
-(``pcx_tt_round``) or swap its storage axes (``pcx_tt_reorder``).
+"""Arithmetic on interpolants: the operand checks shared by the operators of the four classes, the operators
+of the three classes that hold value tensors (:class:`ValueAlgebraMixin`), the block-diagonal stacking of two
+tensor trains, and the device calls that round a tensor train (``pcx_tt_round``) or swap its storage axes
+(``pcx_tt_reorder``).
 
 Dense, spline and slider operators combine value tensors with NumPy on the host: the result is a new
 interpolant whose device model is built on its first evaluation, so the intermediate results of a chain
@@ -10,6 +11,8 @@ on the device.
 from __future__ import annotations
 
 import ctypes
+import itertools
+import operator
 
 import numpy as np
 
@@ -38,6 +41,77 @@ def check_compatible(a, b) -> None:
         raise ValueError(f"Domain mismatch: {a.domain} vs {b.domain}")
     if a.max_derivative_order != b.max_derivative_order:
         raise ValueError(f"max_derivative_order mismatch: {a.max_derivative_order} vs {b.max_derivative_order}")
+
+
+def leaves(other, attr: str):
+    """What pairs with a composite's leaves in an operator: ``other``'s own leaves (``attr``), or the scalar itself
+    for each."""
+    return getattr(other, attr) if hasattr(other, attr) else itertools.repeat(other)
+
+
+class ValueAlgebraMixin:
+    """The ten arithmetic operators of the classes that hold value tensors (dense, spline, slider; reference
+    barycentric.py:2433-2500, spline.py:1912-2010, slider.py:1285-1390).  The host class supplies
+
+    * ``_check_operand(other)``: its compatibility check (default :func:`check_compatible`);
+    * ``_leafwise(op, other)``: a new object with ``op(a, b)`` on every value tensor ``a`` -- ``b`` is the matching
+      tensor of ``other``, or ``other`` itself when it is a float;
+    * ``_leafwise_inplace(op, other)``: the same in place.  It rebinds ``tensor_values`` to a new array and clears
+      ``_cached_error_estimate`` on the leaves and the owner: the device copies recognise staleness by the identity of
+      that array, so it is never modified in place.
+
+    ``op`` is ``operator.add``, ``operator.sub`` or ``operator.mul`` (with ``float(scalar)``)."""
+
+    _check_operand = check_compatible
+
+    def __add__(self, other):
+        if type(self) is not type(other):
+            return NotImplemented
+        self._check_operand(other)
+        return self._leafwise(operator.add, other)
+
+    def __sub__(self, other):
+        if type(self) is not type(other):
+            return NotImplemented
+        self._check_operand(other)
+        return self._leafwise(operator.sub, other)
+
+    def __mul__(self, scalar):
+        if not is_scalar(scalar):
+            return NotImplemented
+        return self._leafwise(operator.mul, float(scalar))
+
+    def __rmul__(self, scalar):
+        return self.__mul__(scalar)
+
+    def __truediv__(self, scalar):
+        if not is_scalar(scalar):
+            return NotImplemented
+        return self.__mul__(1.0 / float(scalar))
+
+    def __neg__(self):
+        return self.__mul__(-1.0)
+
+    def __iadd__(self, other):
+        self._check_operand(other)
+        self._leafwise_inplace(operator.add, other)
+        return self
+
+    def __isub__(self, other):
+        self._check_operand(other)
+        self._leafwise_inplace(operator.sub, other)
+        return self
+
+    def __imul__(self, scalar):
+        if not is_scalar(scalar):
+            return NotImplemented
+        self._leafwise_inplace(operator.mul, float(scalar))
+        return self
+
+    def __itruediv__(self, scalar):
+        if not is_scalar(scalar):
+            return NotImplemented
+        return self.__imul__(1.0 / float(scalar))
 
 
 # --------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
-"""Roots, minima and maxima of an interpolant along one dimension: argument rules, the batch driver and the host
-restatement (reference ``_calculus.py:198-355``).
+"""Roots, minima and maxima of an interpolant along one dimension: argument rules, the batch driver, the front end the
+four model classes share (:class:`FibreCalculusMixin`) and the host restatement (reference ``_calculus.py:198-355``).
 
 Every fibre of at most :data:`MAX_DEVICE_N` nodes is solved on the device (``pcx_*_calculus_batch``,
 ``csrc/calculus_kernels.h``).  Longer fibres still come from the device, and the single calls then finish here with
@@ -53,47 +53,42 @@ def fixed_row(ndim: int, dim: int, params) -> np.ndarray:
     return np.array([[float(vals[k]) for k in range(ndim) if k != dim]], dtype=float).reshape(1, ndim - 1)
 
 
-def validate_batch_args(ndim: int, dim, fixed, domain, n_nodes) -> np.ndarray:
-    """The ``(N, ndim - 1)`` float64 rows of a batch call along ``dim`` (``n_nodes`` and ``domain`` by dimension),
-    checked on the host before any launch."""
+def validate_dim(ndim: int, dim) -> None:
+    """``dim`` of a batch call: an int (no bool) in ``[0, ndim)``."""
     if isinstance(dim, bool) or not isinstance(dim, (int, np.integer)):
         raise TypeError(f"dim must be an int, got {type(dim).__name__}")
     if dim < 0 or dim >= ndim:
         raise ValueError(f"dim {dim} out of range [0, {ndim - 1}]")
+
+
+def validate_batch_args(ndim: int, dim, fixed, domain, n_nodes) -> np.ndarray:
+    """The ``(N, ndim - 1)`` float64 rows of a batch call along ``dim`` (``n_nodes`` and ``domain`` by dimension),
+    checked on the host before any launch: ``dim``, the 64-node cap of the solver along it, then the rows."""
+    validate_dim(ndim, dim)
     n = int(n_nodes[dim])
     if n > MAX_DEVICE_N:
         raise ValueError(f"dimension {dim} has {n} nodes: the batched solver takes at most {MAX_DEVICE_N} "
                          f"(the single-row calls handle more on the host)")
-    rows = np.ascontiguousarray(np.asarray(fixed, dtype=np.float64))
-    if ndim == 1 and rows.ndim == 1 and rows.size == 0:
-        rows = rows.reshape(0, 0)
-    if rows.ndim != 2 or rows.shape[1] != ndim - 1:
-        raise ValueError(f"fixed must have shape (N, {ndim - 1}), got {rows.shape}")
-    others = [k for k in range(ndim) if k != dim]
-    for c, k in enumerate(others):
-        lo, hi = domain[k]
-        bad = np.nonzero((rows[:, c] < lo) | (rows[:, c] > hi))[0]
-        if bad.size:
-            r = int(bad[0])
-            raise ValueError(f"Fixed value {rows[r, c]} for dim {k} outside domain [{lo}, {hi}] (row {r})")
-    return rows
+    return _host_rows(ndim, dim, fixed, domain)
 
 
 def validate_fibre_args(ndim: int, dim, fixed, domain):
-    """:func:`validate_batch_args` for the calls that need no solver (``ladder_batch`` / ``fibre_batch``): the same
+    """The rows of the calls that need no solver (``ladder_batch`` / ``fibre_batch``): :func:`validate_batch_args`'s
     checks and messages without the 64-node cap along ``dim``.  NaN passes the domain check (it makes its row NaN).
     ``fixed`` may be a device array: its shape is checked here, its values are not (they would have to come to the
     host first); it is returned as the ``DeviceArray``."""
     from .device import as_device_array
-    if isinstance(dim, bool) or not isinstance(dim, (int, np.integer)):
-        raise TypeError(f"dim must be an int, got {type(dim).__name__}")
-    if dim < 0 or dim >= ndim:
-        raise ValueError(f"dim {dim} out of range [0, {ndim - 1}]")
+    validate_dim(ndim, dim)
     dev = as_device_array(fixed)
     if dev is not None:
         if dev.ndim != 2 or dev.shape[1] != ndim - 1:
             raise ValueError(f"fixed must have shape (N, {ndim - 1}), got {dev.shape}")
         return dev
+    return _host_rows(ndim, dim, fixed, domain)
+
+
+def _host_rows(ndim: int, dim: int, fixed, domain) -> np.ndarray:
+    """Host ``fixed`` as ``(N, ndim - 1)`` float64 rows, every value inside its dimension's domain (NaN passes)."""
     rows = np.ascontiguousarray(np.asarray(fixed, dtype=np.float64))
     if ndim == 1 and rows.ndim == 1 and rows.size == 0:
         rows = rows.reshape(0, 0)
@@ -191,35 +186,6 @@ def run_ladder(lib, device: int, stream, call_host, call_dev, rows, xs, m: int, 
     if dev_out is not None:
         return out
     return res if rows_dev else res.to_host()
-
-
-def composite_ladder(model, entry: str, dim, fixed, xs, derivative_order, derivative_id, out):
-    """``ladder_batch`` of a class built out of barycentric handles (``ChebyshevSpline``, ``ChebyshevSlider``): the
-    arguments, checks and messages of ``ChebyshevApproximation.ladder_batch``, every one of them before the model goes to
-    a device, then ``entry`` / ``entry + "_dev"`` through :func:`run_ladder`."""
-    import ctypes
-    d = model.num_dimensions
-    if derivative_order is None and derivative_id is None:
-        derivative_order = [0] * d
-    else:
-        derivative_order = model._resolve_derivative_args(derivative_order, derivative_id)
-    if not model._built:
-        raise RuntimeError("Call build() first")
-    rows = validate_fibre_args(d, dim, fixed, model.domain)
-    arr = np.asarray(derivative_order)
-    if arr.shape != (d,):
-        raise ValueError(f"derivative_order must have {d} entries, got {list(np.shape(derivative_order))}")
-    spec = _lib.i32(arr)
-    xv, m, per_row = validate_ladder_xs(xs, rows.shape[0])
-    validate_ladder_out(out, (rows.shape[0], m))
-    s = model._dev()
-    lib, h, dim = s.lib, s.handle, int(dim)
-    host, dev = getattr(lib, entry), getattr(lib, entry + "_dev")
-    return run_ladder(
-        lib, s.device, ctypes.c_void_p(),                      # the composite entries run on their handle's streams
-        lambda f, N, x, mm, pr, o: host(h, dim, _lib.p_i32(spec), f, N, x, mm, pr, o),
-        lambda f, N, x, mm, pr, o, st: dev(h, dim, _lib.p_i32(spec), f, N, x, mm, pr, o, st),
-        rows, xv, m, per_row, out)
 
 
 def validate_targets(targets, N: int, name: str = "targets") -> np.ndarray:
@@ -574,6 +540,221 @@ def run_single_level(fibre_fn, solve_fn, n: int, level: np.ndarray, domain):
     if n <= MAX_DEVICE_N:
         return single_roots(*solve_fn())
     return roots_1d(np.asarray(fibre_fn(), dtype=float) - float(level[0]), domain)
+
+
+# ---------------------------------------------------------------------------------------------- the front end
+class FibreCalculusMixin:
+    """The operations along one dimension of the four model classes: ``roots`` / ``minimize`` / ``maximize``, their
+    ``_batch`` forms, ``invert_batch``, ``fibre_batch`` and the driver of ``ladder_batch``.  Needs ``num_dimensions``,
+    ``domain``, ``n_nodes`` and ``_built`` on the host class, and:
+
+    * ``_fibre_prefix``: the prefix of the class's C entries (``"pcx_bary"``, ``"pcx_spline"``, ``"pcx_slider"``,
+      ``"pcx_tt"``); ``_ladder_own_stream``: whether its ladder runs on the stream ``<prefix>_stream`` reports (dense,
+      TT) or on the handle's own streams (the composites: the null stream is passed);
+    * ``_fibre_grid(dim)`` -> ``(nodes, weights, diff, (a, b))`` of a dimension and ``_fibre_values(points)``, the model
+      without a derivative at ``(n, d)`` points -- what a single call above 64 nodes finishes on the host with.
+
+    A class overrides, where its own differ: ``_fibre_check_built()`` (default: ``_built``), ``_fibre_domain()`` and
+    ``_fibre_counts()`` (domain and node counts by user dimension; default ``domain`` / ``n_nodes``),
+    ``_fibre_handle()`` (default ``_dev()``), ``_domain_arrays()`` (what the two solver entries take between ``dim``
+    and the rows; default the domain's ends) and ``_fibre_shape(dim)`` (``(n, width)`` of the batch results).  The
+    public methods reach the device through ``self._calculus_batch`` / ``self._solve_batch`` only."""
+
+    _ladder_own_stream = False
+
+    # ------------------------------------------------------------ hooks
+    def _fibre_check_built(self) -> None:
+        if not self._built:
+            raise RuntimeError("Call build() first")
+
+    def _fibre_domain(self):
+        return self.domain
+
+    def _fibre_counts(self):
+        return self.n_nodes
+
+    def _fibre_handle(self):
+        return self._dev()
+
+    def _domain_arrays(self):
+        """The leading arguments of the two solver entries, between ``dim`` and the rows: the domain's lower and upper
+        ends by dimension; empty for the TT, whose handle knows its domain."""
+        dom = np.asarray(self.domain, dtype=float)
+        return _lib.f64(dom[:, 0]), _lib.f64(dom[:, 1])
+
+    def _fibre_shape(self, dim: int):
+        return int(self._fibre_counts()[dim]), None
+
+    def _fibre_nodes(self, dim: int) -> np.ndarray:
+        """The values ``fibre_batch`` takes the ladder at."""
+        return np.asarray(self._fibre_grid(dim)[0], dtype=float)
+
+    # ------------------------------------------------------------ the two device entries
+    def _calculus_batch(self, dim: int, rows: np.ndarray, mode: int):
+        """``<prefix>_calculus_batch`` over validated rows (see :func:`run_batch`)."""
+        n, width = self._fibre_shape(dim)
+        h = self._fibre_handle()
+        entry = getattr(h.lib, self._fibre_prefix + "_calculus_batch")
+        lead = self._domain_arrays()
+        rows = _lib.f64(rows)
+        N = rows.shape[0]
+
+        def call(r, c, v, loc):
+            return entry(h.handle, int(dim), *map(_lib.p_f64, lead), _lib.p_f64(rows), N, mode, r, c, v, loc)
+        return run_batch(call, h.lib, n, N, mode, width=width)
+
+    def _solve_batch(self, dim: int, rows: np.ndarray, targets: np.ndarray, method: int):
+        """``<prefix>_solve_batch`` over validated rows and targets (see :func:`run_solve`)."""
+        n, width = self._fibre_shape(dim)
+        h = self._fibre_handle()
+        entry = getattr(h.lib, self._fibre_prefix + "_solve_batch")
+        lead = self._domain_arrays()
+        rows, targets = _lib.f64(rows), _lib.f64(targets)
+        N = rows.shape[0]
+
+        def call(r, c, x, s):
+            return entry(h.handle, int(dim), *map(_lib.p_f64, lead), _lib.p_f64(rows), _lib.p_f64(targets), N, method,
+                         r, c, x, s)
+        return run_solve(call, h.lib, n, N, method, width=width)
+
+    # ------------------------------------------------------------ single calls
+    def _single_args(self, dim, fixed):
+        """A single call's validated ``dim``, its one batch row, the node count along ``dim``, the device-evaluated
+        fibre for the host finish (a callable) and that dimension's grid."""
+        self._fibre_check_built()
+        d = self.num_dimensions
+        dim, params = validate_calculus_args(d, dim, fixed, self._fibre_domain())
+        row = fixed_row(d, dim, params)
+        grid = self._fibre_grid(dim)
+        return dim, row, int(self._fibre_counts()[dim]), lambda: self._fibre_values(fibre_points(d, dim, row, grid[0])), grid
+
+    def _calculus(self, dim, fixed, mode: str):
+        dim, row, n, fibre, grid = self._single_args(dim, fixed)
+        return run_single(fibre, lambda m: self._calculus_batch(dim, row, m), n, mode, *grid)
+
+    def _level_roots(self, dim, fixed, level: np.ndarray) -> np.ndarray:
+        dim, row, n, fibre, grid = self._single_args(dim, fixed)
+        return run_single_level(fibre, lambda: self._solve_batch(dim, row, level, 0), n, level, grid[3])
+
+    def roots(self, dim=None, fixed=None, *, level=0.0) -> np.ndarray:
+        """Sorted real roots along ``dim`` with every other dimension fixed (``fixed = {dim_index: value}``) by the
+        colleague-matrix method.  The fibre is evaluated and solved on the device; above 64 nodes the solve runs on the
+        host (NumPy ``chebroots``).  A non-finite fibre raises ``numpy.linalg.LinAlgError``.  Unlike the reference, which
+        clips from outside only, a root within ``1e-10`` (of the half-width) of an end of the domain along ``dim``, on
+        either side of it, is returned as exactly that end; the batched forms and the critical points of
+        :meth:`minimize` / :meth:`maximize` follow the same rule.
+
+        ``level`` (keyword only, a finite scalar) asks for the solutions of ``p = level`` instead: the level is
+        subtracted from the fibre on the device, one rounding per value, before the same solver.  ``None`` or ``0.0``
+        is the call without a level, the same launches and bits."""
+        lv = validate_level(level, 1)
+        if lv is None:
+            return self._calculus(dim, fixed, "roots")
+        return self._level_roots(dim, fixed, lv)
+
+    def minimize(self, dim=None, fixed=None):
+        """``(value, location)`` of the minimum along ``dim``: the roots of the derivative series and the two ends are
+        the candidates, the first smallest value wins.  A critical point within ``1e-10`` of an end is that end (see
+        :meth:`roots`)."""
+        return self._calculus(dim, fixed, "min")
+
+    def maximize(self, dim=None, fixed=None):
+        """``(value, location)`` of the maximum along ``dim``, as :meth:`minimize`."""
+        return self._calculus(dim, fixed, "max")
+
+    # ------------------------------------------------------------ batches
+    def _calculus_rows(self, dim, fixed) -> np.ndarray:
+        self._fibre_check_built()
+        return validate_batch_args(self.num_dimensions, dim, fixed, self._fibre_domain(), self._fibre_counts())
+
+    def roots_batch(self, dim: int, fixed, *, level=None):
+        """Roots along ``dim`` for every row of ``fixed`` (host float64 ``(N, d-1)``: the other dimensions in
+        increasing order), in one device pass (extension).  Returns ``(roots, counts)``: ``roots`` float64
+        ``(N, max(n_dim-1, 1))`` ascending and NaN-padded, ``counts`` int32 ``(N,)``, -1 where the fibre was not finite
+        or the eigenvalue iteration failed.  At most 64 nodes along ``dim``.
+
+        ``level`` (keyword only, a finite scalar or an ``(N,)`` array, one level per row) asks for the solutions of
+        ``p = level`` instead: the level is subtracted from the fibre on the device, one rounding per value, before the
+        same solver.  ``None`` or ``0.0`` is the call without a level, the same launches and bits."""
+        rows = self._calculus_rows(dim, fixed)
+        lv = validate_level(level, rows.shape[0])
+        if lv is None:
+            return self._calculus_batch(int(dim), rows, 0)
+        return self._solve_batch(int(dim), rows, lv, 0)
+
+    def invert_batch(self, dim: int, fixed, targets):
+        """The value of dimension ``dim`` at which the model equals each row's target (extension; the class's
+        ``pcx_bary_solve_batch`` / ``pcx_spline_solve_batch`` / ``pcx_slider_solve_batch`` / ``pcx_tt_solve_batch``,
+        method 1): ``fixed`` as in :meth:`roots_batch`, ``targets`` a finite scalar or ``(N,)`` array.  Returns
+        ``(x (N,) float64, status (N,) int32)``.  On the knots ``[lo, nodes..., hi]`` of the fibre
+        a segment brackets when the value at its lower knot equals the target or ``p - target`` changes sign across it;
+        ``status`` is the number of bracketing segments: ``0`` the target is not reached on the knots (``x`` NaN),
+        ``1`` unique on the knots, ``> 1`` not unique (``x`` is the lowest), ``-1`` the fibre is not finite or the
+        solver's fixed iteration cap was reached (``x`` NaN).  ``x`` is the knot itself where the value equals the
+        target there, else the root inside the lowest bracketing segment, down to adjacent doubles.  A constant fibre
+        equal to its target gives ``status = n + 2`` and ``x = lo`` when the sums at the two ends return the constant
+        itself (a power of two, zero), else n to n + 2.  A root closer to 0 than ``2^-9 max(|lo|, |hi|)`` is returned to
+        within ``2^-10 eps max(|lo|, |hi|)``, not to adjacent doubles.  Only crossings between knots are seen: two
+        solutions inside one node interval are invisible here, and ``roots_batch(level=)`` finds them.  At most 64
+        nodes along ``dim``.  One device lane solves one row (``csrc/invert_kernels.h``)."""
+        rows = self._calculus_rows(dim, fixed)
+        return self._solve_batch(int(dim), rows, validate_targets(targets, rows.shape[0]), 1)
+
+    def minimize_batch(self, dim: int, fixed):
+        """``(values, locations)``, float64 ``(N,)``, of the minimum along ``dim`` for every row of ``fixed``
+        (extension; arguments as :meth:`roots_batch`).  NaN where a row failed."""
+        rows = self._calculus_rows(dim, fixed)
+        val, loc, _ = self._calculus_batch(int(dim), rows, 1)
+        return val, loc
+
+    def maximize_batch(self, dim: int, fixed):
+        """``(values, locations)`` of the maximum along ``dim`` for every row of ``fixed`` (extension)."""
+        rows = self._calculus_rows(dim, fixed)
+        val, loc, _ = self._calculus_batch(int(dim), rows, 2)
+        return val, loc
+
+    # ------------------------------------------------------------ ladders and fibres
+    def _ladder_orders(self, derivative_order, derivative_id):
+        """The derivative orders of a ladder call: no spec at all is the value."""
+        if derivative_order is None and derivative_id is None:
+            return [0] * self.num_dimensions
+        return self._resolve_derivative_args(derivative_order, derivative_id)
+
+    def _ladder(self, dim, fixed, xs, out, orders=None):
+        """``ladder_batch`` over resolved derivative ``orders`` (None: the class's entries take no spec): every check
+        before the model goes to a device, then ``<prefix>_ladder_batch`` / ``_dev`` through :func:`run_ladder`."""
+        import ctypes
+        self._fibre_check_built()
+        d = self.num_dimensions
+        rows = validate_fibre_args(d, dim, fixed, self._fibre_domain())
+        spec = ()
+        if orders is not None:
+            arr = np.asarray(orders)
+            if arr.shape != (d,):
+                raise ValueError(f"derivative_order must have {d} entries, got {list(np.shape(orders))}")
+            arr = _lib.i32(arr)
+            spec = (_lib.p_i32(arr),)
+        xv, m, per_row = validate_ladder_xs(xs, rows.shape[0])
+        validate_ladder_out(out, (rows.shape[0], m))                    # refused before the model goes to a device
+        s = self._fibre_handle()
+        lib, h, dim = s.lib, s.handle, int(dim)
+        st = ctypes.c_void_p()                                          # null: the composites run on their handle's streams
+        if self._ladder_own_stream:
+            _lib.check(getattr(lib, self._fibre_prefix + "_stream")(h, ctypes.byref(st)), lib)
+        host, dev = (getattr(lib, self._fibre_prefix + name) for name in ("_ladder_batch", "_ladder_batch_dev"))
+        return run_ladder(
+            lib, s.device, st,
+            lambda f, N, x, mm, pr, o: host(h, dim, *spec, f, N, x, mm, pr, o),
+            lambda f, N, x, mm, pr, o, stream: dev(h, dim, *spec, f, N, x, mm, pr, o, stream),
+            rows, xv, m, per_row, out)
+
+    def fibre_batch(self, dim: int, fixed, derivative_order=None, *, derivative_id=None, out=None):
+        """Every row's restriction to ``dim`` at that dimension's own nodes (ascending), ``(N, n_dim)``:
+        :meth:`ladder_batch` at those nodes, bit for bit."""
+        self._fibre_check_built()
+        validate_dim(self.num_dimensions, dim)
+        return self.ladder_batch(dim, fixed, self._fibre_nodes(int(dim)), derivative_order, derivative_id=derivative_id,
+                                 out=out)
 
 
 # ---------------------------------------------------------------------------------------------- box integrals

@@ -36,6 +36,8 @@ import numpy as np
 from numpy.polynomial.chebyshev import chebpts1
 
 from . import _algebra, _lib
+from ._algebra import ValueAlgebraMixin
+from ._calculus import FibreCalculusMixin
 from ._derivative_ids import DerivativeIdMixin
 from ._ergonomics import ErgonomicsMixin
 from ._version import __version__
@@ -294,7 +296,7 @@ class _DeviceModel:
             pass
 
 
-class ChebyshevApproximation(ErgonomicsMixin, DerivativeIdMixin):
+class ChebyshevApproximation(ErgonomicsMixin, DerivativeIdMixin, FibreCalculusMixin, ValueAlgebraMixin):
     """Multi-dimensional Chebyshev interpolant evaluated on the GPU.
 
     Parameters mirror the reference (barycentric.py:341-355).  ``function(point, data)``
@@ -952,65 +954,21 @@ class ChebyshevApproximation(ErgonomicsMixin, DerivativeIdMixin):
         return self._reduced(np.ascontiguousarray(tensor), nodes, weights, diffs, domain, n_nodes)
 
     # ---------------------------------------------------------------- algebra
-    # Reference barycentric.py:2433-2500.  The value tensors are combined with NumPy; the result shares this
-    # object's nodes, weights and differentiation matrices, and its device model is built on first evaluation.
-    # The in-place forms rebind tensor_values to a new array: the device copy is recognised as stale by the
-    # identity of that array (_DeviceModel.tensor_ref), so it must never be modified in place.
+    # Reference barycentric.py:2433-2500; the operators are _algebra.ValueAlgebraMixin's.  The value tensors are
+    # combined with NumPy; the result shares this object's nodes, weights and differentiation matrices, and its
+    # device model is built on first evaluation.  The in-place forms rebind tensor_values to a new array: the device
+    # copy is recognised as stale by the identity of that array (_DeviceModel.tensor_ref), so it must never be
+    # modified in place.
     def _combined(self, tensor) -> "ChebyshevApproximation":
         return self._reduced(tensor, self.nodes, self.weights, self.diff_matrices,
                              [list(b) for b in self.domain], list(self.n_nodes))
 
-    def __add__(self, other):
-        if type(self) is not type(other):
-            return NotImplemented
-        _algebra.check_compatible(self, other)
-        return self._combined(self.tensor_values + other.tensor_values)
+    def _leafwise(self, op, other) -> "ChebyshevApproximation":
+        return self._combined(op(self.tensor_values, getattr(other, "tensor_values", other)))
 
-    def __sub__(self, other):
-        if type(self) is not type(other):
-            return NotImplemented
-        _algebra.check_compatible(self, other)
-        return self._combined(self.tensor_values - other.tensor_values)
-
-    def __mul__(self, scalar):
-        if not _algebra.is_scalar(scalar):
-            return NotImplemented
-        return self._combined(self.tensor_values * float(scalar))
-
-    def __rmul__(self, scalar):
-        return self.__mul__(scalar)
-
-    def __truediv__(self, scalar):
-        if not _algebra.is_scalar(scalar):
-            return NotImplemented
-        return self.__mul__(1.0 / float(scalar))
-
-    def __neg__(self):
-        return self.__mul__(-1.0)
-
-    def __iadd__(self, other):
-        _algebra.check_compatible(self, other)
-        self.tensor_values = self.tensor_values + other.tensor_values
+    def _leafwise_inplace(self, op, other) -> None:
+        self.tensor_values = op(self.tensor_values, getattr(other, "tensor_values", other))
         self._cached_error_estimate = None
-        return self
-
-    def __isub__(self, other):
-        _algebra.check_compatible(self, other)
-        self.tensor_values = self.tensor_values - other.tensor_values
-        self._cached_error_estimate = None
-        return self
-
-    def __imul__(self, scalar):
-        if not _algebra.is_scalar(scalar):
-            return NotImplemented
-        self.tensor_values = self.tensor_values * float(scalar)
-        self._cached_error_estimate = None
-        return self
-
-    def __itruediv__(self, scalar):
-        if not _algebra.is_scalar(scalar):
-            return NotImplemented
-        return self.__imul__(1.0 / float(scalar))
 
     # ---------------------------------------------------------------- persistence
     def __getstate__(self) -> dict:
@@ -1147,139 +1105,37 @@ class ChebyshevApproximation(ErgonomicsMixin, DerivativeIdMixin):
                 "variance": float(var.value)}
 
     # ---------------------------------------------------------------- calculus
-    def _calculus_batch(self, dim: int, rows: np.ndarray, mode: int):
-        """``pcx_bary_calculus_batch`` over validated rows (see :func:`pychebyshev_amd._calculus.run_batch`)."""
-        from . import _calculus
-        m = self._model()
-        lo = _lib.f64([float(b[0]) for b in self.domain])
-        hi = _lib.f64([float(b[1]) for b in self.domain])
-        rows = _lib.f64(rows)
-        N = rows.shape[0]
+    # _calculus.FibreCalculusMixin's methods over these hooks; below, what this class adds to their docstrings.
+    _fibre_prefix = "pcx_bary"
+    _ladder_own_stream = True
 
-        def call(r, c, v, loc):
-            return m.lib.pcx_bary_calculus_batch(m.handle, int(dim), _lib.p_f64(lo), _lib.p_f64(hi), _lib.p_f64(rows), N,
-                                                 mode, r, c, v, loc)
-        return _calculus.run_batch(call, m.lib, int(self.n_nodes[dim]), N, mode)
-
-    def _calculus(self, dim, fixed, mode: str):
-        from . import _calculus
+    def _fibre_check_built(self) -> None:
         if self.tensor_values is None:
             raise RuntimeError("Call build() first")
-        d = self.num_dimensions
-        dim, params = _calculus.validate_calculus_args(d, dim, fixed, self.domain)
-        row = _calculus.fixed_row(d, dim, params)
-        n = int(self.n_nodes[dim])
-        return _calculus.run_single(
-            lambda: self.vectorized_eval_batch(_calculus.fibre_points(d, dim, row, self.nodes[dim]), [0] * d),
-            lambda m: self._calculus_batch(dim, row, m), n, mode, self.nodes[dim], self.weights[dim],
-            self.diff_matrices[dim], (self.domain[dim][0], self.domain[dim][1]))
 
-    def _solve_batch(self, dim: int, rows: np.ndarray, targets: np.ndarray, method: int):
-        """``pcx_bary_solve_batch`` over validated rows and targets (see :func:`pychebyshev_amd._calculus.run_solve`)."""
-        from . import _calculus
-        m = self._model()
-        lo = _lib.f64([float(b[0]) for b in self.domain])
-        hi = _lib.f64([float(b[1]) for b in self.domain])
-        rows, targets = _lib.f64(rows), _lib.f64(targets)
-        N = rows.shape[0]
+    def _fibre_handle(self) -> _DeviceModel:
+        return self._model()
 
-        def call(r, c, x, s):
-            return m.lib.pcx_bary_solve_batch(m.handle, int(dim), _lib.p_f64(lo), _lib.p_f64(hi), _lib.p_f64(rows),
-                                              _lib.p_f64(targets), N, method, r, c, x, s)
-        return _calculus.run_solve(call, m.lib, int(self.n_nodes[dim]), N, method)
+    def _fibre_grid(self, dim: int):
+        return self.nodes[dim], self.weights[dim], self.diff_matrices[dim], (self.domain[dim][0], self.domain[dim][1])
 
-    def _level_roots(self, dim, fixed, level: np.ndarray) -> np.ndarray:
-        from . import _calculus
-        if self.tensor_values is None:
-            raise RuntimeError("Call build() first")
-        d = self.num_dimensions
-        dim, params = _calculus.validate_calculus_args(d, dim, fixed, self.domain)
-        row = _calculus.fixed_row(d, dim, params)
-        return _calculus.run_single_level(
-            lambda: self.vectorized_eval_batch(_calculus.fibre_points(d, dim, row, self.nodes[dim]), [0] * d),
-            lambda: self._solve_batch(dim, row, level, 0), int(self.n_nodes[dim]), level,
-            (self.domain[dim][0], self.domain[dim][1]))
+    def _fibre_values(self, points) -> np.ndarray:
+        return self.vectorized_eval_batch(points, [0] * self.num_dimensions)
 
     def roots(self, dim=None, fixed=None, *, level=0.0) -> np.ndarray:
-        """Sorted real roots along ``dim`` with every other dimension fixed (``fixed = {dim_index: value}``) by the
-        colleague-matrix method (reference barycentric.py:2277-2327, _calculus.py:198-244).  The fibre is evaluated
-        and solved on the device; above 64 nodes the solve runs on the host (NumPy ``chebroots``).  A non-finite
-        fibre raises ``numpy.linalg.LinAlgError``.  Unlike the reference, which clips from outside only, a root
-        within ``1e-10`` (of the half-width) of an end of ``domain[dim]``, on either side of it, is returned as exactly
-        that end; the batched forms and the critical points of :meth:`minimize` / :meth:`maximize` follow the same
-        rule.
-
-        ``level`` (keyword only, a finite scalar) asks for the solutions of ``p = level`` instead: the level is
-        subtracted from the fibre on the device, one rounding per value, before the same solver.  ``None`` or ``0.0``
-        is the call without a level, the same launches and bits."""
-        from . import _calculus
-        lv = _calculus.validate_level(level, 1)
-        if lv is None:
-            return self._calculus(dim, fixed, "roots")
-        return self._level_roots(dim, fixed, lv)
+        """:meth:`FibreCalculusMixin.roots <pychebyshev_amd._calculus.FibreCalculusMixin.roots>`, ``level`` included
+        (reference barycentric.py:2277-2327, _calculus.py:198-244)."""
+        return super().roots(dim, fixed, level=level)
 
     def minimize(self, dim=None, fixed=None):
-        """``(value, location)`` of the minimum along ``dim`` (reference barycentric.py:2329-2377): the roots of the
-        derivative series and the two ends are the candidates, the first smallest value wins.  A critical point
-        within ``1e-10`` of an end is that end (see :meth:`roots`)."""
-        return self._calculus(dim, fixed, "min")
+        """:meth:`FibreCalculusMixin.minimize <pychebyshev_amd._calculus.FibreCalculusMixin.minimize>` (reference
+        barycentric.py:2329-2377)."""
+        return super().minimize(dim, fixed)
 
     def maximize(self, dim=None, fixed=None):
-        """``(value, location)`` of the maximum along ``dim`` (reference barycentric.py:2379-2427)."""
-        return self._calculus(dim, fixed, "max")
-
-    def _calculus_rows(self, dim, fixed) -> np.ndarray:
-        from . import _calculus
-        if self.tensor_values is None:
-            raise RuntimeError("Call build() first")
-        return _calculus.validate_batch_args(self.num_dimensions, dim, fixed, self.domain, self.n_nodes)
-
-    def roots_batch(self, dim: int, fixed, *, level=None):
-        """Roots along ``dim`` for every row of ``fixed`` (host float64 ``(N, d-1)``: the other dimensions in
-        increasing order), in one device pass (extension).  Returns ``(roots, counts)``: ``roots`` float64
-        ``(N, max(n_dim-1, 1))`` ascending and NaN-padded, ``counts`` int32 ``(N,)``, -1 where the fibre was not finite
-        or the eigenvalue iteration failed.  At most 64 nodes along ``dim``.
-
-        ``level`` (keyword only, a finite scalar or an ``(N,)`` array, one level per row) asks for the solutions of ``p = level`` instead: the level is
-        subtracted from the fibre on the device, one rounding per value, before the same solver.  ``None`` or ``0.0``
-        is the call without a level, the same launches and bits."""
-        from . import _calculus
-        rows = self._calculus_rows(dim, fixed)
-        lv = _calculus.validate_level(level, rows.shape[0])
-        if lv is None:
-            return self._calculus_batch(int(dim), rows, 0)
-        return self._solve_batch(int(dim), rows, lv, 0)
-
-    def invert_batch(self, dim: int, fixed, targets):
-        """The value of dimension ``dim`` at which the model equals each row's target (extension;
-        ``pcx_bary_solve_batch``, method 1): ``fixed`` as in :meth:`roots_batch`, ``targets`` a finite scalar or ``(N,)``
-        array.  Returns ``(x (N,) float64, status (N,) int32)``.  On the knots ``[lo, nodes..., hi]`` of the fibre
-        a segment brackets when the value at its lower knot equals the target or ``p - target`` changes sign across it;
-        ``status`` is the number of bracketing segments: ``0`` the target is not reached on the knots (``x`` NaN),
-        ``1`` unique on the knots, ``> 1`` not unique (``x`` is the lowest), ``-1`` the fibre is not finite or the
-        solver's fixed iteration cap was reached (``x`` NaN).  ``x`` is the knot itself where the value equals the
-        target there, else the root inside the lowest bracketing segment, down to adjacent doubles.  A constant fibre
-        equal to its target gives ``status = n + 2`` and ``x = lo`` when the sums at the two ends return the constant
-        itself (a power of two, zero), else n to n + 2.  A root closer to 0 than ``2^-9 max(|lo|, |hi|)`` is returned to
-        within ``2^-10 eps max(|lo|, |hi|)``, not to adjacent doubles.  Only crossings between knots are seen: two
-        solutions inside one node interval are invisible here, and ``roots_batch(level=)`` finds them.  At most 64
-        nodes along ``dim``.  One device lane solves one row (``csrc/invert_kernels.h``)."""
-        from . import _calculus
-        rows = self._calculus_rows(dim, fixed)
-        return self._solve_batch(int(dim), rows, _calculus.validate_targets(targets, rows.shape[0]), 1)
-
-    def minimize_batch(self, dim: int, fixed):
-        """``(values, locations)``, float64 ``(N,)``, of the minimum along ``dim`` for every row of ``fixed``
-        (extension; arguments as :meth:`roots_batch`).  NaN where a row failed."""
-        rows = self._calculus_rows(dim, fixed)
-        val, loc, _ = self._calculus_batch(int(dim), rows, 1)
-        return val, loc
-
-    def maximize_batch(self, dim: int, fixed):
-        """``(values, locations)`` of the maximum along ``dim`` for every row of ``fixed`` (extension)."""
-        rows = self._calculus_rows(dim, fixed)
-        val, loc, _ = self._calculus_batch(int(dim), rows, 2)
-        return val, loc
+        """:meth:`FibreCalculusMixin.maximize <pychebyshev_amd._calculus.FibreCalculusMixin.maximize>` (reference
+        barycentric.py:2379-2427)."""
+        return super().maximize(dim, fixed)
 
     def ladder_batch(self, dim: int, fixed, xs, derivative_order=None, *, derivative_id=None, out=None):
         """The model along ``dim`` at ``m`` values for every row of ``fixed`` (extension; a spot or vol ladder, a
@@ -1302,39 +1158,13 @@ class ChebyshevApproximation(ErgonomicsMixin, DerivativeIdMixin):
         ``fixed`` and a per-row ``xs`` may be device arrays (device rows are not checked against the domain).  With a
         device ``fixed`` the result is a :class:`~pychebyshev_amd.device.DeviceArray`, complete on return.  ``out=``
         takes a ``DeviceArray`` or a C-contiguous float64 NumPy array of shape ``(N, m)``; it is filled and returned."""
-        from . import _calculus
-        if derivative_order is None and derivative_id is None:
-            derivative_order = [0] * self.num_dimensions
-        else:
-            derivative_order = self._resolve_derivative_args(derivative_order, derivative_id)
-        if self.tensor_values is None:
-            raise RuntimeError("Call build() first")
-        rows = _calculus.validate_fibre_args(self.num_dimensions, dim, fixed, self.domain)
-        spec = self._check_orders(derivative_order)
-        xv, m, per_row = _calculus.validate_ladder_xs(xs, rows.shape[0])
-        _calculus.validate_ladder_out(out, (rows.shape[0], m))         # refused before the model goes to a device
-        model = self._model()
-        st = ctypes.c_void_p()
-        _lib.check(model.lib.pcx_bary_stream(model.handle, ctypes.byref(st)), model.lib)
-        lib, h, dim = model.lib, model.handle, int(dim)
-        return _calculus.run_ladder(
-            lib, model.device, st,
-            lambda f, N, x, mm, pr, o: lib.pcx_bary_ladder_batch(h, dim, _lib.p_i32(spec), f, N, x, mm, pr, o),
-            lambda f, N, x, mm, pr, o, s: lib.pcx_bary_ladder_batch_dev(h, dim, _lib.p_i32(spec), f, N, x, mm, pr, o, s),
-            rows, xv, m, per_row, out)
+        return self._ladder(dim, fixed, xs, out, self._ladder_orders(derivative_order, derivative_id))
 
     def fibre_batch(self, dim: int, fixed, derivative_order=None, *, derivative_id=None, out=None):
-        """Every row's restriction to ``dim`` at that dimension's own nodes, ``(N, n_dim)``: :meth:`ladder_batch` at
-        ``self.nodes[dim]`` (ascending), bit for bit -- the fibre the calculus batches expand into ``n_dim`` point
-        evaluations, from one contraction per row."""
-        if self.tensor_values is None:
-            raise RuntimeError("Call build() first")
-        if isinstance(dim, bool) or not isinstance(dim, (int, np.integer)):
-            raise TypeError(f"dim must be an int, got {type(dim).__name__}")
-        if dim < 0 or dim >= self.num_dimensions:
-            raise ValueError(f"dim {dim} out of range [0, {self.num_dimensions - 1}]")
-        return self.ladder_batch(dim, fixed, np.asarray(self.nodes[dim], dtype=float), derivative_order,
-                                 derivative_id=derivative_id, out=out)
+        """:meth:`FibreCalculusMixin.fibre_batch <pychebyshev_amd._calculus.FibreCalculusMixin.fibre_batch>` at
+        ``self.nodes[dim]`` -- the fibre the calculus batches expand into ``n_dim`` point evaluations, from one
+        contraction per row."""
+        return super().fibre_batch(dim, fixed, derivative_order, derivative_id=derivative_id, out=out)
 
     def fast_eval(self, point, derivative_order=None, *, derivative_id=None) -> float:
         """Deprecated alias kept for drop-in compatibility (reference :789-869): same value as

@@ -4,9 +4,6 @@
 #include "pcx_bary_internal.h"
 #include "bary_ladder_kernels.h"
 
-// doubles of the wider side (rows in, ladders out) one pass of a host-pointer batch stages: 8 MB, an eighth of a
-// kChunkPoints piece of pcx_bary_eval_batch
-static const int64_t kLadderPassDoubles = (int64_t)1 << 20;
 static const int kLadderLdsMax = 64 * 1024;      // the MFMA form's wave: above it the rows form
 
 static size_t ladder_mfma_lds(const BaryLadder &lp) {
@@ -116,22 +113,11 @@ PCX_HIDDEN int bary_ladder_launch(pcx_bary *h, const BaryLadder &lp, const int32
     return PCX_OK;
 }
 
+// ladder_check on the handle's dimensions, then the plan (its dim check has passed by then)
 static int bary_ladder_check(pcx_bary *h, int dim, const int32_t *deriv, const void *fixed, int64_t N, const void *xs, int m,
                              int xs_per_row, const void *out, BaryLadder *lp) {
-    if (!h) return fail(PCX_ERR_INVALID, "handle is NULL");
-    if (N < 0) return fail(PCX_ERR_INVALID, "N < 0");
-    if (m < 0) return fail(PCX_ERR_INVALID, "m < 0");
-    if (xs_per_row != 0 && xs_per_row != 1) return fail(PCX_ERR_INVALID, "xs_per_row = %d is neither 0 nor 1", xs_per_row);
-    int rc = bary_ladder_plan(h, dim, lp);
-    if (rc) return rc;
-    if (deriv)
-        for (int k = 0; k < h->dims.d; ++k)
-            if (deriv[k] < 0 || deriv[k] > 8)
-                return fail(PCX_ERR_INVALID, "derivative order %d at dim %d outside [0, 8]", (int)deriv[k], k);
-    if (N > 0 && lp->nq > 0 && !fixed) return fail(PCX_ERR_INVALID, "fixed is NULL");
-    if (m > 0 && (xs_per_row ? N > 0 : true) && !xs) return fail(PCX_ERR_INVALID, "xs is NULL");
-    if (N > 0 && m > 0 && !out) return fail(PCX_ERR_INVALID, "out is NULL");
-    return PCX_OK;
+    const int rc = ladder_check(h, h ? h->dims.d : 0, dim, deriv, fixed, N, xs, m, xs_per_row, out);
+    return rc ? rc : bary_ladder_plan(h, dim, lp);
 }
 
 extern "C" int pcx_bary_ladder_batch_dev(pcx_bary *h, int dim, const int32_t *deriv, const double *d_fixed, int64_t N,
@@ -147,9 +133,9 @@ extern "C" int pcx_bary_ladder_batch_dev(pcx_bary *h, int dim, const int32_t *de
     if (xs_per_row) return bary_ladder_launch(h, lp, deriv, d_fixed, lp.nq, xs, m, m, (long)N, d_out, st);
     // shared values come from the host: a buffer of this call's, so the call waits for its kernel before it frees it
     DevBuf dxs;
-    if ((rc = dxs.alloc((size_t)m * sizeof(double)))) return rc;
-    HIP_TRY(hipMemcpyAsync(dxs.p, xs, (size_t)m * sizeof(double), hipMemcpyHostToDevice, st));
-    rc = bary_ladder_launch(h, lp, deriv, d_fixed, lp.nq, dxs.as<double>(), 0, m, (long)N, d_out, st);
+    const double *d_shared = nullptr;
+    if ((rc = ladder_shared_xs(dxs, xs, m, true, st, &d_shared))) return rc;
+    rc = bary_ladder_launch(h, lp, deriv, d_fixed, lp.nq, d_shared, 0, m, (long)N, d_out, st);
     const hipError_t e = hipStreamSynchronize(st);
     if (rc) return rc;
     HIP_TRY(e);
@@ -167,38 +153,12 @@ extern "C" int pcx_bary_ladder_batch(pcx_bary *h, int dim, const int32_t *deriv,
     HIP_TRY(hipSetDevice(h->device));
     std::lock_guard<std::mutex> lk(h->mu);
     DevBuf dxs;
-    if (!xs_per_row) {
-        if ((rc = dxs.alloc((size_t)m * sizeof(double)))) return rc;
-        HIP_TRY(hipMemcpy(dxs.p, xs, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
-    }
-    // A staged row is the d - 1 fixed coordinates, then the row's m values when xs is per row (a d = 1 model with shared
-    // values stages one unused double per row).  Passes of pcx_bary_ladder_pass_rows rows, each through the shared driver.
-    const int nq = lp.nq;
-    const int w = std::max(1, nq + (xs_per_row ? m : 0));
-    const int64_t pass = std::max<int64_t>(1, kLadderPassDoubles / std::max(w, m));
-    const bool direct = !xs_per_row && nq > 0;       // the caller's `fixed` is the staged array
-    std::vector<double> rows;
-    for (int64_t start = 0; start < N; start += pass) {
-        const int64_t cnt = std::min<int64_t>(pass, N - start);
-        const double *src = fixed + (size_t)start * nq;
-        if (!direct) {
-            rows.assign((size_t)cnt * w, 0.0);
-            for (int64_t r = 0; r < cnt; ++r) {
-                double *dst = rows.data() + (size_t)r * w;
-                if (nq) memcpy(dst, fixed + (size_t)(start + r) * nq, (size_t)nq * sizeof(double));
-                if (xs_per_row) memcpy(dst + nq, xs + (size_t)(start + r) * m, (size_t)m * sizeof(double));
-            }
-            src = rows.data();
-        }
-        rc = stage_host_batch(h->stage, h->device, h->stream, src, cnt, w, m, out + (size_t)start * m,
-                              StagePlan{cnt, cnt, false, true},
-                              [&](int, hipStream_t st, const double *dp, long c, double *dout) {
-                                  return xs_per_row ? bary_ladder_launch(h, lp, deriv, dp, w, dp + nq, w, m, c, dout, st)
-                                                    : bary_ladder_launch(h, lp, deriv, dp, w, dxs.as<double>(), 0, m, c, dout, st);
+    const double *d_shared = nullptr;
+    if (!xs_per_row && (rc = ladder_shared_xs(dxs, xs, m, false, nullptr, &d_shared))) return rc;
+    return ladder_host_passes(h->stage, h->device, h->stream, lp.nq, fixed, N, xs, d_shared, m, xs_per_row, out,
+                              [&](const double *df, long fs, const double *dx, long xstr, long cnt, double *dout, hipStream_t st) {
+                                  return bary_ladder_launch(h, lp, deriv, df, fs, dx, xstr, m, cnt, dout, st);
                               });
-        if (rc) return rc;
-    }
-    return PCX_OK;
     PCX_API_END
 }
 

@@ -268,6 +268,90 @@ static int stage_host_batch(HostStage &s, int device, hipStream_t main, const do
     return PCX_OK;
 }
 
+// ---------------------------------------------------------------------------------
+// What the four pcx_*_ladder_batch / _dev pairs share (pcx_bary_ladder.hip, pcx_tt_ladder.hip, pcx_piecewise_ladder.hip)
+// ---------------------------------------------------------------------------------
+// The argument checks of a ladder entry on a model of d dimensions, in the entries' order; a class's own checks go in
+// front or behind.  deriv may be NULL (a class without a spec, or the plain values).
+static int ladder_check(const void *h, int d, int dim, const int32_t *deriv, const void *fixed, int64_t N, const void *xs, int m,
+                        int xs_per_row, const void *out) {
+    if (!h) return fail(PCX_ERR_INVALID, "handle is NULL");
+    if (N < 0) return fail(PCX_ERR_INVALID, "N < 0");
+    if (m < 0) return fail(PCX_ERR_INVALID, "m < 0");
+    if (xs_per_row != 0 && xs_per_row != 1) return fail(PCX_ERR_INVALID, "xs_per_row = %d is neither 0 nor 1", xs_per_row);
+    if (dim < 0 || dim >= d) return fail(PCX_ERR_INVALID, "dim %d out of range [0, %d]", dim, d - 1);
+    if (deriv)
+        for (int k = 0; k < d; ++k)
+            if (deriv[k] < 0 || deriv[k] > 8)
+                return fail(PCX_ERR_INVALID, "derivative order %d at dim %d outside [0, 8]", (int)deriv[k], k);
+    if (N > 0 && d > 1 && !fixed) return fail(PCX_ERR_INVALID, "fixed is NULL");
+    if (m > 0 && (xs_per_row ? N > 0 : true) && !xs) return fail(PCX_ERR_INVALID, "xs is NULL");
+    if (N > 0 && m > 0 && !out) return fail(PCX_ERR_INVALID, "out is NULL");
+    return PCX_OK;
+}
+
+// The m values all rows share, from the host into a buffer of the call's (DevBuf) or of the handle's (Scratch): queued
+// on st, or with a blocking copy; *d_xs: where they are on the device.
+static int ladder_upload_xs(void *p, const double *xs, int m, bool queued, hipStream_t st, const double **d_xs) {
+    if (queued) HIP_TRY(hipMemcpyAsync(p, xs, (size_t)m * sizeof(double), hipMemcpyHostToDevice, st));
+    else HIP_TRY(hipMemcpy(p, xs, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
+    *d_xs = (const double *)p;
+    return PCX_OK;
+}
+static int ladder_shared_xs(DevBuf &buf, const double *xs, int m, bool queued, hipStream_t st, const double **d_xs) {
+    const int rc = buf.alloc((size_t)m * sizeof(double));
+    return rc ? rc : ladder_upload_xs(buf.p, xs, m, queued, st, d_xs);
+}
+static int ladder_shared_xs(Scratch &buf, const double *xs, int m, bool queued, hipStream_t st, const double **d_xs) {
+    const int rc = buf.reserve((size_t)m * sizeof(double));
+    return rc ? rc : ladder_upload_xs(buf.ptr, xs, m, queued, st, d_xs);
+}
+
+// doubles of the wider side (rows in, ladders out) one pass of a host-pointer ladder stages: 8 MB, an eighth of a
+// kChunkPoints piece of pcx_bary_eval_batch
+static const int64_t kLadderPassDoubles = (int64_t)1 << 20;
+
+// A staged row is the nq fixed coordinates, then the row's m values when xs is per row -- at least one double: a
+// one-dimensional model with shared values stages one unused double per row.
+static int ladder_row_width(int nq, int m, int xs_per_row) { return std::max(1, nq + (xs_per_row ? m : 0)); }
+// rows per pass
+static int64_t ladder_pass_rows(int nq, int m, int xs_per_row) {
+    return std::max<int64_t>(1, kLadderPassDoubles / std::max(ladder_row_width(nq, m, xs_per_row), m));
+}
+
+// The host-pointer form of every ladder: the rows are packed (shared values and nq > 0: the caller's `fixed` is the
+// staged array already) and go through stage_host_batch in passes of ladder_pass_rows rows.
+// run(d_fixed, fstride, d_xs, xstride, cnt, d_out, st) queues cnt device-resident rows on st, the stage's stream of the
+// pass (`main`: one slot); d_shared: the shared values on the device.  Caller holds the handle's mutex.
+template <typename Run>
+static int ladder_host_passes(HostStage &stage, int device, hipStream_t main, int nq, const double *fixed, int64_t N,
+                              const double *xs, const double *d_shared, int m, int xs_per_row, double *out, Run &&run) {
+    const int w = ladder_row_width(nq, m, xs_per_row);
+    const int64_t pass = ladder_pass_rows(nq, m, xs_per_row);
+    const bool direct = !xs_per_row && nq > 0;
+    std::vector<double> rows;
+    for (int64_t start = 0; start < N; start += pass) {
+        const int64_t cnt = std::min<int64_t>(pass, N - start);
+        const double *src = fixed + (size_t)start * nq;
+        if (!direct) {
+            rows.assign((size_t)cnt * w, 0.0);
+            for (int64_t r = 0; r < cnt; ++r) {
+                double *dst = rows.data() + (size_t)r * w;
+                if (nq) memcpy(dst, fixed + (size_t)(start + r) * nq, (size_t)nq * sizeof(double));
+                if (xs_per_row) memcpy(dst + nq, xs + (size_t)(start + r) * m, (size_t)m * sizeof(double));
+            }
+            src = rows.data();
+        }
+        int rc = stage_host_batch(stage, device, main, src, cnt, w, m, out + (size_t)start * m, StagePlan{cnt, cnt, false, true},
+                                  [&](int, hipStream_t st, const double *dp, long c, double *dout) {
+                                      return xs_per_row ? run(dp, (long)w, dp + nq, (long)w, c, dout, st)
+                                                        : run(dp, (long)w, d_shared, 0L, c, dout, st);
+                                  });
+        if (rc) return rc;
+    }
+    return PCX_OK;
+}
+
 // true when the runtime reports [p, p + bytes), bytes > 0, as page-locked host memory at both ends and up to 14 interior
 // points (two separate registrations could cover just the ends)
 static bool host_range_locked(const void *p, size_t bytes) {

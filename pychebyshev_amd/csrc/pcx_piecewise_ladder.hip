@@ -6,63 +6,10 @@
 #include "pcx_spline_internal.h"
 #include "piecewise_ladder_kernels.h"
 
-// doubles of the wider side (rows in, ladders out) one pass of a host-pointer batch stages: pcx_bary_ladder_batch's rule
-static const int64_t kLadderPassDoubles = (int64_t)1 << 20;
 // doubles of fibres (spline) or of result (slider) one chunk of rows holds: the calculus batches' kCalcChunkPoints
 static const long kLadderChunkDoubles = 1L << 21;
 
 static unsigned grid_for(long total) { return (unsigned)std::max<long>(1, std::min<long>((total + 255) / 256, 8192)); }
-
-// bary_ladder_check's checks and messages for a model of d dimensions
-static int piecewise_ladder_check(const void *h, int d, int dim, const int32_t *deriv, const void *fixed, int64_t N,
-                                  const void *xs, int m, int xs_per_row, const void *out) {
-    if (!h) return fail(PCX_ERR_INVALID, "handle is NULL");
-    if (N < 0) return fail(PCX_ERR_INVALID, "N < 0");
-    if (m < 0) return fail(PCX_ERR_INVALID, "m < 0");
-    if (xs_per_row != 0 && xs_per_row != 1) return fail(PCX_ERR_INVALID, "xs_per_row = %d is neither 0 nor 1", xs_per_row);
-    if (dim < 0 || dim >= d) return fail(PCX_ERR_INVALID, "dim %d out of range [0, %d]", dim, d - 1);
-    if (deriv)
-        for (int k = 0; k < d; ++k)
-            if (deriv[k] < 0 || deriv[k] > 8)
-                return fail(PCX_ERR_INVALID, "derivative order %d at dim %d outside [0, 8]", (int)deriv[k], k);
-    if (N > 0 && d > 1 && !fixed) return fail(PCX_ERR_INVALID, "fixed is NULL");
-    if (m > 0 && (xs_per_row ? N > 0 : true) && !xs) return fail(PCX_ERR_INVALID, "xs is NULL");
-    if (N > 0 && m > 0 && !out) return fail(PCX_ERR_INVALID, "out is NULL");
-    return PCX_OK;
-}
-
-// The host-pointer form of both classes, pcx_bary_ladder_batch's staging: a staged row is the nq fixed coordinates, then
-// the row's m values when xs is per row (at least one double), in passes of 2^20 / max(that width, m) rows.
-// run(d_fixed, fstride, d_xs, xstride, cnt, d_out) queues cnt device-resident rows on `st`; d_shared: the shared values
-// on the device.
-template <typename Run>
-static int ladder_host_passes(HostStage &stage, int device, hipStream_t st, int nq, const double *fixed, int64_t N,
-                              const double *xs, const double *d_shared, int m, int xs_per_row, double *out, Run &&run) {
-    const int w = std::max(1, nq + (xs_per_row ? m : 0));
-    const int64_t pass = std::max<int64_t>(1, kLadderPassDoubles / std::max(w, m));
-    const bool direct = !xs_per_row && nq > 0;       // the caller's `fixed` is the staged array
-    std::vector<double> rows;
-    for (int64_t start = 0; start < N; start += pass) {
-        const int64_t cnt = std::min<int64_t>(pass, N - start);
-        const double *src = fixed + (size_t)start * nq;
-        if (!direct) {
-            rows.assign((size_t)cnt * w, 0.0);
-            for (int64_t r = 0; r < cnt; ++r) {
-                double *dst = rows.data() + (size_t)r * w;
-                if (nq) memcpy(dst, fixed + (size_t)(start + r) * nq, (size_t)nq * sizeof(double));
-                if (xs_per_row) memcpy(dst + nq, xs + (size_t)(start + r) * m, (size_t)m * sizeof(double));
-            }
-            src = rows.data();
-        }
-        int rc = stage_host_batch(stage, device, st, src, cnt, w, m, out + (size_t)start * m, StagePlan{cnt, cnt, false, true},
-                                  [&](int, hipStream_t, const double *dp, long c, double *dout) {
-                                      return xs_per_row ? run(dp, (long)w, dp + nq, (long)w, c, dout)
-                                                        : run(dp, (long)w, d_shared, 0L, c, dout);
-                                  });
-        if (rc) return rc;
-    }
-    return PCX_OK;
-}
 
 // ---------------------------------------------------------------------------------
 // spline
@@ -213,20 +160,16 @@ extern "C" int pcx_spline_ladder_batch_dev(pcx_spline *h, int dim, const int32_t
                                            const double *xs, int m, int xs_per_row, double *d_out, void *stream) {
     PCX_API_BEGIN
     (void)stream;                                              // the work runs on the handle's streams; complete on return
-    int rc = piecewise_ladder_check(h, h ? h->sd.d : 0, dim, deriv, d_fixed, N, xs, m, xs_per_row, d_out);
+    int rc = ladder_check(h, h ? h->sd.d : 0, dim, deriv, d_fixed, N, xs, m, xs_per_row, d_out);
     if (rc) return rc;
     if (N == 0 || m == 0) return PCX_OK;
     HIP_TRY(hipSetDevice(h->device));
     std::lock_guard<std::mutex> lk(h->mu);
     SplineLadderCall c;
-    DevView dxs{};
+    const double *d_xs = xs;
     if ((rc = spline_ladder_prepare(h, dim, deriv, m, xs_per_row ? nullptr : xs, (size_t)m, N, c))) return rc;
-    if (!xs_per_row) {                                         // shared values come from the host
-        if ((rc = h->s_ladder[4].reserve((size_t)m * sizeof(double)))) return rc;
-        dxs.p = h->s_ladder[4].ptr;
-        HIP_TRY(hipMemcpy(dxs.p, xs, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
-    }
-    rc = spline_ladder_rows(h, c, d_fixed, c.nq, xs_per_row ? xs : dxs.as<double>(), xs_per_row ? m : 0, (long)N, d_out);
+    if (!xs_per_row && (rc = ladder_shared_xs(h->s_ladder[4], xs, m, false, nullptr, &d_xs))) return rc;     // shared values come from the host
+    rc = spline_ladder_rows(h, c, d_fixed, c.nq, d_xs, xs_per_row ? m : 0, (long)N, d_out);
     return spline_ladder_finish(h, rc);
     PCX_API_END
 }
@@ -234,24 +177,20 @@ extern "C" int pcx_spline_ladder_batch_dev(pcx_spline *h, int dim, const int32_t
 extern "C" int pcx_spline_ladder_batch(pcx_spline *h, int dim, const int32_t *deriv, const double *fixed, int64_t N,
                                        const double *xs, int m, int xs_per_row, double *out) {
     PCX_API_BEGIN
-    int rc = piecewise_ladder_check(h, h ? h->sd.d : 0, dim, deriv, fixed, N, xs, m, xs_per_row, out);
+    int rc = ladder_check(h, h ? h->sd.d : 0, dim, deriv, fixed, N, xs, m, xs_per_row, out);
     if (rc) return rc;
     if (N == 0 || m == 0) return PCX_OK;
     HIP_TRY(hipSetDevice(h->device));
     std::lock_guard<std::mutex> lk(h->mu);
     SplineLadderCall c;
-    DevView dxs{};
-    const int w = std::max(1, h->sd.d - 1 + (xs_per_row ? m : 0));
-    const int64_t pass = std::max<int64_t>(1, kLadderPassDoubles / std::max(w, m));
+    const double *d_shared = nullptr;
+    const int64_t pass = ladder_pass_rows(h->sd.d - 1, m, xs_per_row);
     if ((rc = spline_ladder_prepare(h, dim, deriv, m, xs, xs_per_row ? (size_t)N * m : (size_t)m, std::min<int64_t>(pass, N), c)))
         return rc;
-    if (!xs_per_row) {
-        if ((rc = h->s_ladder[4].reserve((size_t)m * sizeof(double)))) return rc;
-        dxs.p = h->s_ladder[4].ptr;
-        HIP_TRY(hipMemcpy(dxs.p, xs, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
-    }
-    rc = ladder_host_passes(h->stage, h->device, h->stream, c.nq, fixed, N, xs, dxs.as<double>(), m, xs_per_row, out,
-                            [&](const double *df, long fs, const double *dx, long xstr, long cnt, double *dout) {
+    if (!xs_per_row && (rc = ladder_shared_xs(h->s_ladder[4], xs, m, false, nullptr, &d_shared))) return rc;
+    // the rows run on the handle's streams: the stage's stream of a pass is h->stream
+    rc = ladder_host_passes(h->stage, h->device, h->stream, c.nq, fixed, N, xs, d_shared, m, xs_per_row, out,
+                            [&](const double *df, long fs, const double *dx, long xstr, long cnt, double *dout, hipStream_t) {
                                 return spline_ladder_rows(h, c, df, fs, dx, xstr, cnt, dout);
                             });
     return spline_ladder_finish(h, rc);
@@ -397,20 +336,16 @@ extern "C" int pcx_slider_ladder_batch_dev(pcx_slider *h, int dim, const int32_t
                                            const double *xs, int m, int xs_per_row, double *d_out, void *stream) {
     PCX_API_BEGIN
     (void)stream;                                              // the work runs on the handle's stream; complete on return
-    int rc = piecewise_ladder_check(h, h ? h->d : 0, dim, deriv, d_fixed, N, xs, m, xs_per_row, d_out);
+    int rc = ladder_check(h, h ? h->d : 0, dim, deriv, d_fixed, N, xs, m, xs_per_row, d_out);
     if (rc) return rc;
     if (N == 0 || m == 0) return PCX_OK;
     HIP_TRY(hipSetDevice(h->device));
     std::lock_guard<std::mutex> lk(h->mu);
     SliderLadderCall c;
-    DevView dxs{};
+    const double *d_xs = xs;
     if ((rc = slider_ladder_prepare(h, dim, deriv, m, N, c))) return rc;
-    if (!xs_per_row) {                                         // shared values come from the host
-        if ((rc = h->s_ladder[0].reserve((size_t)m * sizeof(double)))) return rc;
-        dxs.p = h->s_ladder[0].ptr;
-        HIP_TRY(hipMemcpy(dxs.p, xs, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
-    }
-    rc = slider_ladder_rows(h, c, d_fixed, h->d - 1, xs_per_row ? xs : dxs.as<double>(), xs_per_row ? m : 0, (long)N, d_out);
+    if (!xs_per_row && (rc = ladder_shared_xs(h->s_ladder[0], xs, m, false, nullptr, &d_xs))) return rc;     // shared values come from the host
+    rc = slider_ladder_rows(h, c, d_fixed, h->d - 1, d_xs, xs_per_row ? m : 0, (long)N, d_out);
     return slider_ladder_finish(h, rc);
     PCX_API_END
 }
@@ -418,23 +353,18 @@ extern "C" int pcx_slider_ladder_batch_dev(pcx_slider *h, int dim, const int32_t
 extern "C" int pcx_slider_ladder_batch(pcx_slider *h, int dim, const int32_t *deriv, const double *fixed, int64_t N,
                                        const double *xs, int m, int xs_per_row, double *out) {
     PCX_API_BEGIN
-    int rc = piecewise_ladder_check(h, h ? h->d : 0, dim, deriv, fixed, N, xs, m, xs_per_row, out);
+    int rc = ladder_check(h, h ? h->d : 0, dim, deriv, fixed, N, xs, m, xs_per_row, out);
     if (rc) return rc;
     if (N == 0 || m == 0) return PCX_OK;
     HIP_TRY(hipSetDevice(h->device));
     std::lock_guard<std::mutex> lk(h->mu);
     SliderLadderCall c;
-    DevView dxs{};
-    const int w = std::max(1, h->d - 1 + (xs_per_row ? m : 0));
-    const int64_t pass = std::max<int64_t>(1, kLadderPassDoubles / std::max(w, m));
+    const double *d_shared = nullptr;
+    const int64_t pass = ladder_pass_rows(h->d - 1, m, xs_per_row);
     if ((rc = slider_ladder_prepare(h, dim, deriv, m, std::min<int64_t>(pass, N), c))) return rc;
-    if (!xs_per_row) {
-        if ((rc = h->s_ladder[0].reserve((size_t)m * sizeof(double)))) return rc;
-        dxs.p = h->s_ladder[0].ptr;
-        HIP_TRY(hipMemcpy(dxs.p, xs, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
-    }
-    rc = ladder_host_passes(h->stage, h->device, h->stream, h->d - 1, fixed, N, xs, dxs.as<double>(), m, xs_per_row, out,
-                            [&](const double *df, long fs, const double *dx, long xstr, long cnt, double *dout) {
+    if (!xs_per_row && (rc = ladder_shared_xs(h->s_ladder[0], xs, m, false, nullptr, &d_shared))) return rc;
+    rc = ladder_host_passes(h->stage, h->device, h->stream, h->d - 1, fixed, N, xs, d_shared, m, xs_per_row, out,
+                            [&](const double *df, long fs, const double *dx, long xstr, long cnt, double *dout, hipStream_t) {
                                 return slider_ladder_rows(h, c, df, fs, dx, xstr, cnt, dout);
                             });
     return slider_ladder_finish(h, rc);

@@ -4,14 +4,11 @@
 #include "pcx_internal.h"
 #include "tt_ladder_kernels.h"
 
-// as pcx_bary_ladder_batch: doubles of the wider side one pass of a host-pointer batch stages
-static const int64_t kLadderPassDoubles = (int64_t)1 << 20;
-
-// dim in the USER's frame -> its storage position and, per storage position, the column of `fixed` it reads
+// dim in the USER's frame (range-checked by ladder_check) -> its storage position and, per storage position, the column
+// of `fixed` it reads
 static int tt_ladder_plan(const TTBoxView &v, int dim, int m, TTLadder *lp) {
     const TTDims &dims = *v.dims;
     const int d = dims.d;
-    if (dim < 0 || dim >= d) return fail(PCX_ERR_INVALID, "dim %d out of range [0, %d]", dim, d - 1);
     *lp = TTLadder{};
     lp->d = d;
     lp->m = m;
@@ -64,18 +61,12 @@ static int tt_ladder_launch(const TTBoxView &v, const TTLadder &lp, const double
     return PCX_OK;
 }
 
+// the handle's view, ladder_check on its dimensions (a TT ladder takes no spec), then the plan
 static int tt_ladder_check(pcx_tt *h, TTBoxView *v, int dim, const void *fixed, int64_t N, const void *xs, int m, int xs_per_row,
                            const void *out, TTLadder *lp) {
     int rc = tt_box_view(h, v);
-    if (rc) return rc;
-    if (N < 0) return fail(PCX_ERR_INVALID, "N < 0");
-    if (m < 0) return fail(PCX_ERR_INVALID, "m < 0");
-    if (xs_per_row != 0 && xs_per_row != 1) return fail(PCX_ERR_INVALID, "xs_per_row = %d is neither 0 nor 1", xs_per_row);
-    if ((rc = tt_ladder_plan(*v, dim, m, lp))) return rc;
-    if (N > 0 && lp->d > 1 && !fixed) return fail(PCX_ERR_INVALID, "fixed is NULL");
-    if (m > 0 && (xs_per_row ? N > 0 : true) && !xs) return fail(PCX_ERR_INVALID, "xs is NULL");
-    if (N > 0 && m > 0 && !out) return fail(PCX_ERR_INVALID, "out is NULL");
-    return PCX_OK;
+    if (!rc) rc = ladder_check(h, v->dims->d, dim, nullptr, fixed, N, xs, m, xs_per_row, out);
+    return rc ? rc : tt_ladder_plan(*v, dim, m, lp);
 }
 
 extern "C" int pcx_tt_ladder_batch_dev(pcx_tt *h, int dim, const double *d_fixed, int64_t N, const double *xs, int m,
@@ -93,9 +84,9 @@ extern "C" int pcx_tt_ladder_batch_dev(pcx_tt *h, int dim, const double *d_fixed
     if (xs_per_row) return tt_ladder_launch(v, lp, d_fixed, nq, xs, m, (long)N, d_out, st);
     // shared values come from the host: a buffer of this call's, so the call waits for its kernel before it frees it
     DevBuf dxs;
-    if ((rc = dxs.alloc((size_t)m * sizeof(double)))) return rc;
-    HIP_TRY(hipMemcpyAsync(dxs.p, xs, (size_t)m * sizeof(double), hipMemcpyHostToDevice, st));
-    rc = tt_ladder_launch(v, lp, d_fixed, nq, dxs.as<double>(), 0, (long)N, d_out, st);
+    const double *d_shared = nullptr;
+    if ((rc = ladder_shared_xs(dxs, xs, m, true, st, &d_shared))) return rc;
+    rc = tt_ladder_launch(v, lp, d_fixed, nq, d_shared, 0, (long)N, d_out, st);
     const hipError_t e = hipStreamSynchronize(st);
     if (rc) return rc;
     HIP_TRY(e);
@@ -114,36 +105,11 @@ extern "C" int pcx_tt_ladder_batch(pcx_tt *h, int dim, const double *fixed, int6
     HIP_TRY(hipSetDevice(v.device));
     std::lock_guard<std::mutex> lk(*v.mu);
     DevBuf dxs;
-    if (!xs_per_row) {
-        if ((rc = dxs.alloc((size_t)m * sizeof(double)))) return rc;
-        HIP_TRY(hipMemcpy(dxs.p, xs, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
-    }
-    // staged rows and passes as pcx_bary_ladder_batch
-    const int nq = lp.d - 1;
-    const int w = std::max(1, nq + (xs_per_row ? m : 0));
-    const int64_t pass = std::max<int64_t>(1, kLadderPassDoubles / std::max(w, m));
-    const bool direct = !xs_per_row && nq > 0;
-    std::vector<double> rows;
-    for (int64_t start = 0; start < N; start += pass) {
-        const int64_t cnt = std::min<int64_t>(pass, N - start);
-        const double *src = fixed + (size_t)start * nq;
-        if (!direct) {
-            rows.assign((size_t)cnt * w, 0.0);
-            for (int64_t r = 0; r < cnt; ++r) {
-                double *dst = rows.data() + (size_t)r * w;
-                if (nq) memcpy(dst, fixed + (size_t)(start + r) * nq, (size_t)nq * sizeof(double));
-                if (xs_per_row) memcpy(dst + nq, xs + (size_t)(start + r) * m, (size_t)m * sizeof(double));
-            }
-            src = rows.data();
-        }
-        rc = stage_host_batch(*v.stage, v.device, v.stream, src, cnt, w, m, out + (size_t)start * m,
-                              StagePlan{cnt, cnt, false, true},
-                              [&](int, hipStream_t st, const double *dp, long c, double *dout) {
-                                  return xs_per_row ? tt_ladder_launch(v, lp, dp, w, dp + nq, w, c, dout, st)
-                                                    : tt_ladder_launch(v, lp, dp, w, dxs.as<double>(), 0, c, dout, st);
+    const double *d_shared = nullptr;
+    if (!xs_per_row && (rc = ladder_shared_xs(dxs, xs, m, false, nullptr, &d_shared))) return rc;
+    return ladder_host_passes(*v.stage, v.device, v.stream, lp.d - 1, fixed, N, xs, d_shared, m, xs_per_row, out,
+                              [&](const double *df, long fs, const double *dx, long xstr, long cnt, double *dout, hipStream_t st) {
+                                  return tt_ladder_launch(v, lp, df, fs, dx, xstr, cnt, dout, st);
                               });
-        if (rc) return rc;
-    }
-    return PCX_OK;
     PCX_API_END
 }

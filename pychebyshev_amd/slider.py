@@ -44,6 +44,8 @@ from typing import Callable, List, Sequence, Tuple
 import numpy as np
 
 from . import _algebra, _calculus, _lib
+from ._algebra import ValueAlgebraMixin
+from ._calculus import FibreCalculusMixin
 from ._version import __version__
 from ._derivative_ids import DerivativeIdMixin
 from ._ergonomics import ErgonomicsMixin
@@ -98,7 +100,7 @@ class _DeviceSlider:
             pass
 
 
-class ChebyshevSlider(ErgonomicsMixin, DerivativeIdMixin):
+class ChebyshevSlider(ErgonomicsMixin, DerivativeIdMixin, FibreCalculusMixin, ValueAlgebraMixin):
     """Sum of low-dimensional slides around ``pivot_point`` (signature: reference slider.py:80-90)."""
 
     def __init__(self, function: Callable, num_dimensions: int,
@@ -257,9 +259,9 @@ class ChebyshevSlider(ErgonomicsMixin, DerivativeIdMixin):
         return _composite_eval_grid(self, "pcx_slider_eval_tensor_grid", axes, derivative_order, derivative_id, out)
 
     # ---------------------------------------------------------------- algebra
-    # Reference slider.py:1285-1390: slide by slide on the host, pivot_value combined the same way.  The in-place
-    # forms rebind every slide's tensor_values and pivot_value, which is how the device copy
-    # (_DeviceSlider.matches) sees that it is stale.
+    # Reference slider.py:1285-1390; the operators are _algebra.ValueAlgebraMixin's: slide by slide on the host
+    # (the slides' own hooks), pivot_value combined the same way.  The in-place forms rebind every slide's
+    # tensor_values and pivot_value, which is how the device copy (_DeviceSlider.matches) sees that it is stale.
     def _check_slider_compatible(self, other) -> None:
         _algebra.check_compatible(self, other)
         if self.partition != other.partition:
@@ -289,70 +291,17 @@ class ChebyshevSlider(ErgonomicsMixin, DerivativeIdMixin):
         obj._device_index = self.__dict__.get("_device_index")
         return obj
 
-    def __add__(self, other):
-        if type(self) is not type(other):
-            return NotImplemented
-        self._check_slider_compatible(other)
-        return self._with_slides([s._combined(s.tensor_values + t.tensor_values) for s, t in zip(self.slides, other.slides)],
-                                 self.pivot_value + other.pivot_value)
+    _check_operand = _check_slider_compatible
 
-    def __sub__(self, other):
-        if type(self) is not type(other):
-            return NotImplemented
-        self._check_slider_compatible(other)
-        return self._with_slides([s._combined(s.tensor_values - t.tensor_values) for s, t in zip(self.slides, other.slides)],
-                                 self.pivot_value - other.pivot_value)
+    def _leafwise(self, op, other) -> "ChebyshevSlider":
+        return self._with_slides([s._leafwise(op, t) for s, t in zip(self.slides, _algebra.leaves(other, "slides"))],
+                                 op(self.pivot_value, getattr(other, "pivot_value", other)))
 
-    def __mul__(self, scalar):
-        if not _algebra.is_scalar(scalar):
-            return NotImplemented
-        f = float(scalar)
-        return self._with_slides([s._combined(s.tensor_values * f) for s in self.slides], self.pivot_value * f)
-
-    def __rmul__(self, scalar):
-        return self.__mul__(scalar)
-
-    def __truediv__(self, scalar):
-        if not _algebra.is_scalar(scalar):
-            return NotImplemented
-        return self.__mul__(1.0 / float(scalar))
-
-    def __neg__(self):
-        return self.__mul__(-1.0)
-
-    def __iadd__(self, other):
-        self._check_slider_compatible(other)
-        for s, t in zip(self.slides, other.slides):
-            s.tensor_values = s.tensor_values + t.tensor_values
-            s._cached_error_estimate = None
-        self.pivot_value = self.pivot_value + other.pivot_value
+    def _leafwise_inplace(self, op, other) -> None:
+        for s, t in zip(self.slides, _algebra.leaves(other, "slides")):
+            s._leafwise_inplace(op, t)
+        self.pivot_value = op(self.pivot_value, getattr(other, "pivot_value", other))
         self._cached_error_estimate = None
-        return self
-
-    def __isub__(self, other):
-        self._check_slider_compatible(other)
-        for s, t in zip(self.slides, other.slides):
-            s.tensor_values = s.tensor_values - t.tensor_values
-            s._cached_error_estimate = None
-        self.pivot_value = self.pivot_value - other.pivot_value
-        self._cached_error_estimate = None
-        return self
-
-    def __imul__(self, scalar):
-        if not _algebra.is_scalar(scalar):
-            return NotImplemented
-        f = float(scalar)
-        for s in self.slides:
-            s.tensor_values = s.tensor_values * f
-            s._cached_error_estimate = None
-        self.pivot_value = self.pivot_value * f
-        self._cached_error_estimate = None
-        return self
-
-    def __itruediv__(self, scalar):
-        if not _algebra.is_scalar(scalar):
-            return NotImplemented
-        return self.__imul__(1.0 / float(scalar))
 
     # ---------------------------------------------------------------- extrude / slice
     def _assembled(self, num_dimensions, domain, n_nodes, partition, pivot_point, slides, pivot_value) -> "ChebyshevSlider":
@@ -521,9 +470,8 @@ class ChebyshevSlider(ErgonomicsMixin, DerivativeIdMixin):
         return out
 
     # ---------------------------------------------------------------- calculus
-    def _domain_arrays(self):
-        dom = np.asarray(self.domain, dtype=float)
-        return _lib.f64(dom[:, 0]), _lib.f64(dom[:, 1])
+    # _calculus.FibreCalculusMixin's methods over these hooks; below, what this class adds to their docstrings.
+    _fibre_prefix = "pcx_slider"
 
     def _owner_grid(self, dim: int):
         """Nodes, weights and differentiation matrix of ``dim``: those of the slide that owns it."""
@@ -532,126 +480,27 @@ class ChebyshevSlider(ErgonomicsMixin, DerivativeIdMixin):
         slide = self.slides[idx]
         return slide.nodes[local], slide.weights[local], slide.diff_matrices[local]
 
-    def _calculus_batch(self, dim: int, rows: np.ndarray, mode: int):
-        """``pcx_slider_calculus_batch`` over validated rows (see :func:`pychebyshev_amd._calculus.run_batch`)."""
-        s = self._dev()
-        lo, hi = self._domain_arrays()
-        rows = _lib.f64(rows)
-        N = rows.shape[0]
+    def _fibre_grid(self, dim: int):
+        return (*self._owner_grid(dim), (self.domain[dim][0], self.domain[dim][1]))
 
-        def call(r, c, v, loc):
-            return s.lib.pcx_slider_calculus_batch(s.handle, int(dim), _lib.p_f64(lo), _lib.p_f64(hi), _lib.p_f64(rows), N,
-                                                   mode, r, c, v, loc)
-        return _calculus.run_batch(call, s.lib, int(self.n_nodes[dim]), N, mode)
-
-    def _calculus(self, dim, fixed, mode: str):
-        if not self._built:
-            raise RuntimeError("Call build() first")
-        d = self.num_dimensions
-        dim, params = _calculus.validate_calculus_args(d, dim, fixed, self.domain)
-        row = _calculus.fixed_row(d, dim, params)
-        nodes, weights, diff = self._owner_grid(dim)
-        return _calculus.run_single(
-            lambda: self.eval_batch(_calculus.fibre_points(d, dim, row, nodes), [0] * d),
-            lambda m: self._calculus_batch(dim, row, m), int(self.n_nodes[dim]), mode, nodes, weights, diff,
-            (self.domain[dim][0], self.domain[dim][1]))
-
-    def _solve_batch(self, dim: int, rows: np.ndarray, targets: np.ndarray, method: int):
-        """``pcx_slider_solve_batch`` over validated rows and targets (see :func:`pychebyshev_amd._calculus.run_solve`)."""
-        s = self._dev()
-        lo, hi = self._domain_arrays()
-        rows, targets = _lib.f64(rows), _lib.f64(targets)
-        N = rows.shape[0]
-
-        def call(r, c, x, st):
-            return s.lib.pcx_slider_solve_batch(s.handle, int(dim), _lib.p_f64(lo), _lib.p_f64(hi), _lib.p_f64(rows),
-                                                _lib.p_f64(targets), N, method, r, c, x, st)
-        return _calculus.run_solve(call, s.lib, int(self.n_nodes[dim]), N, method)
-
-    def _level_roots(self, dim, fixed, level: np.ndarray) -> np.ndarray:
-        if not self._built:
-            raise RuntimeError("Call build() first")
-        d = self.num_dimensions
-        dim, params = _calculus.validate_calculus_args(d, dim, fixed, self.domain)
-        row = _calculus.fixed_row(d, dim, params)
-        nodes = self._owner_grid(dim)[0]
-        return _calculus.run_single_level(
-            lambda: self.eval_batch(_calculus.fibre_points(d, dim, row, nodes), [0] * d),
-            lambda: self._solve_batch(dim, row, level, 0), int(self.n_nodes[dim]), level,
-            (self.domain[dim][0], self.domain[dim][1]))
+    def _fibre_values(self, points) -> np.ndarray:
+        return self.eval_batch(points, [0] * self.num_dimensions)
 
     def roots(self, dim=None, fixed=None, *, level=0.0) -> np.ndarray:
-        """Sorted real roots along ``dim`` with every other dimension fixed (``fixed = {dim_index: value}``;
-        reference slider.py:1178-1224, which slices to one dimension and re-interpolates at the nodes).  The fibre is
-        formed and solved on the device; above 64 nodes the solve runs on the host (NumPy ``chebroots``).  A
-        non-finite fibre raises ``numpy.linalg.LinAlgError``.  A root within ``1e-10`` (of the half-width) of an end
-        of ``domain[dim]``, on either side of it, is returned as exactly that end, and so is a critical point of
-        :meth:`minimize` / :meth:`maximize` (the reference clips from outside only).
-
-        ``level`` (keyword only, a finite scalar) asks for the solutions of ``p = level`` instead: the level is
-        subtracted from the fibre on the device, one rounding per value, before the same solver.  ``None`` or ``0.0``
-        is the call without a level, the same launches and bits."""
-        lv = _calculus.validate_level(level, 1)
-        if lv is None:
-            return self._calculus(dim, fixed, "roots")
-        return self._level_roots(dim, fixed, lv)
+        """:meth:`FibreCalculusMixin.roots <pychebyshev_amd._calculus.FibreCalculusMixin.roots>`, ``level`` included
+        (reference slider.py:1178-1224, which slices to one dimension and re-interpolates at the nodes): here the fibre
+        is formed and solved on the device."""
+        return super().roots(dim, fixed, level=level)
 
     def minimize(self, dim=None, fixed=None):
-        """``(value, location)`` of the minimum along ``dim`` (reference slider.py:1226-1264)."""
-        return self._calculus(dim, fixed, "min")
+        """:meth:`FibreCalculusMixin.minimize <pychebyshev_amd._calculus.FibreCalculusMixin.minimize>` (reference
+        slider.py:1226-1264)."""
+        return super().minimize(dim, fixed)
 
     def maximize(self, dim=None, fixed=None):
-        """``(value, location)`` of the maximum along ``dim`` (reference slider.py:1266-1283)."""
-        return self._calculus(dim, fixed, "max")
-
-    def _calculus_rows(self, dim, fixed) -> np.ndarray:
-        if not self._built:
-            raise RuntimeError("Call build() first")
-        return _calculus.validate_batch_args(self.num_dimensions, dim, fixed, self.domain, self.n_nodes)
-
-    def roots_batch(self, dim: int, fixed, *, level=None):
-        """Roots along ``dim`` for every row of ``fixed`` (host float64 ``(N, d-1)``: the other dimensions in
-        increasing order), in one device pass (extension).  Returns ``(roots, counts)`` as
-        :meth:`ChebyshevApproximation.roots_batch`.  At most 64 nodes along ``dim``.
-
-        ``level`` (keyword only, a finite scalar or an ``(N,)`` array, one level per row) asks for the solutions of ``p = level`` instead: the level is
-        subtracted from the fibre on the device, one rounding per value, before the same solver.  ``None`` or ``0.0``
-        is the call without a level, the same launches and bits."""
-        rows = self._calculus_rows(dim, fixed)
-        lv = _calculus.validate_level(level, rows.shape[0])
-        if lv is None:
-            return self._calculus_batch(int(dim), rows, 0)
-        return self._solve_batch(int(dim), rows, lv, 0)
-
-    def invert_batch(self, dim: int, fixed, targets):
-        """The value of dimension ``dim`` at which the model equals each row's target (extension;
-        ``pcx_slider_solve_batch``, method 1): ``fixed`` as in :meth:`roots_batch`, ``targets`` a finite scalar or ``(N,)``
-        array.  Returns ``(x (N,) float64, status (N,) int32)``.  On the knots ``[lo, nodes..., hi]`` of the fibre
-        a segment brackets when the value at its lower knot equals the target or ``p - target`` changes sign across it;
-        ``status`` is the number of bracketing segments: ``0`` the target is not reached on the knots (``x`` NaN),
-        ``1`` unique on the knots, ``> 1`` not unique (``x`` is the lowest), ``-1`` the fibre is not finite or the
-        solver's fixed iteration cap was reached (``x`` NaN).  ``x`` is the knot itself where the value equals the
-        target there, else the root inside the lowest bracketing segment, down to adjacent doubles.  A constant fibre
-        equal to its target gives ``status = n + 2`` and ``x = lo`` when the sums at the two ends return the constant
-        itself (a power of two, zero), else n to n + 2.  A root closer to 0 than ``2^-9 max(|lo|, |hi|)`` is returned to
-        within ``2^-10 eps max(|lo|, |hi|)``, not to adjacent doubles.  Only crossings between knots are seen: two
-        solutions inside one node interval are invisible here, and ``roots_batch(level=)`` finds them.  At most 64
-        nodes along ``dim``.  One device lane solves one row (``csrc/invert_kernels.h``)."""
-        rows = self._calculus_rows(dim, fixed)
-        return self._solve_batch(int(dim), rows, _calculus.validate_targets(targets, rows.shape[0]), 1)
-
-    def minimize_batch(self, dim: int, fixed):
-        """``(values, locations)``, float64 ``(N,)``, of the minimum along ``dim`` for every row of ``fixed``
-        (extension; arguments as :meth:`roots_batch`).  NaN where a row failed."""
-        rows = self._calculus_rows(dim, fixed)
-        val, loc, _ = self._calculus_batch(int(dim), rows, 1)
-        return val, loc
-
-    def maximize_batch(self, dim: int, fixed):
-        """``(values, locations)`` of the maximum along ``dim`` for every row of ``fixed`` (extension)."""
-        rows = self._calculus_rows(dim, fixed)
-        val, loc, _ = self._calculus_batch(int(dim), rows, 2)
-        return val, loc
+        """:meth:`FibreCalculusMixin.maximize <pychebyshev_amd._calculus.FibreCalculusMixin.maximize>` (reference
+        slider.py:1266-1283)."""
+        return super().maximize(dim, fixed)
 
     def ladder_batch(self, dim: int, fixed, xs, derivative_order=None, *, derivative_id=None, out=None):
         """The slider along ``dim`` at ``m`` values for every row of ``fixed`` (extension; a spot or vol ladder over a
@@ -671,19 +520,12 @@ class ChebyshevSlider(ErgonomicsMixin, DerivativeIdMixin):
         alone (a NaN among the other slides' coordinates then does not show); one inside another slide is that slide's
         derivative at the row, at every value (``xs`` is then not read: a NaN there does not show); one that spans two
         slides or more is ``+0.0`` everywhere."""
-        return _calculus.composite_ladder(self, "pcx_slider_ladder_batch", dim, fixed, xs, derivative_order, derivative_id, out)
+        return self._ladder(dim, fixed, xs, out, self._ladder_orders(derivative_order, derivative_id))
 
     def fibre_batch(self, dim: int, fixed, derivative_order=None, *, derivative_id=None, out=None):
-        """Every row's restriction to ``dim`` at that dimension's own nodes, ``(N, n_dim)``: :meth:`ladder_batch` at the
-        nodes of the slide that owns ``dim`` (ascending), bit for bit."""
-        if not self._built:
-            raise RuntimeError("Call build() first")
-        if isinstance(dim, bool) or not isinstance(dim, (int, np.integer)):
-            raise TypeError(f"dim must be an int, got {type(dim).__name__}")
-        if dim < 0 or dim >= self.num_dimensions:
-            raise ValueError(f"dim {dim} out of range [0, {self.num_dimensions - 1}]")
-        return self.ladder_batch(dim, fixed, np.asarray(self._owner_grid(int(dim))[0], dtype=float), derivative_order,
-                                 derivative_id=derivative_id, out=out)
+        """:meth:`FibreCalculusMixin.fibre_batch <pychebyshev_amd._calculus.FibreCalculusMixin.fibre_batch>` at the
+        nodes of the slide that owns ``dim``."""
+        return super().fibre_batch(dim, fixed, derivative_order, derivative_id=derivative_id, out=out)
 
     # ---------------------------------------------------------------- misc
     @property

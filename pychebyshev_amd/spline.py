@@ -40,7 +40,9 @@ from typing import Callable, List, Sequence, Tuple
 
 import numpy as np
 
-from . import _algebra, _lib
+from . import _algebra, _calculus, _lib
+from ._algebra import ValueAlgebraMixin
+from ._calculus import FibreCalculusMixin
 from ._derivative_ids import DerivativeIdMixin
 from ._ergonomics import ErgonomicsMixin
 from ._version import __version__
@@ -89,7 +91,7 @@ class _DeviceSpline:
             pass
 
 
-class ChebyshevSpline(ErgonomicsMixin, DerivativeIdMixin):
+class ChebyshevSpline(ErgonomicsMixin, DerivativeIdMixin, FibreCalculusMixin, ValueAlgebraMixin):
     """Piecewise Chebyshev interpolation with user-specified knots (signature: reference
     spline.py:106-123)."""
 
@@ -478,11 +480,9 @@ class ChebyshevSpline(ErgonomicsMixin, DerivativeIdMixin):
     def _calculus_pieces(self, dim, fixed):
         """The validated ``dim`` and, along it, each piece selected by the fixed values (``searchsorted(knots, v,
         side="right")`` capped at the last interval, as the reference's ``slice``) with its own ``fixed``."""
-        from ._calculus import validate_calculus_args
-        if not self._built:
-            raise RuntimeError("Call build() first")
+        self._fibre_check_built()
         d = self.num_dimensions
-        dim, params = validate_calculus_args(d, dim, fixed, self.domain)
+        dim, params = _calculus.validate_calculus_args(d, dim, fixed, self.domain)
         vals = dict(params)
         ranges = []
         for k in range(d):
@@ -505,25 +505,24 @@ class ChebyshevSpline(ErgonomicsMixin, DerivativeIdMixin):
             return None
         return [int(v) for v in along[:, 0]]
 
-    def _calculus_batch(self, dim: int, rows: np.ndarray, mode: int):
-        """``pcx_spline_calculus_batch`` over validated rows (see :func:`pychebyshev_amd._calculus.run_batch`)."""
-        from . import _calculus
-        counts = self._dim_counts(dim)
-        s = self._dev()
-        lo = _lib.f64([float(b[0]) for b in self.domain])
-        hi = _lib.f64([float(b[1]) for b in self.domain])
-        rows = _lib.f64(rows)
-        N = rows.shape[0]
+    _fibre_prefix = "pcx_spline"
 
-        def call(r, c, v, loc):
-            return s.lib.pcx_spline_calculus_batch(s.handle, int(dim), _lib.p_f64(lo), _lib.p_f64(hi), _lib.p_f64(rows), N,
-                                                   mode, r, c, v, loc)
-        return _calculus.run_batch(call, s.lib, max(counts), N, mode, width=sum(max(n - 1, 1) for n in counts))
+    def _fibre_counts(self):
+        """The largest node count over the pieces, by dimension: what the 64-node cap sees."""
+        return [max(int(p.n_nodes[k]) for p in self._pieces) for k in range(self.num_dimensions)]
+
+    def _fibre_shape(self, dim: int):
+        """The batch results' ``n`` is the longest piece's, their width the sum over the pieces along ``dim``."""
+        counts = self._dim_counts(dim)
+        return max(counts), sum(max(n - 1, 1) for n in counts)
+
+    def _fibre_nodes(self, dim: int) -> np.ndarray:
+        stride = int(np.prod(self._shape[dim + 1:], dtype=int))
+        return np.concatenate([np.asarray(self._pieces[j * stride].nodes[dim], dtype=float) for j in range(self._shape[dim])])
 
     def _calculus(self, dim, fixed, mode: str):
         """A single call: the one-row batch when every piece along ``dim`` has at most 64 nodes (one device call for all
         pieces), else every piece on its own (their single calls finish long fibres on the host) and the host merge."""
-        from . import _calculus
         dim, pieces, sub = self._calculus_pieces(dim, fixed)
         counts = self._dim_counts(dim)
         if counts is not None and max(counts) <= _calculus.MAX_DEVICE_N:
@@ -534,25 +533,9 @@ class ChebyshevSpline(ErgonomicsMixin, DerivativeIdMixin):
             return _calculus.merge_pieces("roots", [p.roots(dim, sub) for p in pieces], self.domain[dim])
         return _calculus.merge_pieces(mode, [(p.minimize if mode == "min" else p.maximize)(dim, sub) for p in pieces])
 
-    def _solve_batch(self, dim: int, rows: np.ndarray, targets: np.ndarray, method: int):
-        """``pcx_spline_solve_batch`` over validated rows and targets (see :func:`pychebyshev_amd._calculus.run_solve`)."""
-        from . import _calculus
-        counts = self._dim_counts(dim)
-        s = self._dev()
-        lo = _lib.f64([float(b[0]) for b in self.domain])
-        hi = _lib.f64([float(b[1]) for b in self.domain])
-        rows, targets = _lib.f64(rows), _lib.f64(targets)
-        N = rows.shape[0]
-
-        def call(r, c, x, st):
-            return s.lib.pcx_spline_solve_batch(s.handle, int(dim), _lib.p_f64(lo), _lib.p_f64(hi), _lib.p_f64(rows),
-                                                _lib.p_f64(targets), N, method, r, c, x, st)
-        return _calculus.run_solve(call, s.lib, max(counts), N, method, width=sum(max(n - 1, 1) for n in counts))
-
     def _level_roots(self, dim, fixed, level: np.ndarray) -> np.ndarray:
         """As :meth:`_calculus` for the roots at a level: the one-row batch, or every piece on its own and the host
         merge."""
-        from . import _calculus
         dim, pieces, sub = self._calculus_pieces(dim, fixed)
         counts = self._dim_counts(dim)
         if counts is not None and max(counts) <= _calculus.MAX_DEVICE_N:
@@ -563,91 +546,45 @@ class ChebyshevSpline(ErgonomicsMixin, DerivativeIdMixin):
     def roots(self, dim=None, fixed=None, *, level=0.0) -> np.ndarray:
         """Sorted roots along ``dim`` (reference spline.py:1762-1820): every piece along ``dim`` is solved on its own
         interval, the roots are concatenated in piece order and near-duplicates at the knots (``1e-10 (|domain[dim]| +
-        1)``) dropped -- in one device call (the one-row :meth:`roots_batch`) up to 64 nodes per piece.  A root within
-        ``1e-10`` (of the half-width) of an end of its piece's interval, on either side of it, is returned as exactly
-        that end, a knot included, and so is a critical point of :meth:`minimize` / :meth:`maximize` (the reference
-        clips from outside only).
-
-        ``level`` (keyword only, a finite scalar) asks for the solutions of ``p = level`` instead: the level is
-        subtracted from the fibre on the device, one rounding per value, before the same solver.  ``None`` or ``0.0``
-        is the call without a level, the same launches and bits.  Every piece's fibre takes the level."""
-        from . import _calculus
-        lv = _calculus.validate_level(level, 1)
-        if lv is None:
-            return self._calculus(dim, fixed, "roots")
-        return self._level_roots(dim, fixed, lv)
+        1)``) dropped -- in one device call (the one-row :meth:`roots_batch`) up to 64 nodes per piece.  The end rule of
+        :meth:`FibreCalculusMixin.roots <pychebyshev_amd._calculus.FibreCalculusMixin.roots>` holds per piece: a root
+        within ``1e-10`` (of the half-width) of an end of its piece's interval, on either side of it, is returned as
+        exactly that end, a knot included, and so is a critical point of :meth:`minimize` / :meth:`maximize` (the
+        reference clips from outside only).  ``level`` as there; every piece's fibre takes the level."""
+        return super().roots(dim, fixed, level=level)
 
     def minimize(self, dim=None, fixed=None):
-        """``(value, location)`` of the minimum along ``dim`` over the pieces in order, strictly smaller wins
-        (reference spline.py:1822-1865)."""
-        return self._calculus(dim, fixed, "min")
+        """:meth:`FibreCalculusMixin.minimize <pychebyshev_amd._calculus.FibreCalculusMixin.minimize>` over the pieces
+        in order, strictly smaller wins (reference spline.py:1822-1865)."""
+        return super().minimize(dim, fixed)
 
     def maximize(self, dim=None, fixed=None):
-        """``(value, location)`` of the maximum along ``dim`` (reference spline.py:1867-1910)."""
-        return self._calculus(dim, fixed, "max")
+        """:meth:`FibreCalculusMixin.maximize <pychebyshev_amd._calculus.FibreCalculusMixin.maximize>` over the pieces
+        (reference spline.py:1867-1910)."""
+        return super().maximize(dim, fixed)
 
     def _calculus_rows(self, dim, fixed) -> np.ndarray:
-        from . import _calculus
-        if not self._built:
-            raise RuntimeError("Call build() first")
-        largest = [max(int(p.n_nodes[k]) for p in self._pieces) for k in range(self.num_dimensions)]
-        rows = _calculus.validate_batch_args(self.num_dimensions, dim, fixed, self.domain, largest)
+        rows = super()._calculus_rows(dim, fixed)
         if self._dim_counts(int(dim)) is None:
             raise ValueError(f"pieces that share an interval of dimension {dim} differ in their node counts there: "
                              f"the batched solver needs one grid per interval (the single-row calls handle this)")
         return rows
 
     def roots_batch(self, dim: int, fixed, *, level=None):
-        """Roots along ``dim`` for every row of ``fixed`` (host float64 ``(N, d-1)``: the other dimensions in increasing
-        order) in one device pass (extension; ``pcx_spline_calculus_batch``): the fibre points of every piece along
-        ``dim`` go through the spline's own evaluation, one launch solves all rows and pieces, a last kernel merges the
-        pieces of a row as :meth:`roots` does.  Returns ``(roots, counts)``: ``roots`` float64 ``(N, W)`` with ``W`` the
-        sum of ``max(n_j - 1, 1)`` over the pieces along ``dim``, ascending and NaN-padded; ``counts`` int32 ``(N,)``,
-        -1 where a piece's fibre was not finite or its eigenvalue iteration failed.  At most 64 nodes per piece.
-
-        ``level`` (keyword only, a finite scalar or an ``(N,)`` array, one level per row) asks for the solutions of ``p = level`` instead: the level is
-        subtracted from the fibre on the device, one rounding per value, before the same solver.  ``None`` or ``0.0``
-        is the call without a level, the same launches and bits.  Every ``(row, piece)`` fibre takes its row's level."""
-        from . import _calculus
-        rows = self._calculus_rows(dim, fixed)
-        lv = _calculus.validate_level(level, rows.shape[0])
-        if lv is None:
-            return self._calculus_batch(int(dim), rows, 0)
-        return self._solve_batch(int(dim), rows, lv, 0)
+        """:meth:`FibreCalculusMixin.roots_batch <pychebyshev_amd._calculus.FibreCalculusMixin.roots_batch>` over the
+        pieces (``pcx_spline_calculus_batch``): the fibre points of every piece along ``dim`` go through the spline's own
+        evaluation, one launch solves all rows and pieces, a last kernel merges the pieces of a row as :meth:`roots`
+        does.  ``roots`` is ``(N, W)`` with ``W`` the sum of ``max(n_j - 1, 1)`` over the pieces along ``dim``; ``counts``
+        is -1 where a piece's fibre was not finite or its eigenvalue iteration failed.  At most 64 nodes per piece.
+        Every ``(row, piece)`` fibre takes its row's ``level``."""
+        return super().roots_batch(dim, fixed, level=level)
 
     def invert_batch(self, dim: int, fixed, targets):
-        """The value of dimension ``dim`` at which the model equals each row's target (extension;
-        ``pcx_spline_solve_batch``, method 1): ``fixed`` as in :meth:`roots_batch`, ``targets`` a finite scalar or ``(N,)``
-        array.  Returns ``(x (N,) float64, status (N,) int32)``.  Every piece along ``dim`` is solved as its own fibre on its own interval and
-        nodes; ``x`` is the lowest over the pieces with ``status > 0`` and ``status`` the sum of the pieces' statuses, so
-        a solution exactly on an interior knot is counted by both pieces that find it; a ``-1`` in any piece makes the
-        row ``-1``.  Per piece: On the knots ``[lo, nodes..., hi]`` of the fibre
-        a segment brackets when the value at its lower knot equals the target or ``p - target`` changes sign across it;
-        ``status`` is the number of bracketing segments: ``0`` the target is not reached on the knots (``x`` NaN),
-        ``1`` unique on the knots, ``> 1`` not unique (``x`` is the lowest), ``-1`` the fibre is not finite or the
-        solver's fixed iteration cap was reached (``x`` NaN).  ``x`` is the knot itself where the value equals the
-        target there, else the root inside the lowest bracketing segment, down to adjacent doubles.  A constant fibre
-        equal to its target gives ``status = n + 2`` and ``x = lo`` when the sums at the two ends return the constant
-        itself (a power of two, zero), else n to n + 2.  A root closer to 0 than ``2^-9 max(|lo|, |hi|)`` is returned to
-        within ``2^-10 eps max(|lo|, |hi|)``, not to adjacent doubles.  Only crossings between knots are seen: two
-        solutions inside one node interval are invisible here, and ``roots_batch(level=)`` finds them.  At most 64
-        nodes along ``dim``.  One device lane solves one row (``csrc/invert_kernels.h``)."""
-        from . import _calculus
-        rows = self._calculus_rows(dim, fixed)
-        return self._solve_batch(int(dim), rows, _calculus.validate_targets(targets, rows.shape[0]), 1)
-
-    def minimize_batch(self, dim: int, fixed):
-        """``(values, locations)``, float64 ``(N,)``, of the minimum along ``dim`` for every row of ``fixed``
-        (extension; arguments as :meth:`roots_batch`).  NaN where a row failed."""
-        rows = self._calculus_rows(dim, fixed)
-        val, loc, _ = self._calculus_batch(int(dim), rows, 1)
-        return val, loc
-
-    def maximize_batch(self, dim: int, fixed):
-        """``(values, locations)`` of the maximum along ``dim`` for every row of ``fixed`` (extension)."""
-        rows = self._calculus_rows(dim, fixed)
-        val, loc, _ = self._calculus_batch(int(dim), rows, 2)
-        return val, loc
+        """:meth:`FibreCalculusMixin.invert_batch <pychebyshev_amd._calculus.FibreCalculusMixin.invert_batch>` per
+        piece: every piece along ``dim`` is solved as its own fibre on its own interval and nodes; ``x`` is the lowest
+        over the pieces with ``status > 0`` and ``status`` the sum of the pieces' statuses, so a solution exactly on an
+        interior knot is counted by both pieces that find it; a ``-1`` in any piece makes the row ``-1``."""
+        return super().invert_batch(dim, fixed, targets)
 
     def ladder_batch(self, dim: int, fixed, xs, derivative_order=None, *, derivative_id=None, out=None):
         """The spline along ``dim`` at ``m`` values for every row of ``fixed`` (extension; a spot ladder over a kinked
@@ -668,22 +605,14 @@ class ChebyshevSpline(ErgonomicsMixin, DerivativeIdMixin):
         value falls into.  ``result[r, x]`` is bit for bit what that piece's own ``ladder_batch`` gives for the row and
         value, and depends neither on the batch, nor on ``m``, nor on whether ``xs`` is shared.  Pieces that share an
         interval of ``dim`` must have the same node count there."""
-        from . import _calculus
-        return _calculus.composite_ladder(self, "pcx_spline_ladder_batch", dim, fixed, xs, derivative_order, derivative_id, out)
+        return self._ladder(dim, fixed, xs, out, self._ladder_orders(derivative_order, derivative_id))
 
     def fibre_batch(self, dim: int, fixed, derivative_order=None, *, derivative_id=None, out=None):
         """Every row's fibres along ``dim``, ``(N, sum_j n_j)``: the fibres of the pieces along ``dim`` in piece order,
         nodes ascending -- the values the calculus batches expand into points, from one contraction per row and piece.
-        Type-1 nodes never sit on a knot, so this is :meth:`ladder_batch` at the concatenated nodes, bit for bit."""
-        if not self._built:
-            raise RuntimeError("Call build() first")
-        if isinstance(dim, bool) or not isinstance(dim, (int, np.integer)):
-            raise TypeError(f"dim must be an int, got {type(dim).__name__}")
-        if dim < 0 or dim >= self.num_dimensions:
-            raise ValueError(f"dim {dim} out of range [0, {self.num_dimensions - 1}]")
-        stride = int(np.prod(self._shape[dim + 1:], dtype=int))
-        nodes = np.concatenate([np.asarray(self._pieces[j * stride].nodes[dim], dtype=float) for j in range(self._shape[dim])])
-        return self.ladder_batch(dim, fixed, nodes, derivative_order, derivative_id=derivative_id, out=out)
+        Type-1 nodes never sit on a knot, so this is :meth:`ladder_batch` at the concatenated nodes, bit for bit (see
+        :meth:`FibreCalculusMixin.fibre_batch <pychebyshev_amd._calculus.FibreCalculusMixin.fibre_batch>`)."""
+        return super().fibre_batch(dim, fixed, derivative_order, derivative_id=derivative_id, out=out)
 
     # ---------------------------------------------------------------- extrude / slice
     def _reshaped(self, pieces, domain, knots, n_nodes) -> "ChebyshevSpline":
@@ -868,9 +797,9 @@ class ChebyshevSpline(ErgonomicsMixin, DerivativeIdMixin):
         return out
 
     # ---------------------------------------------------------------- algebra
-    # Reference spline.py:1912-2010: piece by piece on the host (ChebyshevApproximation's operators), the
-    # result a new spline over the same knots.  The in-place forms rebind every piece's tensor_values, which is
-    # how the device copy (_DeviceSpline.matches) sees that it is stale.
+    # Reference spline.py:1912-2010; the operators are _algebra.ValueAlgebraMixin's: piece by piece on the host
+    # (the pieces' own hooks), the result a new spline over the same knots.  The in-place forms rebind every
+    # piece's tensor_values, which is how the device copy (_DeviceSpline.matches) sees that it is stale.
     def _check_spline_compatible(self, other) -> None:
         _algebra.check_compatible(self, other)
         if self.knots != other.knots:
@@ -902,67 +831,15 @@ class ChebyshevSpline(ErgonomicsMixin, DerivativeIdMixin):
         obj._device_index = self._device_index
         return obj
 
-    def __add__(self, other):
-        if type(self) is not type(other):
-            return NotImplemented
-        self._check_spline_compatible(other)
-        return self._with_pieces([p._combined(p.tensor_values + q.tensor_values)
-                                  for p, q in zip(self._pieces, other._pieces)])
+    _check_operand = _check_spline_compatible
 
-    def __sub__(self, other):
-        if type(self) is not type(other):
-            return NotImplemented
-        self._check_spline_compatible(other)
-        return self._with_pieces([p._combined(p.tensor_values - q.tensor_values)
-                                  for p, q in zip(self._pieces, other._pieces)])
+    def _leafwise(self, op, other) -> "ChebyshevSpline":
+        return self._with_pieces([p._leafwise(op, q) for p, q in zip(self._pieces, _algebra.leaves(other, "_pieces"))])
 
-    def __mul__(self, scalar):
-        if not _algebra.is_scalar(scalar):
-            return NotImplemented
-        s = float(scalar)
-        return self._with_pieces([p._combined(p.tensor_values * s) for p in self._pieces])
-
-    def __rmul__(self, scalar):
-        return self.__mul__(scalar)
-
-    def __truediv__(self, scalar):
-        if not _algebra.is_scalar(scalar):
-            return NotImplemented
-        return self.__mul__(1.0 / float(scalar))
-
-    def __neg__(self):
-        return self.__mul__(-1.0)
-
-    def __iadd__(self, other):
-        self._check_spline_compatible(other)
-        for p, q in zip(self._pieces, other._pieces):
-            p.tensor_values = p.tensor_values + q.tensor_values
-            p._cached_error_estimate = None
+    def _leafwise_inplace(self, op, other) -> None:
+        for p, q in zip(self._pieces, _algebra.leaves(other, "_pieces")):
+            p._leafwise_inplace(op, q)
         self._cached_error_estimate = None
-        return self
-
-    def __isub__(self, other):
-        self._check_spline_compatible(other)
-        for p, q in zip(self._pieces, other._pieces):
-            p.tensor_values = p.tensor_values - q.tensor_values
-            p._cached_error_estimate = None
-        self._cached_error_estimate = None
-        return self
-
-    def __imul__(self, scalar):
-        if not _algebra.is_scalar(scalar):
-            return NotImplemented
-        s = float(scalar)
-        for p in self._pieces:
-            p.tensor_values = p.tensor_values * s
-            p._cached_error_estimate = None
-        self._cached_error_estimate = None
-        return self
-
-    def __itruediv__(self, scalar):
-        if not _algebra.is_scalar(scalar):
-            return NotImplemented
-        return self.__imul__(1.0 / float(scalar))
 
     # ---------------------------------------------------------------- properties
     @property

@@ -53,7 +53,8 @@ from typing import Callable, List, Sequence, Tuple
 import numpy as np
 from numpy.polynomial.chebyshev import chebpts1
 
-from . import _lib
+from . import _calculus, _lib
+from ._calculus import FibreCalculusMixin
 from ._ergonomics import ErgonomicsMixin
 from ._version import __version__
 
@@ -538,7 +539,7 @@ class _DeviceTT:
             pass
 
 
-class ChebyshevTT(ErgonomicsMixin):
+class ChebyshevTT(ErgonomicsMixin, FibreCalculusMixin):
     """Chebyshev interpolation in tensor-train format (signature: reference :1088-1100)."""
 
     def __init__(self, function: Callable, num_dimensions: int,
@@ -1098,107 +1099,52 @@ class ChebyshevTT(ErgonomicsMixin):
         """``domain`` indexed by user dimension: user dimension u lives at storage position ``_dim_order.index(u)``."""
         return [self.domain[self._dim_order.index(u)] for u in range(self.num_dimensions)]
 
-    def _calculus_batch(self, dim: int, rows: np.ndarray, mode: int):
-        from . import _calculus
-        t = self._dev()
-        rows = _lib.f64(rows)
-        N = rows.shape[0]
+    # _calculus.FibreCalculusMixin's methods over these hooks: ``dim``, ``fixed`` and the rows' columns are in the
+    # user's frame, the handle applies ``dim_order``; below, what this class adds to their docstrings.
+    _fibre_prefix = "pcx_tt"
+    _ladder_own_stream = True
+    _fibre_domain = _user_frame_domain
 
-        def call(r, c, v, loc):
-            return t.lib.pcx_tt_calculus_batch(t.handle, int(dim), _lib.p_f64(rows), N, mode, r, c, v, loc)
-        return _calculus.run_batch(call, t.lib, int(self.n_nodes[self._dim_order.index(dim)]), N, mode)
+    def _fibre_counts(self):
+        return [self.n_nodes[self._dim_order.index(u)] for u in range(self.num_dimensions)]
 
-    def _calculus(self, dim, fixed, mode: str):
-        from . import _calculus
+    def _domain_arrays(self):
+        return ()                                   # the handle knows its domain: the entries take no lo / hi
+
+    def _fibre_grid(self, dim: int):
+        """The grid of user dimension ``dim``, built only where a single call finishes on the host (above 64 nodes)."""
         from .barycentric import chebyshev_nodes, compute_barycentric_weights, compute_differentiation_matrix
-        if not self._built:
-            raise RuntimeError("Call build() first")
-        d = self.num_dimensions
-        udom = self._user_frame_domain()
-        dim, params = _calculus.validate_calculus_args(d, dim, fixed, udom)
-        row = _calculus.fixed_row(d, dim, params)
-        n = int(self.n_nodes[self._dim_order.index(dim)])
-        a, b = udom[dim]
+        pos = self._dim_order.index(dim)
+        n, (a, b) = int(self.n_nodes[pos]), self.domain[pos]
         if n <= _calculus.MAX_DEVICE_N:
-            nodes = weights = diff = None
-        else:
-            nodes = chebyshev_nodes(a, b, n)
-            weights = compute_barycentric_weights(nodes)
-            diff = compute_differentiation_matrix(nodes, weights)
-        return _calculus.run_single(
-            lambda: self.eval_batch(_calculus.fibre_points(d, dim, row, nodes)),
-            lambda m: self._calculus_batch(dim, row, m), n, mode, nodes, weights, diff, (a, b))
+            return None, None, None, (a, b)
+        nodes = chebyshev_nodes(a, b, n)
+        weights = compute_barycentric_weights(nodes)
+        return nodes, weights, compute_differentiation_matrix(nodes, weights), (a, b)
 
-    def _solve_batch(self, dim: int, rows: np.ndarray, targets: np.ndarray, method: int):
-        """``pcx_tt_solve_batch`` over validated rows and targets (see :func:`pychebyshev_amd._calculus.run_solve`)."""
-        from . import _calculus
-        t = self._dev()
-        rows, targets = _lib.f64(rows), _lib.f64(targets)
-        N = rows.shape[0]
-
-        def call(r, c, x, s):
-            return t.lib.pcx_tt_solve_batch(t.handle, int(dim), _lib.p_f64(rows), _lib.p_f64(targets), N, method, r, c, x, s)
-        return _calculus.run_solve(call, t.lib, int(self.n_nodes[self._dim_order.index(dim)]), N, method)
-
-    def _level_roots(self, dim, fixed, level: np.ndarray) -> np.ndarray:
-        from . import _calculus
-        from .barycentric import chebyshev_nodes
-        if not self._built:
-            raise RuntimeError("Call build() first")
-        d = self.num_dimensions
-        udom = self._user_frame_domain()
-        dim, params = _calculus.validate_calculus_args(d, dim, fixed, udom)
-        row = _calculus.fixed_row(d, dim, params)
-        n = int(self.n_nodes[self._dim_order.index(dim)])
-        a, b = udom[dim]
-        return _calculus.run_single_level(
-            lambda: self.eval_batch(_calculus.fibre_points(d, dim, row, chebyshev_nodes(a, b, n))),
-            lambda: self._solve_batch(dim, row, level, 0), n, level, (a, b))
+    def _fibre_values(self, points) -> np.ndarray:
+        return self.eval_batch(points)
 
     def roots(self, dim=None, fixed=None, *, level=0.0) -> np.ndarray:
-        """Sorted roots along user dimension ``dim`` with the others fixed (reference tensor_train.py:1749-1790): the
-        fibre is the TT's values at the nodes of ``dim``, evaluated and solved on the device (above 64 nodes the
-        solve runs on the host).  ``dim`` and ``fixed`` are in the user's frame.  A root within ``1e-10`` (of the
-        half-width) of an end of the domain along ``dim``, on either side of it, is returned as exactly that end, and so
-        is a critical point of :meth:`minimize` / :meth:`maximize` (the reference clips from outside only).
-
-        ``level`` (keyword only, a finite scalar) asks for the solutions of ``p = level`` instead: the level is
-        subtracted from the fibre on the device, one rounding per value, before the same solver.  ``None`` or ``0.0``
-        is the call without a level, the same launches and bits."""
-        from . import _calculus
-        lv = _calculus.validate_level(level, 1)
-        if lv is None:
-            return self._calculus(dim, fixed, "roots")
-        return self._level_roots(dim, fixed, lv)
+        """:meth:`FibreCalculusMixin.roots <pychebyshev_amd._calculus.FibreCalculusMixin.roots>`, ``level`` included,
+        along user dimension ``dim`` (reference tensor_train.py:1749-1790): the fibre is the TT's values at the nodes of
+        ``dim``.  ``dim`` and ``fixed`` are in the user's frame."""
+        return super().roots(dim, fixed, level=level)
 
     def minimize(self, dim=None, fixed=None):
-        """``(value, location)`` of the minimum along user dimension ``dim`` (reference tensor_train.py:1792-1831)."""
-        return self._calculus(dim, fixed, "min")
+        """:meth:`FibreCalculusMixin.minimize <pychebyshev_amd._calculus.FibreCalculusMixin.minimize>` along user
+        dimension ``dim`` (reference tensor_train.py:1792-1831)."""
+        return super().minimize(dim, fixed)
 
     def maximize(self, dim=None, fixed=None):
-        """``(value, location)`` of the maximum along user dimension ``dim`` (reference tensor_train.py:1833-1872)."""
-        return self._calculus(dim, fixed, "max")
-
-    def _calculus_rows(self, dim, fixed) -> np.ndarray:
-        from . import _calculus
-        if not self._built:
-            raise RuntimeError("Call build() first")
-        user_n = [self.n_nodes[self._dim_order.index(u)] for u in range(self.num_dimensions)]
-        return _calculus.validate_batch_args(self.num_dimensions, dim, fixed, self._user_frame_domain(), user_n)
+        """:meth:`FibreCalculusMixin.maximize <pychebyshev_amd._calculus.FibreCalculusMixin.maximize>` along user
+        dimension ``dim`` (reference tensor_train.py:1833-1872)."""
+        return super().maximize(dim, fixed)
 
     def roots_batch(self, dim: int, fixed, *, level=None):
-        """Roots along user dimension ``dim`` for every row of ``fixed`` (extension; as
-        ``ChebyshevApproximation.roots_batch``, columns = the other user dimensions in increasing order).
-
-        ``level`` (keyword only, a finite scalar or an ``(N,)`` array, one level per row) asks for the solutions of ``p = level`` instead: the level is
-        subtracted from the fibre on the device, one rounding per value, before the same solver.  ``None`` or ``0.0``
-        is the call without a level, the same launches and bits."""
-        from . import _calculus
-        rows = self._calculus_rows(dim, fixed)
-        lv = _calculus.validate_level(level, rows.shape[0])
-        if lv is None:
-            return self._calculus_batch(int(dim), rows, 0)
-        return self._solve_batch(int(dim), rows, lv, 0)
+        """:meth:`FibreCalculusMixin.roots_batch <pychebyshev_amd._calculus.FibreCalculusMixin.roots_batch>`, ``level``
+        included, along user dimension ``dim`` (extension; columns = the other user dimensions in increasing order)."""
+        return super().roots_batch(dim, fixed, level=level)
 
     def ladder_batch(self, dim: int, fixed, xs, *, out=None):
         """The model along user dimension ``dim`` at ``m`` values for every row of ``fixed`` (extension; as
@@ -1213,66 +1159,33 @@ class ChebyshevTT(ErgonomicsMixin):
         per value, where ``eval_batch`` on the ``N m`` points walks the whole train ``m`` times per row.
 
         The call takes no derivative spec: a Greek ladder is ``tt.differentiate(spec).ladder_batch(...)``."""
-        from . import _calculus
-        if not self._built:
-            raise RuntimeError("Call build() first")
-        rows = _calculus.validate_fibre_args(self.num_dimensions, dim, fixed, self._user_frame_domain())
-        xv, m, per_row = _calculus.validate_ladder_xs(xs, rows.shape[0])
-        _calculus.validate_ladder_out(out, (rows.shape[0], m))
-        t = self._dev()
-        st = ctypes.c_void_p()
-        _lib.check(t.lib.pcx_tt_stream(t.handle, ctypes.byref(st)), t.lib)
-        lib, h, dim = t.lib, t.handle, int(dim)
-        return _calculus.run_ladder(
-            lib, t.device, st,
-            lambda f, N, x, mm, pr, o: lib.pcx_tt_ladder_batch(h, dim, f, N, x, mm, pr, o),
-            lambda f, N, x, mm, pr, o, s: lib.pcx_tt_ladder_batch_dev(h, dim, f, N, x, mm, pr, o, s),
-            rows, xv, m, per_row, out)
+        return self._ladder(dim, fixed, xs, out)
 
     def fibre_batch(self, dim: int, fixed, *, out=None):
         """Every row's restriction to user dimension ``dim`` at that dimension's ascending nodes (the grid
         :meth:`nodes` gives), ``(N, n_dim)``: :meth:`ladder_batch` at those nodes, bit for bit.  No derivative spec:
         ``tt.differentiate(spec).fibre_batch(...)``."""
         from .barycentric import chebyshev_nodes
-        if not self._built:
-            raise RuntimeError("Call build() first")
-        if isinstance(dim, bool) or not isinstance(dim, (int, np.integer)):
-            raise TypeError(f"dim must be an int, got {type(dim).__name__}")
-        if dim < 0 or dim >= self.num_dimensions:
-            raise ValueError(f"dim {dim} out of range [0, {self.num_dimensions - 1}]")
+        self._fibre_check_built()
+        _calculus.validate_dim(self.num_dimensions, dim)
         pos = self._dim_order.index(int(dim))
         a, b = self.domain[pos]
         return self.ladder_batch(dim, fixed, chebyshev_nodes(a, b, int(self.n_nodes[pos])), out=out)
 
     def invert_batch(self, dim: int, fixed, targets):
-        """The value of dimension ``dim`` at which the model equals each row's target (extension;
-        ``pcx_tt_solve_batch``, method 1): ``fixed`` as in :meth:`roots_batch`, ``targets`` a finite scalar or ``(N,)``
-        array.  Returns ``(x (N,) float64, status (N,) int32)``.  ``dim`` and the columns of ``fixed`` are in the user's frame.  On the knots ``[lo, nodes..., hi]`` of the fibre
-        a segment brackets when the value at its lower knot equals the target or ``p - target`` changes sign across it;
-        ``status`` is the number of bracketing segments: ``0`` the target is not reached on the knots (``x`` NaN),
-        ``1`` unique on the knots, ``> 1`` not unique (``x`` is the lowest), ``-1`` the fibre is not finite or the
-        solver's fixed iteration cap was reached (``x`` NaN).  ``x`` is the knot itself where the value equals the
-        target there, else the root inside the lowest bracketing segment, down to adjacent doubles.  A constant fibre
-        equal to its target gives ``status = n + 2`` and ``x = lo`` when the sums at the two ends return the constant
-        itself (a power of two, zero), else n to n + 2.  A root closer to 0 than ``2^-9 max(|lo|, |hi|)`` is returned to
-        within ``2^-10 eps max(|lo|, |hi|)``, not to adjacent doubles.  Only crossings between knots are seen: two
-        solutions inside one node interval are invisible here, and ``roots_batch(level=)`` finds them.  At most 64
-        nodes along ``dim``.  One device lane solves one row (``csrc/invert_kernels.h``)."""
-        from . import _calculus
-        rows = self._calculus_rows(dim, fixed)
-        return self._solve_batch(int(dim), rows, _calculus.validate_targets(targets, rows.shape[0]), 1)
+        """:meth:`FibreCalculusMixin.invert_batch <pychebyshev_amd._calculus.FibreCalculusMixin.invert_batch>`
+        (``status`` as there).  ``dim`` and the columns of ``fixed`` are in the user's frame."""
+        return super().invert_batch(dim, fixed, targets)
 
     def minimize_batch(self, dim: int, fixed):
-        """``(values, locations)`` of the minimum along user dimension ``dim`` for every row of ``fixed``."""
-        rows = self._calculus_rows(dim, fixed)
-        val, loc, _ = self._calculus_batch(int(dim), rows, 1)
-        return val, loc
+        """:meth:`FibreCalculusMixin.minimize_batch <pychebyshev_amd._calculus.FibreCalculusMixin.minimize_batch>`
+        along user dimension ``dim``."""
+        return super().minimize_batch(dim, fixed)
 
     def maximize_batch(self, dim: int, fixed):
-        """``(values, locations)`` of the maximum along user dimension ``dim`` for every row of ``fixed``."""
-        rows = self._calculus_rows(dim, fixed)
-        val, loc, _ = self._calculus_batch(int(dim), rows, 2)
-        return val, loc
+        """:meth:`FibreCalculusMixin.maximize_batch <pychebyshev_amd._calculus.FibreCalculusMixin.maximize_batch>`
+        along user dimension ``dim``."""
+        return super().maximize_batch(dim, fixed)
 
     def error_estimate(self) -> float:
         """Sum over dimensions of the largest last Chebyshev coefficient (reference :2469-2504)."""
