@@ -394,21 +394,10 @@ static int tt_launch(pcx_tt *h, const double *d_pts, long N, double *d_out, hipS
         const long blocks = (N + PCX_LPP_WG - 1) / PCX_LPP_WG;
         if (blocks > 0x7fffffffL) return fail(PCX_ERR_UNSUPPORTED, "batch too large for one launch");
         const size_t lds = (size_t)h->rmax * PCX_LPP_WG * sizeof(double);
-#define PCX_LPP_GO(RCAP, NJ)                                                                                        \
-        hipLaunchKernelGGL((k_tt_eval_lpp<RCAP, NJ>), dim3((unsigned)blocks), dim3(PCX_LPP_WG), lds, st, h->d_lpp_tab, \
-                           h->dims.d, h->d_lpp_img, d_pts, d_out, N)
-#define PCX_LPP_GO_N(RCAP)                                                                                           \
-        switch (h->lpp_nodes) {                                                                                      \
-        case 1: PCX_LPP_GO(RCAP, 1); break; case 2: PCX_LPP_GO(RCAP, 2); break; case 3: PCX_LPP_GO(RCAP, 3); break;  \
-        case 4: PCX_LPP_GO(RCAP, 4); break; case 5: PCX_LPP_GO(RCAP, 5); break; case 6: PCX_LPP_GO(RCAP, 6); break;  \
-        case 7: PCX_LPP_GO(RCAP, 7); break; case 8: PCX_LPP_GO(RCAP, 8); break; case 9: PCX_LPP_GO(RCAP, 9); break;  \
-        case 10: PCX_LPP_GO(RCAP, 10); break; case 11: PCX_LPP_GO(RCAP, 11); break; case 12: PCX_LPP_GO(RCAP, 12); break; \
-        case 13: PCX_LPP_GO(RCAP, 13); break; case 14: PCX_LPP_GO(RCAP, 14); break; case 15: PCX_LPP_GO(RCAP, 15); break; \
-        case 16: PCX_LPP_GO(RCAP, 16); break; default: PCX_LPP_GO(RCAP, 0); break;                                   \
-        }
-        if (h->lppCap == 8) { PCX_LPP_GO_N(8) } else if (h->lppCap == 12) { PCX_LPP_GO_N(12) } else { PCX_LPP_GO_N(16) }
-#undef PCX_LPP_GO_N
-#undef PCX_LPP_GO
+        tt_lpp_for_model(h->lppCap, h->lpp_nodes, [&](auto rcap, auto nj) {
+            hipLaunchKernelGGL((k_tt_eval_lpp<decltype(rcap)::value, decltype(nj)::value>), dim3((unsigned)blocks), dim3(PCX_LPP_WG),
+                               lds, st, h->d_lpp_tab, h->dims.d, h->d_lpp_img, d_pts, d_out, N);
+        });
         HIP_TRY(hipGetLastError());
         return PCX_OK;
     }
@@ -536,21 +525,10 @@ static int tt_fd_launch(pcx_tt *h, const double *d_pts, long N, const std::vecto
             const long blocks = (N + PCX_LPP_WG - 1) / PCX_LPP_WG;
             if (blocks > 0x7fffffffL) return fail(PCX_ERR_UNSUPPORTED, "batch too large for one launch");
             const size_t lds = (size_t)(h->rmax + 3 * PCX_FD_MAX_ACTIVE + 1) * PCX_LPP_WG * sizeof(double);
-#define PCX_FD_GO(RCAP, NJ)                                                                                             \
-            hipLaunchKernelGGL((k_tt_fd_lpp<RCAP, NJ>), dim3((unsigned)blocks), dim3(PCX_LPP_WG), lds, st, h->d_lpp_tab, d,    \
-                               h->rmax, h->d_lpp_img, d_pts, d_out, N, ostride, (long)s0, pack)
-#define PCX_FD_GO_N(RCAP)                                                                                               \
-            switch (h->lpp_nodes) {                                                                                     \
-            case 1: PCX_FD_GO(RCAP, 1); break; case 2: PCX_FD_GO(RCAP, 2); break; case 3: PCX_FD_GO(RCAP, 3); break;    \
-            case 4: PCX_FD_GO(RCAP, 4); break; case 5: PCX_FD_GO(RCAP, 5); break; case 6: PCX_FD_GO(RCAP, 6); break;    \
-            case 7: PCX_FD_GO(RCAP, 7); break; case 8: PCX_FD_GO(RCAP, 8); break; case 9: PCX_FD_GO(RCAP, 9); break;    \
-            case 10: PCX_FD_GO(RCAP, 10); break; case 11: PCX_FD_GO(RCAP, 11); break; case 12: PCX_FD_GO(RCAP, 12); break; \
-            case 13: PCX_FD_GO(RCAP, 13); break; case 14: PCX_FD_GO(RCAP, 14); break; case 15: PCX_FD_GO(RCAP, 15); break; \
-            case 16: PCX_FD_GO(RCAP, 16); break; default: PCX_FD_GO(RCAP, 0); break;                                     \
-            }
-            if (h->lppCap == 8) { PCX_FD_GO_N(8) } else if (h->lppCap == 12) { PCX_FD_GO_N(12) } else { PCX_FD_GO_N(16) }
-#undef PCX_FD_GO_N
-#undef PCX_FD_GO
+            tt_lpp_for_model(h->lppCap, h->lpp_nodes, [&](auto rcap, auto nj) {
+                hipLaunchKernelGGL((k_tt_fd_lpp<decltype(rcap)::value, decltype(nj)::value>), dim3((unsigned)blocks), dim3(PCX_LPP_WG),
+                                   lds, st, h->d_lpp_tab, d, h->rmax, h->d_lpp_img, d_pts, d_out, N, ostride, (long)s0, pack);
+            });
             HIP_TRY(hipGetLastError());
             continue;
         }

@@ -36,37 +36,15 @@ static int tt_box_launch(const TTBoxView &v, const TTBoxCols &cols, const double
         if (blocks > 0x7fffffffL) return fail(PCX_ERR_UNSUPPORTED, "batch too large for one launch");
         const size_t lds = (size_t)v.rmax * PCX_LPP_WG * sizeof(double);
         const TTLppDim *tab = (const TTLppDim *)v.d_lpp_tab;
-#define PCX_BOX_GO(RCAP, NJ)                                                                                          \
-        hipLaunchKernelGGL((k_tt_box_lpp<RCAP, NJ>), dim3((unsigned)blocks), dim3(PCX_LPP_WG), lds, st, tab, d, cols, \
-                           v.d_lpp_img, d_rows, d_out, N)
-#define PCX_BOX_GO_N(RCAP)                                                                                            \
-        switch (v.lpp_nodes) {                                                                                        \
-        case 1: PCX_BOX_GO(RCAP, 1); break; case 2: PCX_BOX_GO(RCAP, 2); break; case 3: PCX_BOX_GO(RCAP, 3); break;   \
-        case 4: PCX_BOX_GO(RCAP, 4); break; case 5: PCX_BOX_GO(RCAP, 5); break; case 6: PCX_BOX_GO(RCAP, 6); break;   \
-        case 7: PCX_BOX_GO(RCAP, 7); break; case 8: PCX_BOX_GO(RCAP, 8); break; case 9: PCX_BOX_GO(RCAP, 9); break;   \
-        case 10: PCX_BOX_GO(RCAP, 10); break; case 11: PCX_BOX_GO(RCAP, 11); break; case 12: PCX_BOX_GO(RCAP, 12); break; \
-        case 13: PCX_BOX_GO(RCAP, 13); break; case 14: PCX_BOX_GO(RCAP, 14); break; case 15: PCX_BOX_GO(RCAP, 15); break; \
-        case 16: PCX_BOX_GO(RCAP, 16); break; default: PCX_BOX_GO(RCAP, 0); break;                                    \
-        }
-        if (v.lppCap == 8) { PCX_BOX_GO_N(8) } else if (v.lppCap == 12) { PCX_BOX_GO_N(12) } else { PCX_BOX_GO_N(16) }
-#undef PCX_BOX_GO_N
-#undef PCX_BOX_GO
+        tt_lpp_for_model(v.lppCap, v.lpp_nodes, [&](auto rcap, auto nj) {
+            hipLaunchKernelGGL((k_tt_box_lpp<decltype(rcap)::value, decltype(nj)::value>), dim3((unsigned)blocks), dim3(PCX_LPP_WG),
+                               lds, st, tab, d, cols, v.d_lpp_img, d_rows, d_out, N);
+        });
         HIP_TRY(hipGetLastError());
         return PCX_OK;
     }
     if (!v.d_cores) return fail(PCX_ERR_UNSUPPORTED, "the handle holds neither a lane-per-point image nor plain cores");
-    TTBoxGeneric gi{};
-    gi.d = d;
-    gi.rmax = v.rmax;
-    gi.nmax = v.nmax;
-    for (int k = 0; k < d; ++k) {
-        gi.rank[k] = v.ranks[k];
-        gi.n[k] = v.dims->n[k];
-        gi.coff[k] = v.coff[k];
-        gi.lo[k] = v.dims->lo[k];
-        gi.scale[k] = v.dims->scale[k];
-    }
-    gi.rank[d] = v.ranks[d];
+    const TTWaveModel gi = tt_wave_model(v);
     if (!*v.d_rinv) {
         // 1 / j for j = 1 .. nmax + 1 (entry 0 unused): the divisions of the antiderivatives, done once per handle
         std::vector<double> rinv((size_t)gi.nmax + 2, 0.0);
@@ -77,12 +55,9 @@ static int tt_box_launch(const TTBoxView &v, const TTBoxCols &cols, const double
         if (e != hipSuccess) { (void)hipFree(p); HIP_TRY(e); }
         *v.d_rinv = p;
     }
-    const size_t lds = (size_t)4 * (2 * gi.rmax + gi.nmax) * sizeof(double);
-    if (lds > 160 * 1024)
-        return fail(PCX_ERR_UNSUPPORTED, "TT rank %d with %d nodes exceeds the generic box kernel's LDS budget "
-                    "(2 rank + nodes <= 5120)", gi.rmax, gi.nmax);
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void *)k_tt_box_generic, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    size_t lds;
+    const int rc = tt_wave_lds((const void *)k_tt_box_generic, v, 2 * (size_t)v.rmax + v.nmax, "box", "2 rank + nodes", &lds);
+    if (rc) return rc;
     const long blocks = std::min<long>((N + 3) / 4, 256L * 8);
     hipLaunchKernelGGL(k_tt_box_generic, dim3((unsigned)blocks), dim3(256), lds, st, gi, cols, v.d_cores, *v.d_rinv, d_rows, d_out, N);
     HIP_TRY(hipGetLastError());

@@ -36,49 +36,21 @@ static int tt_deriv_launch(const TTBoxView &v, const std::vector<TTDerivPack> &p
         for (int s0 = 0; s0 < m; s0 += PCX_DERIV_PACK) {
             const TTDerivPack &pack = packs[(size_t)s0 / PCX_DERIV_PACK];
             const dim3 grid((unsigned)blocks, (unsigned)std::min(PCX_DERIV_PACK, m - s0));
-#define PCX_DERIV_GO(RCAP, NJ)                                                                                        \
-            hipLaunchKernelGGL((k_tt_deriv_lpp<RCAP, NJ>), grid, dim3(PCX_LPP_WG), lds, st, tab, d, pack, v.d_lpp_img, \
-                               d_pts, d_out, N, m, s0)
-#define PCX_DERIV_GO_N(RCAP)                                                                                          \
-            switch (v.lpp_nodes) {                                                                                    \
-            case 1: PCX_DERIV_GO(RCAP, 1); break; case 2: PCX_DERIV_GO(RCAP, 2); break;                               \
-            case 3: PCX_DERIV_GO(RCAP, 3); break; case 4: PCX_DERIV_GO(RCAP, 4); break;                               \
-            case 5: PCX_DERIV_GO(RCAP, 5); break; case 6: PCX_DERIV_GO(RCAP, 6); break;                               \
-            case 7: PCX_DERIV_GO(RCAP, 7); break; case 8: PCX_DERIV_GO(RCAP, 8); break;                               \
-            case 9: PCX_DERIV_GO(RCAP, 9); break; case 10: PCX_DERIV_GO(RCAP, 10); break;                             \
-            case 11: PCX_DERIV_GO(RCAP, 11); break; case 12: PCX_DERIV_GO(RCAP, 12); break;                           \
-            case 13: PCX_DERIV_GO(RCAP, 13); break; case 14: PCX_DERIV_GO(RCAP, 14); break;                           \
-            case 15: PCX_DERIV_GO(RCAP, 15); break; case 16: PCX_DERIV_GO(RCAP, 16); break;                           \
-            default: PCX_DERIV_GO(RCAP, 0); break;                                                                    \
-            }
-            if (v.lppCap == 8) { PCX_DERIV_GO_N(8) } else if (v.lppCap == 12) { PCX_DERIV_GO_N(12) } else { PCX_DERIV_GO_N(16) }
-#undef PCX_DERIV_GO_N
-#undef PCX_DERIV_GO
+            tt_lpp_for_model(v.lppCap, v.lpp_nodes, [&](auto rcap, auto nj) {
+                hipLaunchKernelGGL((k_tt_deriv_lpp<decltype(rcap)::value, decltype(nj)::value>), grid, dim3(PCX_LPP_WG), lds, st, tab,
+                                   d, pack, v.d_lpp_img, d_pts, d_out, N, m, s0);
+            });
             HIP_TRY(hipGetLastError());
         }
         return PCX_OK;
     }
     if (!v.d_cores) return fail(PCX_ERR_UNSUPPORTED, "the handle holds neither a lane-per-point image nor plain cores");
     TTDerivGeneric gd{};
-    TTBoxGeneric &gi = gd.g;
-    gi.d = d;
-    gi.rmax = v.rmax;
-    gi.nmax = v.nmax;
-    for (int k = 0; k < d; ++k) {
-        gi.rank[k] = v.ranks[k];
-        gi.n[k] = v.dims->n[k];
-        gi.coff[k] = v.coff[k];
-        gi.lo[k] = v.dims->lo[k];
-        gi.scale[k] = v.dims->scale[k];
-        gd.col[k] = v.dims->col[k];
-    }
-    gi.rank[d] = v.ranks[d];
-    const size_t lds = (size_t)4 * (2 * gi.rmax + gi.nmax) * sizeof(double);
-    if (lds > 160 * 1024)
-        return fail(PCX_ERR_UNSUPPORTED, "TT rank %d with %d nodes exceeds the generic derivative kernel's LDS budget "
-                    "(2 rank + nodes <= 5120)", gi.rmax, gi.nmax);
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void *)k_tt_deriv_generic, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    gd.g = tt_wave_model(v);
+    for (int k = 0; k < d; ++k) gd.col[k] = v.dims->col[k];
+    size_t lds;
+    const int rc = tt_wave_lds((const void *)k_tt_deriv_generic, v, 2 * (size_t)v.rmax + v.nmax, "derivative", "2 rank + nodes", &lds);
+    if (rc) return rc;
     const long blocks = std::min<long>((N + 3) / 4, 256L * 8);
     for (int s0 = 0; s0 < m; s0 += PCX_DERIV_PACK) {
         const dim3 grid((unsigned)blocks, (unsigned)std::min(PCX_DERIV_PACK, m - s0));

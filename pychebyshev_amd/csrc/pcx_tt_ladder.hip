@@ -27,7 +27,6 @@ static int tt_ladder_plan(const TTBoxView &v, int dim, int m, TTLadder *lp) {
 static int tt_ladder_launch(const TTBoxView &v, const TTLadder &lp, const double *d_fixed, long fstride, const double *d_xs,
                             long xstride, long N, double *d_out, hipStream_t st) {
     if (N == 0 || lp.m == 0) return PCX_OK;
-    const int d = lp.d;
     if (v.lppCap) {
         const long blocks = (N + PCX_LPP_WG - 1) / PCX_LPP_WG;
         if (blocks > 0x7fffffffL) return fail(PCX_ERR_UNSUPPORTED, "batch too large for one launch");
@@ -38,22 +37,10 @@ static int tt_ladder_launch(const TTBoxView &v, const TTLadder &lp, const double
         return PCX_OK;
     }
     if (!v.d_cores) return fail(PCX_ERR_UNSUPPORTED, "the handle holds neither a lane-per-point image nor plain cores");
-    TTLadderGeneric gi{};
-    gi.nmax = v.nmax;
-    for (int k = 0; k < d; ++k) {
-        gi.rank[k] = v.ranks[k];
-        gi.n[k] = v.dims->n[k];
-        gi.coff[k] = v.coff[k];
-        gi.lo[k] = v.dims->lo[k];
-        gi.scale[k] = v.dims->scale[k];
-    }
-    gi.rank[d] = v.ranks[d];
-    const size_t lds = (size_t)4 * (3 * v.rmax + 2 * v.nmax) * sizeof(double);
-    if (lds > 160 * 1024)
-        return fail(PCX_ERR_UNSUPPORTED, "TT rank %d with %d nodes exceeds the generic ladder kernel's LDS budget "
-                    "(3 rank + 2 nodes <= 5120)", v.rmax, v.nmax);
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void *)k_tt_ladder_generic, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const TTWaveModel gi = tt_wave_model(v);
+    size_t lds;
+    const int rc = tt_wave_lds((const void *)k_tt_ladder_generic, v, 3 * (size_t)v.rmax + 2 * v.nmax, "ladder", "3 rank + 2 nodes", &lds);
+    if (rc) return rc;
     const long blocks = std::min<long>((N + 3) / 4, 256L * 8);
     hipLaunchKernelGGL(k_tt_ladder_generic, dim3((unsigned)blocks), dim3(256), lds, st, gi, lp, v.d_cores, d_fixed, fstride, d_xs,
                        xstride, d_out, N);

@@ -21,6 +21,7 @@
 #pragma once
 
 #include "tt_lpp_kernels.h"
+#include "tt_wave_kernels.h"
 
 struct TTBoxCols {
     int width;                    // doubles per row: d + (integrated dimensions)
@@ -33,15 +34,7 @@ struct TTBoxCols {
 template <int NJ>
 __device__ __forceinline__ void tt_box_basis(bool integ, double ta, double tb, double half, double (&q)[NJ]) {
 #pragma clang fp contract(off)
-    if (!integ) {
-        const double x2 = ta + ta;
-        q[0] = 1.0;
-        asm volatile("" : "+v"(q[0]));       // as tt_lpp_body: one v_mul_f64 per core element of j = 0
-        if constexpr (NJ > 1) q[1] = ta;
-#pragma unroll
-        for (int j = 2; j < NJ; ++j) q[j] = __builtin_fma(x2, q[j - 1], -q[j - 2]);
-        return;
-    }
+    if (!integ) return tt_lpp_basis<NJ>(ta, q);
     q[0] = half * (tb - ta);
     if constexpr (NJ > 1) q[1] = half * (0.5 * (tb * tb) - 0.5 * (ta * ta));
     if constexpr (NJ > 2) {
@@ -60,65 +53,12 @@ __device__ __forceinline__ void tt_box_basis(bool integ, double ta, double tb, d
     }
 }
 
-// tt_lpp_body with the basis handed in
-template <int RL, int NJ>
-__device__ __forceinline__ void tt_box_body(pcx_lpp_cptr G, int rr, const double (&q)[NJ], double *vl) {
-    double v[RL];
-#pragma unroll
-    for (int a = 0; a < RL; ++a) v[a] = vl[a * PCX_LPP_WG];
-    for (int b = 0; b < rr; ++b, G += RL * NJ) {
-        double M[RL];
-#pragma unroll
-        for (int a = 0; a < RL; ++a) M[a] = G[a * NJ] * q[0];
-#pragma unroll
-        for (int j = 1; j < NJ; ++j)
-#pragma unroll
-            for (int a = 0; a < RL; ++a) M[a] = __builtin_fma(q[j], G[a * NJ + j], M[a]);
-        double s;
-        if constexpr (RL < 4) {
-            s = v[0] * M[0];
-#pragma unroll
-            for (int a = 1; a < RL; ++a) s = __builtin_fma(v[a], M[a], s);
-        } else {
-            double s0 = v[0] * M[0], s1 = v[1] * M[1];
-#pragma unroll
-            for (int a = 2; a < RL; a += 2) {
-                s0 = __builtin_fma(v[a], M[a], s0);
-                if (a + 1 < RL) s1 = __builtin_fma(v[a + 1], M[a + 1], s1);
-            }
-            s = s0 + s1;
-        }
-        vl[b * PCX_LPP_WG] = s;
-    }
-}
-
-#define PCX_BOX_RANK_CASES_8(NJ)                                                                          \
-    case 1: tt_box_body<1, NJ>(G, rr, q, vl); break; case 2: tt_box_body<2, NJ>(G, rr, q, vl); break;     \
-    case 3: tt_box_body<3, NJ>(G, rr, q, vl); break; case 4: tt_box_body<4, NJ>(G, rr, q, vl); break;     \
-    case 5: tt_box_body<5, NJ>(G, rr, q, vl); break; case 6: tt_box_body<6, NJ>(G, rr, q, vl); break;     \
-    case 7: tt_box_body<7, NJ>(G, rr, q, vl); break; case 8: tt_box_body<8, NJ>(G, rr, q, vl); break;
-#define PCX_BOX_RANK_CASES_12(NJ)                                                                         \
-    case 9: tt_box_body<9, NJ>(G, rr, q, vl); break; case 10: tt_box_body<10, NJ>(G, rr, q, vl); break;   \
-    case 11: tt_box_body<11, NJ>(G, rr, q, vl); break; case 12: tt_box_body<12, NJ>(G, rr, q, vl); break;
-#define PCX_BOX_RANK_CASES_16(NJ)                                                                         \
-    case 13: tt_box_body<13, NJ>(G, rr, q, vl); break; case 14: tt_box_body<14, NJ>(G, rr, q, vl); break; \
-    case 15: tt_box_body<15, NJ>(G, rr, q, vl); break; case 16: tt_box_body<16, NJ>(G, rr, q, vl); break;
-
 template <int RCAP, int NJ>
 __device__ __forceinline__ void tt_box_dim(int rl, pcx_lpp_cptr G, int rr, bool integ, double ta, double tb, double half,
                                            double *vl) {
     double q[NJ];
     tt_box_basis<NJ>(integ, ta, tb, half, q);
-    switch (rl) {
-        PCX_BOX_RANK_CASES_8(NJ)
-        default:
-            if constexpr (RCAP > 12) {
-                switch (rl) { PCX_BOX_RANK_CASES_12(NJ) PCX_BOX_RANK_CASES_16(NJ) default: break; }
-            } else if constexpr (RCAP > 8) {
-                switch (rl) { PCX_BOX_RANK_CASES_12(NJ) default: break; }
-            }
-            break;
-    }
+    tt_lpp_for_rank<RCAP>(rl, [&](auto r) { tt_lpp_contract<decltype(r)::value, NJ>(G, rr, q, vl); });
 }
 
 // One wave per workgroup, one row per lane; dynamic LDS = max rank * 64 * 8 bytes.  RCAP and NJ as k_tt_eval_lpp.
@@ -152,45 +92,16 @@ k_tt_box_lpp(const TTLppDim *__restrict__ tab, int d, TTBoxCols cols, const doub
         if constexpr (NJ > 0) {
             tt_box_dim<RCAP, NJ>(rl, G, rr, integ, ta, tb, half, vl);
         } else {
-            switch (ct[k].n) {
-            case 1: tt_box_dim<RCAP, 1>(rl, G, rr, integ, ta, tb, half, vl); break;
-            case 2: tt_box_dim<RCAP, 2>(rl, G, rr, integ, ta, tb, half, vl); break;
-            case 3: tt_box_dim<RCAP, 3>(rl, G, rr, integ, ta, tb, half, vl); break;
-            case 4: tt_box_dim<RCAP, 4>(rl, G, rr, integ, ta, tb, half, vl); break;
-            case 5: tt_box_dim<RCAP, 5>(rl, G, rr, integ, ta, tb, half, vl); break;
-            case 6: tt_box_dim<RCAP, 6>(rl, G, rr, integ, ta, tb, half, vl); break;
-            case 7: tt_box_dim<RCAP, 7>(rl, G, rr, integ, ta, tb, half, vl); break;
-            case 8: tt_box_dim<RCAP, 8>(rl, G, rr, integ, ta, tb, half, vl); break;
-            case 9: tt_box_dim<RCAP, 9>(rl, G, rr, integ, ta, tb, half, vl); break;
-            case 10: tt_box_dim<RCAP, 10>(rl, G, rr, integ, ta, tb, half, vl); break;
-            case 11: tt_box_dim<RCAP, 11>(rl, G, rr, integ, ta, tb, half, vl); break;
-            case 12: tt_box_dim<RCAP, 12>(rl, G, rr, integ, ta, tb, half, vl); break;
-            case 13: tt_box_dim<RCAP, 13>(rl, G, rr, integ, ta, tb, half, vl); break;
-            case 14: tt_box_dim<RCAP, 14>(rl, G, rr, integ, ta, tb, half, vl); break;
-            case 15: tt_box_dim<RCAP, 15>(rl, G, rr, integ, ta, tb, half, vl); break;
-            case 16: tt_box_dim<RCAP, 16>(rl, G, rr, integ, ta, tb, half, vl); break;
-            default: break;
-            }
+            tt_lpp_for_nodes(ct[k].n, [&](auto nj) { tt_box_dim<RCAP, decltype(nj)::value>(rl, G, rr, integ, ta, tb, half, vl); });
         }
     }
     if (p < N) out[p] = vl[0];
 }
 
-// Every other model (rank > 16 or n > 16): one wave per row as k_tt_eval_generic -- lanes over the right rank, the
-// cores in their natural (r, n, r') layout, v and q in the wave's LDS slice (2 rmax + nmax doubles per wave).  Lane 0
-// forms the basis as in k_tt_eval_generic; rinv[j] = 1 / j (nmax + 2 doubles, the handle's) spares it the divisions.
-struct TTBoxGeneric {
-    int d;
-    int rank[PCX_MAX_DIMS + 1];
-    int n[PCX_MAX_DIMS];
-    long coff[PCX_MAX_DIMS];
-    double lo[PCX_MAX_DIMS];
-    double scale[PCX_MAX_DIMS];
-    int rmax, nmax;
-};
-
+// Every other model (rank > 16 or n > 16): one wave per row (tt_wave_kernels.h), 2 rmax + nmax doubles of LDS per wave.
+// rinv[j] = 1 / j (nmax + 2 doubles, the handle's) spares lane 0 the divisions of the antiderivatives.
 __global__ void __launch_bounds__(256)
-k_tt_box_generic(TTBoxGeneric gi, TTBoxCols cols, const double *__restrict__ cores, const double *__restrict__ rinv,
+k_tt_box_generic(TTWaveModel gi, TTBoxCols cols, const double *__restrict__ cores, const double *__restrict__ rinv,
                  const double *__restrict__ rows, double *__restrict__ out, long N) {
 #pragma clang fp contract(off)
     extern __shared__ double lds_boxg[];
@@ -206,15 +117,8 @@ k_tt_box_generic(TTBoxGeneric gi, TTBoxCols cols, const double *__restrict__ cor
             const int rl = gi.rank[k], rr = gi.rank[k + 1], n = gi.n[k];
             if (lane == 0) {
                 const double ta = __builtin_fma(row[cols.off[k]] - gi.lo[k], gi.scale[k], -1.0);
-                if (!cols.integ[k]) {             // T_0 .. T_{n-1} by the forward recurrence
-                    double tp = 1.0, tc = ta;
-                    const double x2 = ta + ta;
-                    for (int j = 0; j < n; ++j) {
-                        q[j] = tp;
-                        const double tn = __builtin_fma(x2, tc, -tp);
-                        tp = tc;
-                        tc = tn;
-                    }
+                if (!cols.integ[k]) {
+                    tt_wave_basis(ta, n, q);
                 } else {
                     const double tb = __builtin_fma(row[cols.off[k] + 1] - gi.lo[k], gi.scale[k], -1.0);
                     const double half = cols.half[k];
@@ -233,18 +137,7 @@ k_tt_box_generic(TTBoxGeneric gi, TTBoxCols cols, const double *__restrict__ cor
                     }
                 }
             }
-            // wave-private LDS: operations of one wave execute in order, no barrier needed
-            const double *G = cores + gi.coff[k];
-            for (int b = lane; b < rr; b += 64) {
-                double s = 0.0;
-                for (int a = 0; a < rl; ++a) {
-                    const double *ga = G + ((long)a * n) * rr + b;
-                    double w = 0.0;
-                    for (int j = 0; j < n; ++j) w = __builtin_fma(q[j], ga[(long)j * rr], w);
-                    s = __builtin_fma(va[a], w, s);
-                }
-                vb[b] = s;
-            }
+            tt_wave_left(cores + gi.coff[k], rl, n, rr, q, va, vb, lane);
             double *t = va; va = vb; vb = t;
         }
         if (lane == 0) out[p] = va[0];

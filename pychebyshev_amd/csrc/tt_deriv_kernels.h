@@ -11,8 +11,8 @@
 //     T'_{j+1}  = 2 s T'_j  - T'_{j-1}  + 2 T_j
 //     T''_{j+1} = 2 s T''_j - T''_{j-1} + 4 T'_j
 // No division, nothing singular at a node or at s = +-1 (T'_j(+-1) and T''_j(+-1) are integers and come out exact).
-// T^(p)_j = 0 for j < p, so a spec with p >= n_k gives exactly 0.  p = 0 is tt_box_basis' kept branch: a spec of zeros
-// is the box kernel without an integrated dimension.  One chain per (row, spec): no stencil, no truncation error, any
+// T^(p)_j = 0 for j < p, so a spec with p >= n_k gives exactly 0.  p = 0 is the value basis (tt_lpp_basis), as in tt_box_basis'
+// kept branch: a spec of zeros is the box kernel without an integrated dimension.  One chain per (row, spec): no stencil, no truncation error, any
 // number of differentiated dimensions.
 //
 // Specs go on blockIdx.y; their orders travel by value (TTDerivPack: two bits per STORAGE position), so the branch on
@@ -20,11 +20,8 @@
 // n <= 16) and wave per row on the plain cores for every other model.
 #pragma once
 
-// tt_box_body, the rank-case macros and TTBoxGeneric come from the box header.  Its one non-template kernel belongs to
-// pcx_tt_box.hip: this unit's copy takes another name, or the two objects would define one symbol twice.
-#define k_tt_box_generic k_tt_box_generic_in_deriv_unit
-#include "tt_box_kernels.h"
-#undef k_tt_box_generic
+#include "tt_lpp_kernels.h"
+#include "tt_wave_kernels.h"
 
 #define PCX_DERIV_PACK 64         // specs per launch
 
@@ -38,15 +35,8 @@ __device__ __forceinline__ int tt_deriv_order(unsigned int ord, int k) { return 
 template <int NJ>
 __device__ __forceinline__ void tt_deriv_basis(int o, double s, double sc, double (&q)[NJ]) {
 #pragma clang fp contract(off)
+    if (o == 0) return tt_lpp_basis<NJ>(s, q);
     const double x2 = s + s;
-    if (o == 0) {
-        q[0] = 1.0;
-        asm volatile("" : "+v"(q[0]));       // as tt_lpp_body: one v_mul_f64 per core element of j = 0
-        if constexpr (NJ > 1) q[1] = s;
-#pragma unroll
-        for (int j = 2; j < NJ; ++j) q[j] = __builtin_fma(x2, q[j - 1], -q[j - 2]);
-        return;
-    }
     if (o == 1) {
         q[0] = 0.0;
         if constexpr (NJ > 1) q[1] = sc;
@@ -84,16 +74,7 @@ template <int RCAP, int NJ>
 __device__ __forceinline__ void tt_deriv_dim(int rl, pcx_lpp_cptr G, int rr, int o, double s, double sc, double *vl) {
     double q[NJ];
     tt_deriv_basis<NJ>(o, s, sc, q);
-    switch (rl) {
-        PCX_BOX_RANK_CASES_8(NJ)
-        default:
-            if constexpr (RCAP > 12) {
-                switch (rl) { PCX_BOX_RANK_CASES_12(NJ) PCX_BOX_RANK_CASES_16(NJ) default: break; }
-            } else if constexpr (RCAP > 8) {
-                switch (rl) { PCX_BOX_RANK_CASES_12(NJ) default: break; }
-            }
-            break;
-    }
+    tt_lpp_for_rank<RCAP>(rl, [&](auto r) { tt_lpp_contract<decltype(r)::value, NJ>(G, rr, q, vl); });
 }
 
 // One wave per workgroup, one row per lane, one spec per blockIdx.y (gridDim.y <= PCX_DERIV_PACK); dynamic LDS =
@@ -124,35 +105,16 @@ k_tt_deriv_lpp(const TTLppDim *__restrict__ tab, int d, TTDerivPack pack, const 
         if constexpr (NJ > 0) {
             tt_deriv_dim<RCAP, NJ>(rl, G, rr, o, s, sc, vl);
         } else {
-            switch (ct[k].n) {
-            case 1: tt_deriv_dim<RCAP, 1>(rl, G, rr, o, s, sc, vl); break;
-            case 2: tt_deriv_dim<RCAP, 2>(rl, G, rr, o, s, sc, vl); break;
-            case 3: tt_deriv_dim<RCAP, 3>(rl, G, rr, o, s, sc, vl); break;
-            case 4: tt_deriv_dim<RCAP, 4>(rl, G, rr, o, s, sc, vl); break;
-            case 5: tt_deriv_dim<RCAP, 5>(rl, G, rr, o, s, sc, vl); break;
-            case 6: tt_deriv_dim<RCAP, 6>(rl, G, rr, o, s, sc, vl); break;
-            case 7: tt_deriv_dim<RCAP, 7>(rl, G, rr, o, s, sc, vl); break;
-            case 8: tt_deriv_dim<RCAP, 8>(rl, G, rr, o, s, sc, vl); break;
-            case 9: tt_deriv_dim<RCAP, 9>(rl, G, rr, o, s, sc, vl); break;
-            case 10: tt_deriv_dim<RCAP, 10>(rl, G, rr, o, s, sc, vl); break;
-            case 11: tt_deriv_dim<RCAP, 11>(rl, G, rr, o, s, sc, vl); break;
-            case 12: tt_deriv_dim<RCAP, 12>(rl, G, rr, o, s, sc, vl); break;
-            case 13: tt_deriv_dim<RCAP, 13>(rl, G, rr, o, s, sc, vl); break;
-            case 14: tt_deriv_dim<RCAP, 14>(rl, G, rr, o, s, sc, vl); break;
-            case 15: tt_deriv_dim<RCAP, 15>(rl, G, rr, o, s, sc, vl); break;
-            case 16: tt_deriv_dim<RCAP, 16>(rl, G, rr, o, s, sc, vl); break;
-            default: break;
-            }
+            tt_lpp_for_nodes(ct[k].n, [&](auto nj) { tt_deriv_dim<RCAP, decltype(nj)::value>(rl, G, rr, o, s, sc, vl); });
         }
     }
     if (p < N) out[p * m + s0 + (long)blockIdx.y] = vl[0];
 }
 
-// Every other model (rank > 16 or n > 16): one wave per row as k_tt_box_generic -- lanes over the right rank, the cores
-// in their natural (r, n, r') layout, v and q in the wave's LDS slice (2 rmax + nmax doubles per wave); lane 0 forms
-// the basis.  col[k] = the user column read by storage position k.
+// Every other model (rank > 16 or n > 16): one wave per row (tt_wave_kernels.h), 2 rmax + nmax doubles of LDS per wave.
+// col[k] = the user column read by storage position k.
 struct TTDerivGeneric {
-    TTBoxGeneric g;
+    TTWaveModel g;
     int col[PCX_MAX_DIMS];
 };
 
@@ -161,7 +123,7 @@ k_tt_deriv_generic(TTDerivGeneric gd, TTDerivPack pack, const double *__restrict
                    double *__restrict__ out, long N, int m, int s0) {
 #pragma clang fp contract(off)
     extern __shared__ double lds_derivg[];
-    const TTBoxGeneric &gi = gd.g;
+    const TTWaveModel &gi = gd.g;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const unsigned int ord = pack.ord[blockIdx.y];
@@ -176,19 +138,13 @@ k_tt_deriv_generic(TTDerivGeneric gd, TTDerivPack pack, const double *__restrict
             if (lane == 0) {
                 const double sc = gi.scale[k];
                 const double s = __builtin_fma(row[gd.col[k]] - gi.lo[k], sc, -1.0);
-                const double x2 = s + s;
                 const int o = tt_deriv_order(ord, k);
-                const double f = o == 1 ? sc : sc * sc;
-                double tm = 1.0, tc = s, um = 0.0, uc = 1.0, wm = 0.0, wc = 0.0;      // T, T', T'' at j - 1 and j; j = 1
                 if (o == 0) {
-                    double tp = 1.0;
-                    for (int j = 0; j < n; ++j) {             // T_0 .. T_{n-1}, as k_tt_box_generic
-                        q[j] = tp;
-                        const double tn = __builtin_fma(x2, tc, -tp);
-                        tp = tc;
-                        tc = tn;
-                    }
+                    tt_wave_basis(s, n, q);
                 } else {
+                    const double x2 = s + s;
+                    const double f = o == 1 ? sc : sc * sc;
+                    double tm = 1.0, tc = s, um = 0.0, uc = 1.0, wm = 0.0, wc = 0.0;      // T, T', T'' at j - 1 and j; j = 1
                     q[0] = 0.0;
                     if (n > 1) q[1] = o == 1 ? sc : 0.0;
                     for (int j = 2; j < n; ++j) {
@@ -202,18 +158,7 @@ k_tt_deriv_generic(TTDerivGeneric gd, TTDerivPack pack, const double *__restrict
                     }
                 }
             }
-            // wave-private LDS: operations of one wave execute in order, no barrier needed
-            const double *G = cores + gi.coff[k];
-            for (int b = lane; b < rr; b += 64) {
-                double s = 0.0;
-                for (int a = 0; a < rl; ++a) {
-                    const double *ga = G + ((long)a * n) * rr + b;
-                    double w = 0.0;
-                    for (int j = 0; j < n; ++j) w = __builtin_fma(q[j], ga[(long)j * rr], w);
-                    s = __builtin_fma(va[a], w, s);
-                }
-                vb[b] = s;
-            }
+            tt_wave_left(cores + gi.coff[k], rl, n, rr, q, va, vb, lane);
             double *t = va; va = vb; vb = t;
         }
         if (lane == 0) out[p * m + s0 + (long)blockIdx.y] = va[0];

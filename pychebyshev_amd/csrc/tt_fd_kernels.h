@@ -147,25 +147,7 @@ k_tt_fd_lpp(const TTLppDim *__restrict__ tab, int d, int vrows, const double *__
                 if constexpr (NJ > 0) {
                     tt_lpp_dim<RCAP, NJ>(rl, G, rr, x, vl);
                 } else {
-                    switch (ct[k].n) {
-                    case 1: tt_lpp_dim<RCAP, 1>(rl, G, rr, x, vl); break;
-                    case 2: tt_lpp_dim<RCAP, 2>(rl, G, rr, x, vl); break;
-                    case 3: tt_lpp_dim<RCAP, 3>(rl, G, rr, x, vl); break;
-                    case 4: tt_lpp_dim<RCAP, 4>(rl, G, rr, x, vl); break;
-                    case 5: tt_lpp_dim<RCAP, 5>(rl, G, rr, x, vl); break;
-                    case 6: tt_lpp_dim<RCAP, 6>(rl, G, rr, x, vl); break;
-                    case 7: tt_lpp_dim<RCAP, 7>(rl, G, rr, x, vl); break;
-                    case 8: tt_lpp_dim<RCAP, 8>(rl, G, rr, x, vl); break;
-                    case 9: tt_lpp_dim<RCAP, 9>(rl, G, rr, x, vl); break;
-                    case 10: tt_lpp_dim<RCAP, 10>(rl, G, rr, x, vl); break;
-                    case 11: tt_lpp_dim<RCAP, 11>(rl, G, rr, x, vl); break;
-                    case 12: tt_lpp_dim<RCAP, 12>(rl, G, rr, x, vl); break;
-                    case 13: tt_lpp_dim<RCAP, 13>(rl, G, rr, x, vl); break;
-                    case 14: tt_lpp_dim<RCAP, 14>(rl, G, rr, x, vl); break;
-                    case 15: tt_lpp_dim<RCAP, 15>(rl, G, rr, x, vl); break;
-                    case 16: tt_lpp_dim<RCAP, 16>(rl, G, rr, x, vl); break;
-                    default: break;
-                    }
+                    tt_lpp_for_nodes(ct[k].n, [&](auto nj) { tt_lpp_dim<RCAP, decltype(nj)::value>(rl, G, rr, x, vl); });
                 }
             }
             (void)fd_push(sp, leaf, dig, vl[0], cl, result);

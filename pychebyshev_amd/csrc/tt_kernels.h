@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "pcx_common.h"
+#include "tt_wave_kernels.h"
 
 // Core packing: frag[dim][j][c][t][l] = G[a = 4c + (l>>4)][j][b = 16t + (l&15)], zero padded;
 // c < rc = ceil(r_left/4), t < rt = ceil(r_right/16).
@@ -277,7 +278,7 @@ k_tt_eval_mfma(TTDims dims, TTRanks rk, const double *__restrict__ frag,
 
 // Ranks above 64 (outside the MFMA tilings): one wavefront walks one point at a time through
 // the chain with the cores in their natural (r, n, r') layout -- lanes over the right rank b
-// (coalesced core reads from L2), v and the polynomial values in a per-wave LDS slice.
+// (coalesced core reads from L2), v and the polynomial values in a per-wave LDS slice (tt_wave_kernels.h).
 // LDS per wave: 2 rmax + nmax doubles.
 struct TTGeneric {
     int rank[PCX_MAX_DIMS + 1];
@@ -301,27 +302,8 @@ k_tt_eval_generic(TTDims dims, TTGeneric gi, const double *__restrict__ cores,
             const int rl = gi.rank[k], rr = gi.rank[k + 1], n = dims.n[k];
             const double x = pts[p * d + dims.col[k]];
             const double sc = 2.0 * (x - dims.lo[k]) / (dims.hi[k] - dims.lo[k]) - 1.0;   // tensor_train.py:2254
-            if (lane == 0) {                  // T_0 .. T_{n-1} by the forward recurrence
-                double tp = 1.0, tc = sc;
-                for (int j = 0; j < n; ++j) {
-                    q[j] = tp;
-                    const double tn = __builtin_fma(2.0 * sc, tc, -tp);
-                    tp = tc;
-                    tc = tn;
-                }
-            }
-            // wave-private LDS: operations of one wave execute in order, no barrier needed
-            const double *G = cores + gi.coff[k];
-            for (int b = lane; b < rr; b += 64) {
-                double s = 0.0;
-                for (int a = 0; a < rl; ++a) {
-                    const double *ga = G + ((long)a * n) * rr + b;
-                    double w = 0.0;
-                    for (int j = 0; j < n; ++j) w = __builtin_fma(q[j], ga[(long)j * rr], w);
-                    s = __builtin_fma(va[a], w, s);
-                }
-                vb[b] = s;
-            }
+            if (lane == 0) tt_wave_basis(sc, n, q);
+            tt_wave_left(cores + gi.coff[k], rl, n, rr, q, va, vb, lane);
             double *t = va; va = vb; vb = t;
         }
         if (lane == 0) out[p] = va[0];

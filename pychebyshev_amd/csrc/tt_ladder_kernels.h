@@ -20,6 +20,7 @@
 #pragma once
 
 #include "tt_lpp_kernels.h"
+#include "tt_wave_kernels.h"
 
 struct TTLadder {
     int d, p;                     // dimensions; storage position of the ladder's dimension
@@ -27,15 +28,6 @@ struct TTLadder {
     int rmax;
     int fcol[PCX_MAX_DIMS];       // column of `fixed` read by storage position k (unused at p)
 };
-
-template <int NJ>
-__device__ __forceinline__ void tt_ladder_basis(double x, double (&T)[NJ]) {
-    const double x2 = x + x;
-    T[0] = 1.0;
-    if constexpr (NJ > 1) T[1] = x;
-#pragma unroll
-    for (int j = 2; j < NJ; ++j) T[j] = __builtin_fma(x2, T[j - 1], -T[j - 2]);
-}
 
 // sum_j T_j G[j]: one core fibre (a, :, b) of the image
 template <int NJ>
@@ -50,7 +42,7 @@ __device__ __forceinline__ double tt_ladder_fold(pcx_lpp_cptr G, const double (&
 template <int NJ>
 __device__ __forceinline__ void tt_ladder_left(pcx_lpp_cptr G, int rl, int rr, double x, const double *vin, double *vout) {
     double T[NJ];
-    tt_ladder_basis<NJ>(x, T);
+    tt_lpp_basis<NJ, false>(x, T);
     for (int b = 0; b < rr; ++b) {
         double s = 0.0;
         for (int a = 0; a < rl; ++a, G += NJ) s = __builtin_fma(vin[a * PCX_LPP_WG], tt_ladder_fold<NJ>(G, T), s);
@@ -62,7 +54,7 @@ __device__ __forceinline__ void tt_ladder_left(pcx_lpp_cptr G, int rl, int rr, d
 template <int NJ>
 __device__ __forceinline__ void tt_ladder_right(pcx_lpp_cptr G, int rl, int rr, double x, const double *rin, double *rout) {
     double T[NJ];
-    tt_ladder_basis<NJ>(x, T);
+    tt_lpp_basis<NJ, false>(x, T);
     for (int a = 0; a < rl; ++a) {
         double s = 0.0;
         for (int b = 0; b < rr; ++b) s = __builtin_fma(tt_ladder_fold<NJ>(G + (b * rl + a) * NJ, T), rin[b * PCX_LPP_WG], s);
@@ -87,20 +79,13 @@ __device__ __forceinline__ void tt_ladder_core(pcx_lpp_cptr G, int rl, int rr, c
     }
     for (int xi = 0; xi < m; ++xi) {
         double T[NJ];
-        tt_ladder_basis<NJ>(__builtin_fma(xs[xi] - lo, sc, -1.0), T);
+        tt_lpp_basis<NJ, false>(__builtin_fma(xs[xi] - lo, sc, -1.0), T);
         double s = c[0] * T[0];
 #pragma unroll
         for (int i = 1; i < NJ; ++i) s = __builtin_fma(c[i], T[i], s);
         if (y) y[xi] = s;
     }
 }
-
-#define PCX_TT_LADDER_N_CASES(CALL)                                                                             \
-    case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break;             \
-    case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break; case 8: CALL(8); break;             \
-    case 9: CALL(9); break; case 10: CALL(10); break; case 11: CALL(11); break; case 12: CALL(12); break;       \
-    case 13: CALL(13); break; case 14: CALL(14); break; case 15: CALL(15); break; case 16: CALL(16); break;     \
-    default: break;
 
 // One wave per workgroup, one row per lane; dynamic LDS = 3 * max rank * 64 * 8 bytes: the right chain alternates
 // between two lane-private columns, the left chain between the one it leaves free and a third.  Lanes past N work on
@@ -123,9 +108,7 @@ k_tt_ladder_lpp(const TTLppDim *__restrict__ tab, TTLadder lp, const double *__r
         const double x = __builtin_fma(row[lp.fcol[k]] - ct[k].lo, ct[k].scale, -1.0);
         const pcx_lpp_cptr G = cimg + ct[k].off;
         const int rl = ct[k].rl, rr = ct[k].rr;
-#define PCX_CALL(NJ) tt_ladder_right<NJ>(G, rl, rr, x, rin, rout)
-        switch (ct[k].n) { PCX_TT_LADDER_N_CASES(PCX_CALL) }
-#undef PCX_CALL
+        tt_lpp_for_nodes(ct[k].n, [&](auto nj) { tt_ladder_right<decltype(nj)::value>(G, rl, rr, x, rin, rout); });
         double *t = rin; rin = rout; rout = t;
     }
     double *lin = rout;
@@ -134,9 +117,7 @@ k_tt_ladder_lpp(const TTLppDim *__restrict__ tab, TTLadder lp, const double *__r
         const double x = __builtin_fma(row[lp.fcol[k]] - ct[k].lo, ct[k].scale, -1.0);
         const pcx_lpp_cptr G = cimg + ct[k].off;
         const int rl = ct[k].rl, rr = ct[k].rr;
-#define PCX_CALL(NJ) tt_ladder_left<NJ>(G, rl, rr, x, lin, lout)
-        switch (ct[k].n) { PCX_TT_LADDER_N_CASES(PCX_CALL) }
-#undef PCX_CALL
+        tt_lpp_for_nodes(ct[k].n, [&](auto nj) { tt_ladder_left<decltype(nj)::value>(G, rl, rr, x, lin, lout); });
         double *t = lin; lin = lout; lout = t;
     }
     {
@@ -146,39 +127,16 @@ k_tt_ladder_lpp(const TTLppDim *__restrict__ tab, TTLadder lp, const double *__r
         const double lo = ct[k].lo, sc = ct[k].scale;
         const double *xr = xs + pc * xstride;
         double *y = p < N ? out + p * lp.m : nullptr;
-#define PCX_CALL(NJ) tt_ladder_core<NJ>(G, rl, rr, lin, rin, lo, sc, xr, lp.m, y)
-        switch (ct[k].n) { PCX_TT_LADDER_N_CASES(PCX_CALL) }
-#undef PCX_CALL
+        tt_lpp_for_nodes(ct[k].n, [&](auto nj) { tt_ladder_core<decltype(nj)::value>(G, rl, rr, lin, rin, lo, sc, xr, lp.m, y); });
     }
 }
 
-// Every other model (rank > 16 or n > 16): one wave per row on the plain cores G_k[a][j][b] (as k_tt_box_generic).
+// Every other model (rank > 16 or n > 16): one wave per row on the plain cores G_k[a][j][b] (tt_wave_kernels.h).
 // Per wave in LDS: three rank vectors (the chains, as above), the basis q and the coefficients c
 // (3 rmax + 2 nmax doubles).  Lane 0 forms a dimension's basis; the lanes share the right rank (left chain), the left
-// rank (right chain), the coefficients and at last the m values.  Wave-private LDS: the operations of one wave execute
-// in order, no barrier is needed.
-struct TTLadderGeneric {
-    int rank[PCX_MAX_DIMS + 1];
-    int n[PCX_MAX_DIMS];
-    long coff[PCX_MAX_DIMS];
-    double lo[PCX_MAX_DIMS];
-    double scale[PCX_MAX_DIMS];
-    int nmax;
-};
-
-__device__ __forceinline__ void tt_ladder_basis_lds(double s, int n, double *q) {
-    double tp = 1.0, tc = s;
-    const double x2 = s + s;
-    for (int j = 0; j < n; ++j) {
-        q[j] = tp;
-        const double tn = __builtin_fma(x2, tc, -tp);
-        tp = tc;
-        tc = tn;
-    }
-}
-
+// rank (right chain), the coefficients and at last the m values.
 __global__ void __launch_bounds__(256)
-k_tt_ladder_generic(TTLadderGeneric gi, TTLadder lp, const double *__restrict__ cores, const double *__restrict__ fixed,
+k_tt_ladder_generic(TTWaveModel gi, TTLadder lp, const double *__restrict__ cores, const double *__restrict__ fixed,
                     long fstride, const double *__restrict__ xs, long xstride, double *__restrict__ out, long N) {
     extern __shared__ double lds_ladg[];
     const int lane = threadIdx.x & 63;
@@ -192,7 +150,7 @@ k_tt_ladder_generic(TTLadderGeneric gi, TTLadder lp, const double *__restrict__ 
         if (lane == 0) rin[0] = 1.0;
         for (int k = lp.d - 1; k > lp.p; --k) {
             const int rl = gi.rank[k], rr = gi.rank[k + 1], n = gi.n[k];
-            if (lane == 0) tt_ladder_basis_lds(__builtin_fma(row[lp.fcol[k]] - gi.lo[k], gi.scale[k], -1.0), n, q);
+            if (lane == 0) tt_wave_basis(__builtin_fma(row[lp.fcol[k]] - gi.lo[k], gi.scale[k], -1.0), n, q);
             const double *G = cores + gi.coff[k];
             for (int a = lane; a < rl; a += 64) {
                 double s = 0.0;
@@ -210,18 +168,8 @@ k_tt_ladder_generic(TTLadderGeneric gi, TTLadder lp, const double *__restrict__ 
         if (lane == 0) lin[0] = 1.0;
         for (int k = 0; k < lp.p; ++k) {
             const int rl = gi.rank[k], rr = gi.rank[k + 1], n = gi.n[k];
-            if (lane == 0) tt_ladder_basis_lds(__builtin_fma(row[lp.fcol[k]] - gi.lo[k], gi.scale[k], -1.0), n, q);
-            const double *G = cores + gi.coff[k];
-            for (int b = lane; b < rr; b += 64) {
-                double s = 0.0;
-                for (int a = 0; a < rl; ++a) {
-                    const double *ga = G + ((long)a * n) * rr + b;
-                    double w = 0.0;
-                    for (int j = 0; j < n; ++j) w = __builtin_fma(q[j], ga[(long)j * rr], w);
-                    s = __builtin_fma(lin[a], w, s);
-                }
-                lout[b] = s;
-            }
+            if (lane == 0) tt_wave_basis(__builtin_fma(row[lp.fcol[k]] - gi.lo[k], gi.scale[k], -1.0), n, q);
+            tt_wave_left(cores + gi.coff[k], rl, n, rr, q, lin, lout, lane);
             double *t = lin; lin = lout; lout = t;
         }
         const int k = lp.p;

@@ -23,6 +23,8 @@
 // peak depending on the clock the box settles at (round 2, k_tt_eval_d4: 0.555).
 #pragma once
 
+#include <type_traits>
+
 #include "pcx_common.h"
 
 typedef const double __attribute__((address_space(4))) *pcx_lpp_cptr;
@@ -47,25 +49,86 @@ struct TTLppDim {
 #define PCX_LPP_MINB12 6      // ranks 9..12 at <= 80 VGPRs: at 8 (<= 64 VGPRs) the rank-12 body spills (10-D rank 12: 0.55 against 0.65)
 #endif
 
-template <int RL, int NJ>
-__device__ __forceinline__ void tt_lpp_body(pcx_lpp_cptr G, int rr, double x, double *vl) {
-    double T[NJ], v[RL];
-    const double x2 = x + x;
-    T[0] = 1.0;
-    asm volatile("" : "+v"(T[0]));          // T_0 in a register: M = g * T_0 is one v_mul_f64, not two v_mov_b32
-    if constexpr (NJ > 1) T[1] = x;
+// ---- the chain step every lane-per-row family shares (eval, fd, box, deriv, ladder) ------------------------------------
+// The sixteen left ranks and node counts a lane-per-row body exists for: the one list behind the rank switch, the
+// node-count switch and the launchers' choice of an instantiation.
+#define PCX_LPP_1_8(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
+#define PCX_LPP_9_12(X) X(9) X(10) X(11) X(12)
+#define PCX_LPP_13_16(X) X(13) X(14) X(15) X(16)
+#define PCX_LPP_CASE(V) case V: f(std::integral_constant<int, V>{}); break;
+
+// f(integral_constant<rl>): ranks 1 .. 8 first, the rest only in the instantiations that cover them
+template <int RCAP, class F>
+__device__ __forceinline__ void tt_lpp_for_rank(int rl, F &&f) {
+    switch (rl) {
+        PCX_LPP_1_8(PCX_LPP_CASE)
+        default:
+            if constexpr (RCAP > 12) {
+                switch (rl) { PCX_LPP_9_12(PCX_LPP_CASE) PCX_LPP_13_16(PCX_LPP_CASE) default: break; }
+            } else if constexpr (RCAP > 8) {
+                switch (rl) { PCX_LPP_9_12(PCX_LPP_CASE) default: break; }
+            }
+            break;
+    }
+}
+
+// f(integral_constant<n>) for n = 1 .. 16; false, and no call, for any other n
+template <class F>
+__host__ __device__ __forceinline__ bool tt_lpp_for_nodes(int n, F &&f) {
+    switch (n) { PCX_LPP_1_8(PCX_LPP_CASE) PCX_LPP_9_12(PCX_LPP_CASE) PCX_LPP_13_16(PCX_LPP_CASE) default: return false; }
+    return true;
+}
+
+// The launchers' choice of a kernel<RCAP, NJ>: launch(integral_constant<RCAP>, integral_constant<NJ>) with RCAP = the
+// model's rank cap (8, 12, else 16) and NJ = its node count where every dimension has the same one, else 0.
+template <class F>
+inline void tt_lpp_for_model(int cap, int nodes, F &&launch) {
+    auto with_cap = [&](auto rcap) {
+        if (!tt_lpp_for_nodes(nodes, [&](auto nj) { launch(rcap, nj); })) launch(rcap, std::integral_constant<int, 0>{});
+    };
+    if (cap == 8) with_cap(std::integral_constant<int, 8>{});
+    else if (cap == 12) with_cap(std::integral_constant<int, 12>{});
+    else with_cap(std::integral_constant<int, 16>{});
+}
+
+// The value basis in registers, q_j = T_j(x): T_0 = 1, T_1 = x, T_j = fma(2 x, T_{j-1}, -T_{j-2}).  PIN: T_0 is held in
+// a register, so that M = g * T_0 in tt_lpp_contract is one v_mul_f64, not two v_mov_b32 (the ladder folds T_0 = 1 away
+// instead).  The statements are a macro because tt_lpp_contract needs them in its own body: called there as
+// tt_lpp_basis they are the same operations, but hipcc then allocates k_tt_eval_lpp<8, NJ> differently (with the basis
+// array handed to a second function, 68 bytes of scratch for NJ = 15 where there were none, 76 for 12 at NJ = 0).
+#define PCX_LPP_BASIS(NJ, PIN, x, q)                                                                       \
+    const double x2 = (x) + (x);                                                                              \
+    (q)[0] = 1.0;                                                                                             \
+    if constexpr (PIN) asm volatile("" : "+v"((q)[0]));                                                       \
+    if constexpr (NJ > 1) (q)[1] = (x);                                                                       \
+    _Pragma("unroll") for (int j = 2; j < NJ; ++j) (q)[j] = __builtin_fma(x2, (q)[j - 1], -(q)[j - 2]);
+template <int NJ, bool PIN = true>
+__device__ __forceinline__ void tt_lpp_basis(double x, double (&q)[NJ]) {
+    PCX_LPP_BASIS(NJ, PIN, x, q)
+}
+
+// The body of one left rank: v'[b] = sum_a v[a] sum_j q_j G[a][j][b] for b < rr, through the lane's LDS column vl.
+// xq is the dimension's basis q[NJ] (box, deriv: formed once, before the rank switch) or its mapped coordinate, a double
+// (eval, fd: the value basis is formed here, inside the body).
+template <int RL, int NJ, class Q>
+__device__ __forceinline__ void tt_lpp_contract(pcx_lpp_cptr G, int rr, const Q &xq, double *vl) {
+    double q[NJ], v[RL];
+    if constexpr (std::is_same<Q, double>::value) {
+        PCX_LPP_BASIS(NJ, true, xq, q)
+    } else {
 #pragma unroll
-    for (int j = 2; j < NJ; ++j) T[j] = __builtin_fma(x2, T[j - 1], -T[j - 2]);
+        for (int j = 0; j < NJ; ++j) q[j] = xq[j];
+    }
 #pragma unroll
     for (int a = 0; a < RL; ++a) v[a] = vl[a * PCX_LPP_WG];      // dimension 0 reads the 1.0 the kernel put there
     for (int b = 0; b < rr; ++b, G += RL * NJ) {
         double M[RL];
 #pragma unroll
-        for (int a = 0; a < RL; ++a) M[a] = G[a * NJ] * T[0];
+        for (int a = 0; a < RL; ++a) M[a] = G[a * NJ] * q[0];
 #pragma unroll
         for (int j = 1; j < NJ; ++j)
 #pragma unroll
-            for (int a = 0; a < RL; ++a) M[a] = __builtin_fma(T[j], G[a * NJ + j], M[a]);
+            for (int a = 0; a < RL; ++a) M[a] = __builtin_fma(q[j], G[a * NJ + j], M[a]);
         double s;
         if constexpr (RL < 4) {
             s = v[0] * M[0];
@@ -84,30 +147,10 @@ __device__ __forceinline__ void tt_lpp_body(pcx_lpp_cptr G, int rr, double x, do
     }
 }
 
-#define PCX_LPP_RANK_CASES_8(NJ)                                                                          \
-    case 1: tt_lpp_body<1, NJ>(G, rr, x, vl); break; case 2: tt_lpp_body<2, NJ>(G, rr, x, vl); break;     \
-    case 3: tt_lpp_body<3, NJ>(G, rr, x, vl); break; case 4: tt_lpp_body<4, NJ>(G, rr, x, vl); break;     \
-    case 5: tt_lpp_body<5, NJ>(G, rr, x, vl); break; case 6: tt_lpp_body<6, NJ>(G, rr, x, vl); break;     \
-    case 7: tt_lpp_body<7, NJ>(G, rr, x, vl); break; case 8: tt_lpp_body<8, NJ>(G, rr, x, vl); break;
-#define PCX_LPP_RANK_CASES_12(NJ)                                                                         \
-    case 9: tt_lpp_body<9, NJ>(G, rr, x, vl); break; case 10: tt_lpp_body<10, NJ>(G, rr, x, vl); break;   \
-    case 11: tt_lpp_body<11, NJ>(G, rr, x, vl); break; case 12: tt_lpp_body<12, NJ>(G, rr, x, vl); break;
-#define PCX_LPP_RANK_CASES_16(NJ)                                                                         \
-    case 13: tt_lpp_body<13, NJ>(G, rr, x, vl); break; case 14: tt_lpp_body<14, NJ>(G, rr, x, vl); break; \
-    case 15: tt_lpp_body<15, NJ>(G, rr, x, vl); break; case 16: tt_lpp_body<16, NJ>(G, rr, x, vl); break;
-
+// one dimension of the value chain
 template <int RCAP, int NJ>
 __device__ __forceinline__ void tt_lpp_dim(int rl, pcx_lpp_cptr G, int rr, double x, double *vl) {
-    switch (rl) {
-        PCX_LPP_RANK_CASES_8(NJ)
-        default:
-            if constexpr (RCAP > 12) {
-                switch (rl) { PCX_LPP_RANK_CASES_12(NJ) PCX_LPP_RANK_CASES_16(NJ) default: break; }
-            } else if constexpr (RCAP > 8) {
-                switch (rl) { PCX_LPP_RANK_CASES_12(NJ) default: break; }
-            }
-            break;
-    }
+    tt_lpp_for_rank<RCAP>(rl, [&](auto r) { tt_lpp_contract<decltype(r)::value, NJ>(G, rr, x, vl); });
 }
 
 // One wave per workgroup, one point per lane; dynamic LDS = max rank * 64 * 8 bytes (the lane-private
@@ -142,25 +185,7 @@ k_tt_eval_lpp(const TTLppDim *__restrict__ tab, int d, const double *__restrict_
         if constexpr (NJ > 0) {
             tt_lpp_dim<RCAP, NJ>(rl, G, rr, x, vl);
         } else {
-            switch (ct[k].n) {
-            case 1: tt_lpp_dim<RCAP, 1>(rl, G, rr, x, vl); break;
-            case 2: tt_lpp_dim<RCAP, 2>(rl, G, rr, x, vl); break;
-            case 3: tt_lpp_dim<RCAP, 3>(rl, G, rr, x, vl); break;
-            case 4: tt_lpp_dim<RCAP, 4>(rl, G, rr, x, vl); break;
-            case 5: tt_lpp_dim<RCAP, 5>(rl, G, rr, x, vl); break;
-            case 6: tt_lpp_dim<RCAP, 6>(rl, G, rr, x, vl); break;
-            case 7: tt_lpp_dim<RCAP, 7>(rl, G, rr, x, vl); break;
-            case 8: tt_lpp_dim<RCAP, 8>(rl, G, rr, x, vl); break;
-            case 9: tt_lpp_dim<RCAP, 9>(rl, G, rr, x, vl); break;
-            case 10: tt_lpp_dim<RCAP, 10>(rl, G, rr, x, vl); break;
-            case 11: tt_lpp_dim<RCAP, 11>(rl, G, rr, x, vl); break;
-            case 12: tt_lpp_dim<RCAP, 12>(rl, G, rr, x, vl); break;
-            case 13: tt_lpp_dim<RCAP, 13>(rl, G, rr, x, vl); break;
-            case 14: tt_lpp_dim<RCAP, 14>(rl, G, rr, x, vl); break;
-            case 15: tt_lpp_dim<RCAP, 15>(rl, G, rr, x, vl); break;
-            case 16: tt_lpp_dim<RCAP, 16>(rl, G, rr, x, vl); break;
-            default: break;
-            }
+            tt_lpp_for_nodes(ct[k].n, [&](auto nj) { tt_lpp_dim<RCAP, decltype(nj)::value>(rl, G, rr, x, vl); });
         }
     }
 #ifdef PCX_LPP_LAB_WRAP
