@@ -468,6 +468,17 @@ int pcx_tt_ladder_batch_dev(pcx_tt *h, int dim, const double *d_fixed, int64_t N
 int pcx_tt_deriv_batch(pcx_tt *h, const double *pts, int64_t N, const int32_t *derivs, int m, double *out);
 int pcx_tt_deriv_batch_dev(pcx_tt *h, const double *d_pts, int64_t N, const int32_t *derivs, int m, double *d_out,
                            void *stream);
+/* Value, gradient and Hessian diagonal, batched, in one forward-backward pass per point: out is N x C row-major with
+ * C = 1 + d (second = 0) or 1 + 2 d (second = 1); column 0 is the value, column 1 + u the first and column 1 + d + u the
+ * second partial derivative along dimension u of the USER's dimension order.  One right sweep keeps every right partial
+ * product, one left sweep folds each core with T_j, T'_j and T''_j from the same core loads: about four (second = 0:
+ * three) chains' work whatever d is, against d + 1 / 2 d + 1 chains of pcx_tt_deriv_batch, and as exact.  A dimension
+ * with one node has both derivatives exactly 0, one with two nodes second derivative exactly 0.  second outside {0, 1},
+ * N < 0 or a NULL buffer with N > 0 is PCX_ERR_INVALID before any launch; N = 0 returns PCX_OK without one.  Staging,
+ * the two kernel forms and PCX_ERR_UNSUPPORTED (a wave-per-row model beyond the LDS of a workgroup) as
+ * pcx_tt_deriv_batch[_dev]. */
+int pcx_tt_grad_batch(pcx_tt *h, const double *pts, int64_t N, int second, double *out);
+int pcx_tt_grad_batch_dev(pcx_tt *h, const double *d_pts, int64_t N, int second, double *d_out, void *stream);
 /* Kernel selection: 0 = auto, 1 = direct form on v_mfma_f64_16x16x4 (one GEMM over (node, left
  * rank) per dimension; ranks <= 64), 2 = small-rank "W first" form (ranks <= 12, cores in LDS),
  * 3 = small-rank direct form on v_mfma_f64_4x4x4_4b (ranks <= 12, n <= 16, cores in LDS),

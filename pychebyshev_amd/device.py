@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["DeviceArray", "as_device_array", "is_device_array", "trim_pool"]
+__all__ = ["DeviceArray", "DeviceColumns", "as_device_array", "is_device_array", "trim_pool"]
 
 # Result arrays of the device-resident methods come from a small size-keyed pool: hipMalloc + hipFree of a 32 MB result
 # cost more than the kernel that fills it (finite-difference Greeks at 10^6 points: 1.8 ms per call, 0.83 ms of it the
@@ -50,7 +50,8 @@ def trim_pool() -> None:
 
 class DeviceArray:
     """A float64 C-contiguous array in HBM, allocated through ``pcx_dev_malloc`` (owned: freed
-    with the object) or borrowed from another library (``owner`` keeps that object alive)."""
+    with the object) or borrowed from another library (``owner`` keeps that object alive).  The subclass
+    :class:`DeviceColumns` alone is a strided view of such an array."""
 
     def __init__(self, ptr: int, shape: Tuple[int, ...], device: int, *, owns: bool, owner=None):
         self.ptr = int(ptr)
@@ -142,6 +143,50 @@ class DeviceArray:
         return f"DeviceArray(shape={self.shape}, device={self.device}, {'owned' if self._owns else 'borrowed'})"
 
 
+class DeviceColumns(DeviceArray):
+    """Columns ``[c0, c1)`` of a two-dimensional :class:`DeviceArray` (``squeeze``: the one column ``c0`` as a vector):
+    a strided view of the parent's memory, which it keeps alive.  It carries its strides in
+    ``__cuda_array_interface__`` (so ``torch.as_tensor`` and CuPy see the view, not a copy) and comes to the host as a
+    contiguous NumPy array; the calls of this package that take device arrays want C-contiguous ones and say so
+    (``as_device_array`` refuses a strided view).  It is the one ``DeviceArray`` that is not C-contiguous: ``shape``,
+    ``size`` and ``nbytes`` count the view's own elements, as NumPy's do for a view, not a block of memory.
+    ``to_host()`` downloads the WHOLE parent and slices it on the host (the library has no strided copy): for all the
+    parts of one result, download the parent once (``view.parent.to_host()``) and slice that.  Views are made from a
+    parent only: ``empty`` and ``from_host`` are not available here."""
+
+    @classmethod
+    def empty(cls, shape, device=None):
+        raise TypeError("DeviceColumns is a view of a DeviceArray: allocate with DeviceArray.empty")
+
+    @classmethod
+    def from_host(cls, array, device=None):
+        raise TypeError("DeviceColumns is a view of a DeviceArray: upload with DeviceArray.from_host")
+
+    @property
+    def parent(self) -> DeviceArray:
+        return self._owner
+
+    def __init__(self, parent: DeviceArray, c0: int, c1: int, *, squeeze: bool = False):
+        if parent.ndim != 2 or not 0 <= c0 <= c1 <= parent.shape[1] or (squeeze and c1 != c0 + 1):
+            raise ValueError(f"columns [{c0}, {c1}) of an array of shape {parent.shape}")
+        n, width = parent.shape
+        super().__init__(parent.ptr + 8 * c0 if parent.ptr else 0, (n,) if squeeze else (n, c1 - c0), parent.device,
+                         owns=False, owner=parent)
+        self.strides = (8 * width,) if squeeze else (8 * width, 8)
+        self._cols = (c0, c1, squeeze)
+
+    def to_host(self) -> np.ndarray:
+        c0, c1, squeeze = self._cols
+        host = self._owner.to_host()
+        return np.ascontiguousarray(host[:, c0] if squeeze else host[:, c0:c1])
+
+    @property
+    def __cuda_array_interface__(self) -> dict:
+        if not self.ptr:
+            raise ValueError("DeviceArray was freed")
+        return {"shape": self.shape, "typestr": "<f8", "data": (self.ptr, False), "version": 3, "strides": self.strides}
+
+
 def is_device_array(obj) -> bool:
     return isinstance(obj, DeviceArray) or (not isinstance(obj, np.ndarray) and hasattr(obj, "__cuda_array_interface__"))
 
@@ -164,6 +209,8 @@ def as_device_array(obj) -> Optional[DeviceArray]:
     if isinstance(obj, DeviceArray):
         if not obj.ptr and obj.size:
             raise ValueError("DeviceArray was freed")
+        if isinstance(obj, DeviceColumns) and not _c_contiguous(obj.shape, obj.strides):
+            raise ValueError("device arrays must be C-contiguous")
         return obj
     if isinstance(obj, np.ndarray) or not hasattr(obj, "__cuda_array_interface__"):
         return None

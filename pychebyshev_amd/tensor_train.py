@@ -32,7 +32,9 @@ integrated dimensions (``pcx_tt_box_batch``, ``csrc/tt_box_kernels.h``).
 of the reference's finite differences (the default, unchanged): the same chain with ``T_j``, ``T'_j`` or ``T''_j`` as the
 basis of a differentiated dimension, one launch for all rows and specs (``pcx_tt_deriv_batch``,
 ``csrc/tt_deriv_kernels.h``).  ``differentiate`` returns the derivative as a model: the coefficient-derivative
-recurrence on the host cores.
+recurrence on the host cores.  ``gradient_batch`` / ``gradient`` give the value, every first partial derivative and,
+on request, every dimension's own second derivative from one forward-backward pass per row (``pcx_tt_grad_batch``,
+``csrc/tt_grad_kernels.h``) instead of one chain per spec.
 
 ``orth_left`` / ``orth_right`` run their Householder QR sweep on the device (``pcx_tt_orth``).  ``run_completion`` --
 fixed-rank alternating least squares against the values on the whole grid -- runs all its outer iterations in one
@@ -861,6 +863,72 @@ class ChebyshevTT(ErgonomicsMixin, FibreCalculusMixin):
         if pts.shape[0]:
             _lib.check(host_entry(t.handle, _lib.p_f64(pts), pts.shape[0], _lib.p_i32(block), m, _lib.p_f64(out)), t.lib)
         return out
+
+    def gradient_batch(self, points, *, second: bool = False, out=None):
+        """Value and every first partial derivative of the interpolant at ``(N, d)`` points, exact as
+        ``eval_multi_batch(..., method="analytic")`` (extension): ``(values (N,), grad (N, d))``, and with
+        ``second=True`` ``(values, grad, diag (N, d))``, ``diag[:, u]`` the second derivative along dimension ``u``
+        (the Hessian's diagonal).  Columns are the user's dimensions.
+
+        One forward-backward pass per row (``pcx_tt_grad_batch``, ``csrc/tt_grad_kernels.h``): a right sweep keeps every
+        partial product ``R_k``, a left sweep folds each core with ``T_j``, ``T'_j`` and ``T''_j`` from the same core
+        loads -- three chains' worth of folds for value and gradient (one for the right sweep, two for the left), four
+        with the diagonal, whatever ``d`` is, where the analytic ``eval_multi_batch`` walks one chain per (row, spec):
+        ``d + 1`` / ``2 d + 1`` of them.
+
+        The returns are views of one ``(N, C)`` result, ``C = 1 + d`` or ``1 + 2 d``: column 0 the value, ``1 + u`` the
+        gradient, ``1 + d + u`` the diagonal.  Host points give NumPy arrays; a device array in gives device arrays out
+        (strided :class:`~pychebyshev_amd.device.DeviceColumns` of one :class:`~pychebyshev_amd.device.DeviceArray`,
+        complete on return; ``to_host()`` of a view downloads the whole result, so for all parts on the host download
+        ``view.parent`` once and slice it).  ``out=`` is that ``(N, C)`` result preallocated, a C-contiguous float64 NumPy array or
+        a device array; the views are then of ``out``."""
+        self._check_built()
+        from .device import DeviceArray, DeviceColumns, as_device_array, check_points, is_device_array
+        d = self.num_dimensions
+        second = bool(second)
+        C = 1 + (2 if second else 1) * d
+        t = self._dev()
+        if is_device_array(points):
+            dev_pts, pts = as_device_array(points), None
+            n = check_points(dev_pts, d, t.device)
+        else:
+            pts = _lib.f64(np.asarray(points, dtype=float))
+            if pts.ndim != 2 or pts.shape[1] != d:
+                raise ValueError(f"points must have shape (N, {d}), got {pts.shape}")
+            dev_pts, n = None, pts.shape[0]
+        host_out, dev_out = _calculus.validate_ladder_out(out, (n, C))
+        if dev_out is not None and dev_out.size and dev_out.device != t.device:
+            raise ValueError(f"out lives on device {dev_out.device} but the model is on device {t.device}; "
+                             f"call to_device({dev_out.device}) on the model first")
+        if dev_pts is None and dev_out is None:
+            res = np.empty((n, C)) if host_out is None else host_out
+            if n:
+                _lib.check(t.lib.pcx_tt_grad_batch(t.handle, _lib.p_f64(pts), n, int(second), _lib.p_f64(res)), t.lib)
+        else:
+            res = DeviceArray.empty((n, C), t.device) if dev_out is None else dev_out
+            if n:
+                d_pts = dev_pts if dev_pts is not None else DeviceArray.from_host(pts, t.device)
+                st = ctypes.c_void_p()
+                _lib.check(t.lib.pcx_tt_stream(t.handle, ctypes.byref(st)), t.lib)
+                _lib.check(t.lib.pcx_tt_grad_batch_dev(t.handle, ctypes.c_void_p(d_pts.ptr), n, int(second),
+                                                       ctypes.c_void_p(res.ptr), st), t.lib)
+                _lib.check(t.lib.pcx_stream_synchronize(st), t.lib)
+            if host_out is not None:              # device points, host out=
+                if n:
+                    host_out[...] = res.to_host()
+                res = host_out
+        if isinstance(res, np.ndarray):
+            parts = (res[:, 0], res[:, 1:1 + d]) + ((res[:, 1 + d:],) if second else ())
+        else:
+            parts = (DeviceColumns(res, 0, 1, squeeze=True), DeviceColumns(res, 1, 1 + d)) \
+                + ((DeviceColumns(res, 1 + d, C),) if second else ())
+        return parts
+
+    def gradient(self, point, *, second: bool = False):
+        """Value and gradient at one point, ``(float, (d,) array)``, and with ``second=True`` the second derivatives
+        along each dimension as a third ``(d,)`` array: row 0 of a one-row :meth:`gradient_batch`."""
+        parts = self.gradient_batch(np.asarray([list(point)], dtype=float), second=second)
+        return (float(parts[0][0]),) + tuple(np.array(p[0]) for p in parts[1:])
 
     def _eval_multi_batch_host(self, points, derivative_orders, *, chunk: int = 1 << 18) -> np.ndarray:
         """The finite-difference rules on NumPy columns -- the same record / replay traversal as :meth:`eval_multi`
