@@ -20,6 +20,7 @@ LIB = os.path.join(HERE, "libpcx_hip.so")
 PCX_H = os.path.join("..", "..", "include", "pcx.h")
 HOST_H = ["pcx_common.h", "pcx_internal.h", PCX_H]
 BARY_H = HOST_H + ["pcx_bary_internal.h", "bary_plan.h"]
+TT_H = HOST_H + ["tt_plan.h"]
 SOURCES = {
     "pcx_core.hip": HOST_H,
     "pcx_bary_plan.hip": HOST_H + ["bary_plan.h"],
@@ -38,11 +39,12 @@ SOURCES = {
     "pcx_piecewise_ladder.hip": BARY_H + ["pcx_slider_internal.h", "pcx_spline_internal.h", "gather_kernels.h",
                                  "bary_kernels.h", "bary_ladder_kernels.h", "piecewise_ladder_kernels.h"],
     "pcx_slider_box.hip": BARY_H + ["pcx_slider_internal.h", "gather_kernels.h", "slider_calc_kernels.h"],
-    "pcx_tt.hip": HOST_H + ["tt_kernels.h", "tt_wave_kernels.h", "tt_lpp_kernels.h", "tt_fd_kernels.h"],
-    "pcx_tt_box.hip": HOST_H + ["tt_lpp_kernels.h", "tt_wave_kernels.h", "tt_box_kernels.h"],
-    "pcx_tt_deriv.hip": HOST_H + ["tt_lpp_kernels.h", "tt_wave_kernels.h", "tt_deriv_kernels.h"],
-    "pcx_tt_grad.hip": HOST_H + ["tt_lpp_kernels.h", "tt_wave_kernels.h", "tt_grad_kernels.h"],
-    "pcx_tt_ladder.hip": HOST_H + ["tt_lpp_kernels.h", "tt_wave_kernels.h", "tt_ladder_kernels.h"],
+    "pcx_tt_plan.hip": HOST_H + ["tt_plan.h"],
+    "pcx_tt.hip": TT_H + ["tt_kernels.h", "tt_wave_kernels.h", "tt_lpp_kernels.h", "tt_fd_kernels.h"],
+    "pcx_tt_box.hip": TT_H + ["tt_lpp_kernels.h", "tt_wave_kernels.h", "tt_box_kernels.h"],
+    "pcx_tt_deriv.hip": TT_H + ["tt_lpp_kernels.h", "tt_wave_kernels.h", "tt_deriv_kernels.h"],
+    "pcx_tt_grad.hip": TT_H + ["tt_lpp_kernels.h", "tt_wave_kernels.h", "tt_grad_kernels.h"],
+    "pcx_tt_ladder.hip": TT_H + ["tt_lpp_kernels.h", "tt_wave_kernels.h", "tt_ladder_kernels.h"],
     "pcx_ttbuild.hip": HOST_H + ["ttcross_kernels.h", "ttsvd_kernels.h", "tt_round_kernels.h"],
     "pcx_tt_als.hip": HOST_H + ["tt_als_kernels.h"],
     "pcx_calculus.hip": BARY_H + ["pcx_slider_internal.h", "pcx_spline_internal.h", "gather_kernels.h",

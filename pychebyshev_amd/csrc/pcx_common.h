@@ -130,3 +130,47 @@ struct TTDims {
     double scale[PCX_MAX_DIMS];   // 2 / (hi - lo): s = fma(x - lo, scale, -1) without a division per point
     long frag_off[PCX_MAX_DIMS];  // offset (doubles) of storage dim k in the packed cores
 };
+
+// direct form on the 16x16x4 MFMA (tt_kernels.h, k_tt_eval_mfma)
+struct TTRanks {
+    int rc[PCX_MAX_DIMS];  // left-rank chunks of 4 stored per storage dim (1 for dim 0, RC after)
+    int rt[PCX_MAX_DIMS];  // right-rank tiles of 16 stored per storage dim (RT)
+};
+
+// generic wave-per-point form (tt_kernels.h, k_tt_eval_generic)
+struct TTGeneric {
+    int rank[PCX_MAX_DIMS + 1];
+    long coff[PCX_MAX_DIMS];
+    int rmax, nmax;
+};
+
+// small-rank "W first" form (tt_kernels.h, k_tt_eval_wfirst)
+struct TTWPlan {
+    int ntiles[PCX_MAX_DIMS];   // row tiles stored: ceil(R/16) for dim 0 (left rank 1), R*R/16 after
+    int lds_off[PCX_MAX_DIMS];  // offset (doubles) of dim k's block inside the LDS image
+    int ks;                     // k-steps of 4 every dimension is padded to (= the kernel's KS)
+    int total;                  // doubles in the LDS image
+};
+
+// small-rank direct form on the 4x4x4 MFMA (tt_kernels.h, k_tt_eval_d4)
+struct TTD4Plan {
+    int lds_off[PCX_MAX_DIMS];  // offset (doubles) of dim k's block inside the LDS image
+    int total;                  // doubles in the LDS image
+};
+
+#define PCX_D4_MAX_NODES 16
+
+// lane-per-point form (tt_lpp_kernels.h): one entry per storage dimension, read with scalar loads
+struct TTLppDim {
+    int off;        // offset (doubles) of storage dim k in the image
+    int rl, rr;     // left / right rank
+    int n;          // nodes
+    int col;        // user column read by storage position k (dim_order)
+    int pad_;
+    double lo;
+    double scale;   // 2 / (hi - lo): s = fma(x - lo, scale, -1)
+};
+
+#define PCX_LPP_MAX_RANK 16
+#define PCX_LPP_MAX_NODES 16
+#define PCX_LPP_WG 64

@@ -449,19 +449,16 @@ static int fan_out_host(int n_handles, int device0, int pin, int64_t N, const vo
 // and its stream)
 PCX_HIDDEN int tt_handle_view(pcx_tt *h, int *device, TTDims *dims, hipStream_t *stream);
 
-// pcx_tt.hip: what pcx_tt_box.hip reads of a tensor-train handle -- the shape, the lane-per-point image and table when
-// the model has them (lppCap != 0), else the plain cores, and the mutex and staging buffers its entry points share with
-// pcx_tt_eval_batch.  The pointers live as long as the handle.
+// pcx_tt.hip: what pcx_tt_box.hip, _deriv, _grad and _ladder read of a tensor-train handle -- its plan (tt_plan.h), the
+// lane-per-point image and table when the handle holds them (d_lpp_img != NULL), else the plain cores, and the mutex and
+// staging buffers their entry points share with pcx_tt_eval_batch.  The pointers live as long as the handle.
+struct TTPlan;
 struct TTBoxView {
     int device;
     hipStream_t stream;
-    const TTDims *dims;
-    const int *ranks;            // d + 1
-    const long *coff;            // offset (doubles) of storage dim k in the plain cores
-    int rmax, nmax;
-    int lppCap, lpp_nodes;
+    const TTPlan *plan;
     const double *d_lpp_img;
-    const void *d_lpp_tab;       // TTLppDim[d]
+    const TTLppDim *d_lpp_tab;   // [d]
     const double *d_cores;
     double **d_rinv;             // the handle's table of 1 / j (NULL until the wave-per-row box kernel first runs); freed with the handle
     std::mutex *mu;

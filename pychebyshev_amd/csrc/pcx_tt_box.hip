@@ -5,7 +5,7 @@
 
 // integrated: d flags by USER dimension.  The row offsets follow the user's order; the kernels walk storage positions.
 static int tt_box_plan(const TTBoxView &v, const int32_t *integrated, TTBoxCols *cols) {
-    const TTDims &dims = *v.dims;
+    const TTDims &dims = v.plan->dims;
     const int d = dims.d;
     int user_off[PCX_MAX_DIMS];
     int width = 0;
@@ -30,13 +30,13 @@ static int tt_box_plan(const TTBoxView &v, const int32_t *integrated, TTBoxCols 
 static int tt_box_launch(const TTBoxView &v, const TTBoxCols &cols, const double *d_rows, long N, double *d_out,
                          hipStream_t st) {
     if (N == 0) return PCX_OK;
-    const int d = v.dims->d;
-    if (v.lppCap) {
+    const int d = v.plan->dims.d;
+    if (v.d_lpp_img) {
         const long blocks = (N + PCX_LPP_WG - 1) / PCX_LPP_WG;
         if (blocks > 0x7fffffffL) return fail(PCX_ERR_UNSUPPORTED, "batch too large for one launch");
-        const size_t lds = (size_t)v.rmax * PCX_LPP_WG * sizeof(double);
-        const TTLppDim *tab = (const TTLppDim *)v.d_lpp_tab;
-        tt_lpp_for_model(v.lppCap, v.lpp_nodes, [&](auto rcap, auto nj) {
+        const size_t lds = (size_t)v.plan->rmax * PCX_LPP_WG * sizeof(double);
+        const TTLppDim *tab = v.d_lpp_tab;
+        tt_lpp_for_model(v.plan->lppCap, v.plan->lpp_nodes, [&](auto rcap, auto nj) {
             hipLaunchKernelGGL((k_tt_box_lpp<decltype(rcap)::value, decltype(nj)::value>), dim3((unsigned)blocks), dim3(PCX_LPP_WG),
                                lds, st, tab, d, cols, v.d_lpp_img, d_rows, d_out, N);
         });
@@ -56,7 +56,7 @@ static int tt_box_launch(const TTBoxView &v, const TTBoxCols &cols, const double
         *v.d_rinv = p;
     }
     size_t lds;
-    const int rc = tt_wave_lds((const void *)k_tt_box_generic, v, 2 * (size_t)v.rmax + v.nmax, "box", "2 rank + nodes", &lds);
+    const int rc = tt_wave_lds((const void *)k_tt_box_generic, v, 2 * (size_t)v.plan->rmax + v.plan->nmax, "box", "2 rank + nodes", &lds);
     if (rc) return rc;
     const long blocks = std::min<long>((N + 3) / 4, 256L * 8);
     hipLaunchKernelGGL(k_tt_box_generic, dim3((unsigned)blocks), dim3(256), lds, st, gi, cols, v.d_cores, *v.d_rinv, d_rows, d_out, N);

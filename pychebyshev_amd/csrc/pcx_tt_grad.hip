@@ -20,7 +20,7 @@ static int tt_grad_launch_lpp(const TTBoxView &v, size_t lds, long blocks, const
         HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         lifted.fetch_or(bit, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(PCX_LPP_WG), lds, st, (const TTLppDim *)v.d_lpp_tab, v.dims->d,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(PCX_LPP_WG), lds, st, v.d_lpp_tab, v.plan->dims.d,
                        v.d_lpp_img, d_pts, d_out, N);
     HIP_TRY(hipGetLastError());
     return PCX_OK;
@@ -29,14 +29,14 @@ static int tt_grad_launch_lpp(const TTBoxView &v, size_t lds, long blocks, const
 // N device-resident points -> d_out[p * C + column]; queued on st, not awaited.  Caller holds the handle's mutex.
 static int tt_grad_launch(const TTBoxView &v, int second, const double *d_pts, long N, double *d_out, hipStream_t st) {
     if (N == 0) return PCX_OK;
-    const int d = v.dims->d;
-    if (v.lppCap) {
+    const int d = v.plan->dims.d;
+    if (v.d_lpp_img) {
         const long blocks = (N + PCX_LPP_WG - 1) / PCX_LPP_WG;
         if (blocks > 0x7fffffffL) return fail(PCX_ERR_UNSUPPORTED, "batch too large for one launch");
         // a lane-per-point image has d <= 16 and ranks <= 16: 128 KiB at most, inside the 160 KiB of a workgroup
-        const size_t lds = tt_grad_lpp_columns(v.ranks, d, v.rmax) * PCX_LPP_WG * sizeof(double);
+        const size_t lds = tt_grad_lpp_columns(v.plan->ranks, d, v.plan->rmax) * PCX_LPP_WG * sizeof(double);
         int rc = PCX_OK;
-        tt_lpp_for_model(v.lppCap, v.lpp_nodes, [&](auto rcap, auto nj) {
+        tt_lpp_for_model(v.plan->lppCap, v.plan->lpp_nodes, [&](auto rcap, auto nj) {
             constexpr int RCAP = decltype(rcap)::value, NJ = decltype(nj)::value;
             rc = second ? tt_grad_launch_lpp<RCAP, NJ, true>(v, lds, blocks, d_pts, N, d_out, st)
                         : tt_grad_launch_lpp<RCAP, NJ, false>(v, lds, blocks, d_pts, N, d_out, st);
@@ -46,8 +46,8 @@ static int tt_grad_launch(const TTBoxView &v, int second, const double *d_pts, l
     if (!v.d_cores) return fail(PCX_ERR_UNSUPPORTED, "the handle holds neither a lane-per-point image nor plain cores");
     TTGradGeneric gd{};
     gd.g = tt_wave_model(v);
-    for (int k = 0; k < d; ++k) gd.col[k] = v.dims->col[k];
-    for (int k = 1; k < d; ++k) gd.rsum += v.ranks[k];
+    for (int k = 0; k < d; ++k) gd.col[k] = v.plan->dims.col[k];
+    for (int k = 1; k < d; ++k) gd.rsum += v.plan->ranks[k];
     const void *kernel = second ? (const void *)k_tt_grad_generic<true> : (const void *)k_tt_grad_generic<false>;
     size_t lds;
     const int rc = tt_wave_lds(kernel, v, tt_grad_generic_doubles(gd), "gradient", "sum of ranks + 2 rank + 3 nodes", &lds);
@@ -93,7 +93,7 @@ extern "C" int pcx_tt_grad_batch(pcx_tt *h, const double *pts, int64_t N, int se
     std::lock_guard<std::mutex> lk(*v.mu);
     // as pcx_tt_deriv_batch: pieces of 2^18 points alternate between the two staging slots (d doubles in, C out per row)
     const int64_t chunk = 1 << 18;
-    const int d = v.dims->d;
+    const int d = v.plan->dims.d;
     return stage_host_batch(*v.stage, v.device, v.stream, pts, N, d, tt_grad_columns(d, second), out,
                             StagePlan{chunk, chunk, N > chunk, true},
                             [&](int, hipStream_t st, const double *dp, long cnt, double *dout) {

@@ -7,12 +7,12 @@
 // dim in the USER's frame (range-checked by ladder_check) -> its storage position and, per storage position, the column
 // of `fixed` it reads
 static int tt_ladder_plan(const TTBoxView &v, int dim, int m, TTLadder *lp) {
-    const TTDims &dims = *v.dims;
+    const TTDims &dims = v.plan->dims;
     const int d = dims.d;
     *lp = TTLadder{};
     lp->d = d;
     lp->m = m;
-    lp->rmax = v.rmax;
+    lp->rmax = v.plan->rmax;
     lp->p = -1;
     for (int k = 0; k < d; ++k) {
         const int u = dims.col[k];
@@ -27,11 +27,11 @@ static int tt_ladder_plan(const TTBoxView &v, int dim, int m, TTLadder *lp) {
 static int tt_ladder_launch(const TTBoxView &v, const TTLadder &lp, const double *d_fixed, long fstride, const double *d_xs,
                             long xstride, long N, double *d_out, hipStream_t st) {
     if (N == 0 || lp.m == 0) return PCX_OK;
-    if (v.lppCap) {
+    if (v.d_lpp_img) {
         const long blocks = (N + PCX_LPP_WG - 1) / PCX_LPP_WG;
         if (blocks > 0x7fffffffL) return fail(PCX_ERR_UNSUPPORTED, "batch too large for one launch");
-        const size_t lds = (size_t)3 * v.rmax * PCX_LPP_WG * sizeof(double);
-        hipLaunchKernelGGL(k_tt_ladder_lpp, dim3((unsigned)blocks), dim3(PCX_LPP_WG), lds, st, (const TTLppDim *)v.d_lpp_tab, lp,
+        const size_t lds = (size_t)3 * v.plan->rmax * PCX_LPP_WG * sizeof(double);
+        hipLaunchKernelGGL(k_tt_ladder_lpp, dim3((unsigned)blocks), dim3(PCX_LPP_WG), lds, st, v.d_lpp_tab, lp,
                            v.d_lpp_img, d_fixed, fstride, d_xs, xstride, d_out, N);
         HIP_TRY(hipGetLastError());
         return PCX_OK;
@@ -39,7 +39,7 @@ static int tt_ladder_launch(const TTBoxView &v, const TTLadder &lp, const double
     if (!v.d_cores) return fail(PCX_ERR_UNSUPPORTED, "the handle holds neither a lane-per-point image nor plain cores");
     const TTWaveModel gi = tt_wave_model(v);
     size_t lds;
-    const int rc = tt_wave_lds((const void *)k_tt_ladder_generic, v, 3 * (size_t)v.rmax + 2 * v.nmax, "ladder", "3 rank + 2 nodes", &lds);
+    const int rc = tt_wave_lds((const void *)k_tt_ladder_generic, v, 3 * (size_t)v.plan->rmax + 2 * v.plan->nmax, "ladder", "3 rank + 2 nodes", &lds);
     if (rc) return rc;
     const long blocks = std::min<long>((N + 3) / 4, 256L * 8);
     hipLaunchKernelGGL(k_tt_ladder_generic, dim3((unsigned)blocks), dim3(256), lds, st, gi, lp, v.d_cores, d_fixed, fstride, d_xs,
@@ -52,7 +52,7 @@ static int tt_ladder_launch(const TTBoxView &v, const TTLadder &lp, const double
 static int tt_ladder_check(pcx_tt *h, TTBoxView *v, int dim, const void *fixed, int64_t N, const void *xs, int m, int xs_per_row,
                            const void *out, TTLadder *lp) {
     int rc = tt_box_view(h, v);
-    if (!rc) rc = ladder_check(h, v->dims->d, dim, nullptr, fixed, N, xs, m, xs_per_row, out);
+    if (!rc) rc = ladder_check(h, v->plan->dims.d, dim, nullptr, fixed, N, xs, m, xs_per_row, out);
     return rc ? rc : tt_ladder_plan(*v, dim, m, lp);
 }
 

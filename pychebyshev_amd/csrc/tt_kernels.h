@@ -139,11 +139,7 @@ __device__ __forceinline__ void tt_mfma_nodes(const double *__restrict__ fk, int
 
 // Packing for the direct form: dim 0 keeps its single left chunk, every later dim is
 // padded to the kernel's compile-time RC chunks and RT tiles (zeros), so the node loop
-// needs no rank predicates:  frag[dim][j][c][t][l] = G[a = 4c + (l>>4)][j][b = 16t + (l&15)].
-struct TTRanks {
-    int rc[PCX_MAX_DIMS];  // left-rank chunks of 4 stored per storage dim (1 for dim 0, RC after)
-    int rt[PCX_MAX_DIMS];  // right-rank tiles of 16 stored per storage dim (RT)
-};
+// needs no rank predicates:  frag[dim][j][c][t][l] = G[a = 4c + (l>>4)][j][b = 16t + (l&15)]   (TTRanks, pcx_common.h).
 
 // One wave owns 16*NT points; v (lane group g holds rows a = 4c + g) runs through the
 // dimensions in registers.  The last dimension (right rank 1) is a VALU dot product against
@@ -279,13 +275,7 @@ k_tt_eval_mfma(TTDims dims, TTRanks rk, const double *__restrict__ frag,
 // Ranks above 64 (outside the MFMA tilings): one wavefront walks one point at a time through
 // the chain with the cores in their natural (r, n, r') layout -- lanes over the right rank b
 // (coalesced core reads from L2), v and the polynomial values in a per-wave LDS slice (tt_wave_kernels.h).
-// LDS per wave: 2 rmax + nmax doubles.
-struct TTGeneric {
-    int rank[PCX_MAX_DIMS + 1];
-    long coff[PCX_MAX_DIMS];
-    int rmax, nmax;
-};
-
+// LDS per wave: 2 rmax + nmax doubles (TTGeneric, pcx_common.h).
 __global__ void __launch_bounds__(256)
 k_tt_eval_generic(TTDims dims, TTGeneric gi, const double *__restrict__ cores,
                   const double *__restrict__ pts, double *__restrict__ out, long N) {
@@ -325,14 +315,7 @@ k_tt_eval_generic(TTDims dims, TTGeneric gi, const double *__restrict__ cores,
 // Every dimension is zero-padded to the kernel's compile-time KS k-steps, so the whole
 // batch body is straight-line code.
 // =====================================================================================
-struct TTWPlan {
-    int ntiles[PCX_MAX_DIMS];   // row tiles stored: ceil(R/16) for dim 0 (left rank 1), R*R/16 after
-    int lds_off[PCX_MAX_DIMS];  // offset (doubles) of dim k's block inside the LDS image
-    int ks;                     // k-steps of 4 every dimension is padded to (= the kernel's KS)
-    int total;                  // doubles in the LDS image
-};
-
-// image layout: for k < d-1: frag[k][s][t][64] = G_k[a][4s + (l>>4)][b], m = 16t + (l&15),
+// image layout (TTWPlan, pcx_common.h): for k < d-1: frag[k][s][t][64] = G_k[a][4s + (l>>4)][b], m = 16t + (l&15),
 // a = m / R, b = m % R (zero outside the core); last dim: table [a < R][j < 4 ks], zero padded.
 template <int R>
 __global__ void k_tt_pack_wfirst(const double *__restrict__ G, double *__restrict__ img, int rl,
@@ -591,13 +574,6 @@ template <> struct D4Frag<3> {
     static constexpr int NMP = 4;
     __device__ __forceinline__ void load(const double *p) { const pcx_d2 t = *(const pcx_d2 *)p; v[0] = t.x; v[1] = t.y; v[2] = p[2]; }
 };
-
-struct TTD4Plan {
-    int lds_off[PCX_MAX_DIMS];  // offset (doubles) of dim k's block inside the LDS image
-    int total;                  // doubles in the LDS image
-};
-
-#define PCX_D4_MAX_NODES 16
 
 template <int RA, int NJ>
 __device__ __forceinline__ void tt_d4_mid(const double *fk, double x, double (&v)[RA]) {

@@ -29,19 +29,7 @@
 
 typedef const double __attribute__((address_space(4))) *pcx_lpp_cptr;
 
-struct TTLppDim {
-    int off;        // offset (doubles) of storage dim k in the image
-    int rl, rr;     // left / right rank
-    int n;          // nodes
-    int col;        // user column read by storage position k (dim_order)
-    int pad_;
-    double lo;
-    double scale;   // 2 / (hi - lo): s = fma(x - lo, scale, -1)
-};
-
-#define PCX_LPP_MAX_RANK 16
-#define PCX_LPP_MAX_NODES 16
-#define PCX_LPP_WG 64
+// TTLppDim, PCX_LPP_MAX_RANK, PCX_LPP_MAX_NODES and PCX_LPP_WG: pcx_common.h
 #ifndef PCX_LPP_MINB8
 #define PCX_LPP_MINB8 8       // ranks <= 8
 #endif

@@ -8,6 +8,7 @@
 #pragma once
 
 #include "pcx_internal.h"
+#include "tt_plan.h"
 
 struct TTWaveModel {
     int d;
@@ -49,18 +50,19 @@ __device__ __forceinline__ void tt_wave_left(const double *G, int rl, int n, int
 // ---- host side ----------------------------------------------------------------------------------------------------
 static inline TTWaveModel tt_wave_model(const TTBoxView &v) {
     TTWaveModel gi{};
-    const int d = v.dims->d;
+    const TTPlan &p = *v.plan;
+    const int d = p.dims.d;
     gi.d = d;
-    gi.rmax = v.rmax;
-    gi.nmax = v.nmax;
+    gi.rmax = p.rmax;
+    gi.nmax = p.nmax;
     for (int k = 0; k < d; ++k) {
-        gi.rank[k] = v.ranks[k];
-        gi.n[k] = v.dims->n[k];
-        gi.coff[k] = v.coff[k];
-        gi.lo[k] = v.dims->lo[k];
-        gi.scale[k] = v.dims->scale[k];
+        gi.rank[k] = p.ranks[k];
+        gi.n[k] = p.dims.n[k];
+        gi.coff[k] = p.coff[k];
+        gi.lo[k] = p.dims.lo[k];
+        gi.scale[k] = p.dims.scale[k];
     }
-    gi.rank[d] = v.ranks[d];
+    gi.rank[d] = p.ranks[d];
     return gi;
 }
 
@@ -71,7 +73,7 @@ static inline int tt_wave_lds(const void *kernel, const TTBoxView &v, size_t per
     *lds = 4 * per_wave * sizeof(double);
     if (*lds > 160 * 1024)
         return fail(PCX_ERR_UNSUPPORTED, "TT rank %d with %d nodes exceeds the generic %s kernel's LDS budget (%s <= 5120)",
-                    v.rmax, v.nmax, what, budget);
+                    v.plan->rmax, v.plan->nmax, what, budget);
     if (*lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds));
     return PCX_OK;
 }
