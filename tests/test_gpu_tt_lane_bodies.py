@@ -20,45 +20,21 @@ Worst |got - ref| / (eps A_row) measured on MI355X / the restatement's figure / 
            box 0.52 / 0.74 / 16, ladder 0.48 / 0.37 / 8
     edge   eval 1.86 / 1.84 / 32, deriv order 0: 1.86 / 1.84 / 32, order 1: 1.46 / 1.81 / 32, order 2: 2.60 / 3.24 / 64,
            box 2.08 / 2.91 / 64, ladder 2.69 / 2.80 / 64"""
+import functools
+
 import numpy as np
 import pytest
 
 import tt_chain as C
-from pychebyshev_amd import ChebyshevTT, _lib
+from pychebyshev_amd import _lib
+from tt_rows import check, model as _model, set_kernel as _set_kernel
 
 pytestmark = pytest.mark.gpu
 
 SWEEP = C.sweep_models()
 EDGE = C.edge_models()
 WORST = {}
-
-
-def _model(b):
-    return ChebyshevTT.from_coeff_cores(b.cores, b.domain, dim_order=b.order)
-
-
-def _set_kernel(tt, variant):
-    t = tt._dev()
-    _lib.check(t.lib.pcx_tt_set_kernel(t.handle, variant), t.lib)
-
-
-def _check(got, pair, group, kernel, family, what):
-    """One call against the long-double chain: the normwise bar, then every row against its own amplitude."""
-    ref, amp = pair
-    got = np.asarray(got)
-    assert got.shape == ref.shape and got.dtype == np.float64, what
-    err = np.abs(got.astype(C.LD) - ref)
-    scale = float(np.max(np.abs(ref)))
-    r = C.ratios(got, ref, amp)                      # asserts an exact zero where the amplitude is zero
-    worst = float(np.max(r))
-    key = f"{group} {kernel} {family}"
-    WORST[key] = max(WORST.get(key, 0.0), worst)
-    print(f"{what}: E_norm {float(np.max(err)) / scale if scale else 0.0:.2e}, worst row {worst:.3f} eps A_row "
-          f"(K = {C.K[group][family]})")
-    assert float(np.max(err)) <= 1e-12 * scale, f"{what}: E_norm {float(np.max(err)) / scale:.3e}"
-    at = np.unravel_index(int(np.argmax(r)), r.shape)
-    assert worst <= C.K[group][family], \
-        f"{what}: row {at}: |got - ref| = {worst:.3g} eps A_row > K = {C.K[group][family]} (got {got[at]!r}, ref {float(ref[at])!r})"
+_check = functools.partial(check, WORST)      # tests/tt_rows.py: the normwise bar, then every row against its amplitude
 
 
 def _kept(b, dims):

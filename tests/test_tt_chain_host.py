@@ -1,11 +1,13 @@
 """tests/tt_chain.py on the host: the long-double chain against the three golden files that hold such chains already,
-the coverage of the lane-body sweep computed from its model list alone, and the measurement behind every K of the row
-bound in tests/test_gpu_tt_lane_bodies.py.  Host NumPy only: no GPU."""
+the coverage of the lane-body sweep and of the MFMA forms' list computed from the model lists (and tests/tt_plan_rule.py)
+alone, and the measurement behind every K of the row bound in tests/test_gpu_tt_lane_bodies.py and
+tests/test_gpu_tt_mfma_bodies.py.  Host NumPy only: no GPU."""
 import numpy as np
 import pytest
 
 from conftest import assert_parity, golden, spec_point_tol
 import tt_chain as C
+import tt_plan_rule as R
 
 G22 = golden("g22_tt_transforms")
 G28 = golden("g28_tt_derivatives")
@@ -168,16 +170,105 @@ def test_models_rows_and_cases_are_what_the_sweep_says():
     assert tail.cap == 12 and tail.mode == "mixed" and not C.is_uniform(tail) and tail.rows == max(C.TAIL_NS) == 129
 
 
+def test_the_mfma_list_is_what_its_docstring_says():
+    models = C.mfma_models()
+    first = C.tail_model().number + 1
+    assert first == 292 and [m.number for m in models] == list(range(first, first + 220))
+    assert len({m.name for m in models}) == 220 and all(m.rows == 96 for m in models)
+    assert sum(m.number % 3 == 0 for m in models) in (73, 74)              # every third behind a permuted dim_order
+    for c, ranks in enumerate(C.SMALL_CHAINS):
+        top = max(ranks)
+        assert len(ranks) == 5 and 4 * c < top <= 4 * c + 4 and any(r % 4 for r in ranks[1:-1])
+        mine = [m for m in models if m.ranks == ranks and m.mode != "mfma-global"]
+        assert [m.n for m in mine if m.mode == "mfma-uniform"] == [(n,) * 4 for n in range(1, 33)]
+        mixed = [m.n for m in mine if m.mode == "mfma-mixed"]
+        assert [max(n) for n in mixed] == list(range(2, 33)) and all(n.count(max(n)) == 1 for n in mixed)
+        where = [n.index(max(n)) for n in mixed]
+        assert {0, 3} < set(where) == {0, 1, 2, 3} and all(a != b for a, b in zip(where, where[1:]))
+        for n in mixed:                    # from two k-steps on, a dimension whose last k-step holds zero rows only
+            ks = -(-max(n) // 4)
+            assert ks == 1 or min(n) <= 4 * ks - 4
+    # d = 4 is the largest d whose W-first image fits at R = 12, KS = 8
+    fits = [R.plan(d, [32] * d, [1] + [12] * (d - 1) + [1], [0.0] * d, [1.0] * d, None)["plan"]["wR"] for d in (4, 5)]
+    assert fits == [12, 0]
+    large = [m for m in models if m.ranks in C.LARGE_CHAINS]
+    assert [(max(r), 1 in r[1:-1], 64 in r) for r in C.LARGE_CHAINS] == [(16, False, False), (32, True, False), (64, False, True)]
+    assert {m.ranks[k] % 4 for m in large for k in range(len(m.n))} == {0, 1, 2, 3}              # left ranks
+    assert {1, 15, 16, 17} <= {m.ranks[k + 1] for m in large for k in range(len(m.n))}           # right ranks
+    for ranks in C.LARGE_CHAINS:
+        assert [m.n for m in large if m.ranks == ranks and m.mode == "mfma-uniform"] == [(n,) * (len(ranks) - 1) for n in C.DIRECT_NS]
+    # the last core just past its LDS copy: one node fewer and the planner keeps the copy
+    glob = [m for m in models if m.mode == "mfma-global"]
+    assert [m.ranks for m in glob] == list(C.SMALL_CHAINS + C.LARGE_CHAINS)
+    for m in glob:
+        assert C.plan_of(m)["last_lds_doubles"] == 0 and max(m.n[:-1]) <= 3
+        assert C.plan_of(m._replace(n=m.n[:-1] + (m.n[-1] - 1,)))["last_lds_doubles"] == C.plan_of(m)["last_rows"] * (m.n[-1] - 1)
+    assert [(m.ranks, m.n) for m in models if m.mode == "mfma-lowd"] == list(C.LOWD)
+    assert [(max(r), n) for r, n in C.LOWD] == [(1, (1,)), (1, (7,)), (1, (32,)), (4, (5, 3)), (12, (7, 10)), (16, (6, 5)), (64, (4, 9))]
+    for m in models[:3] + models[-3:] + C.mfma_extra_models():
+        b, again = C.build(m), C.build(m)
+        assert (b.order is not None) == (m.number % 3 == 0) and b.pts.shape == (m.rows, len(m.n))
+        assert b.pts[0].tolist() == [a for a, _ in b.udom] and b.pts[1].tolist() == [hi for _, hi in b.udom]
+        assert np.array_equal(again.pts, b.pts) and all(np.array_equal(x, y) for x, y in zip(again.cores, b.cores))
+
+
+def test_the_mfma_list_reaches_every_body_of_the_three_forms():
+    """Computed from the model list and tests/tt_plan_rule.py's restatement of the planner alone."""
+    models = C.mfma_models()
+    want = C.all_direct_bodies()
+    assert len(want) == 11 + 6 * 2 * 5 + 6 * 2 == 83
+    assert {b[1] for b in want} == {1, 2, 3, 4, 8, 16}
+    assert {b[3] for b in want if b[0] == "nodes" and b[2] == "mid"} == {"ping-pong", "plain"}
+    assert {b[1] for b in want if b[0] == "nodes" and b[3] == "plain"} == {8, 16}
+    assert C.direct_bodies(models) == want
+    want = C.all_wfirst_bodies()
+    assert len(want) == 3 * 8 * 2 == 48
+    assert C.wfirst_bodies(models) == want
+    want = C.all_d4_bodies()
+    assert len(want) == 3 * (4 + 16 + 16) == 108
+    assert C.d4_bodies(models) == want
+    # the bodies are reached on the variant that owns them: which variants a model's plan offers
+    for m in models:
+        small, nmax = max(m.ranks) <= 12, max(m.n)
+        assert C.offered(m) == (1,) + ((2,) if small and nmax <= 32 else ()) + ((3,) if small and nmax <= 16 else ()), m.name
+        p = C.plan_of(m)
+        auto = R.auto_variant(p, 0)
+        assert auto == (4 if max(m.ranks) <= 15 and nmax <= 16 else 3 if 3 in C.offered(m) else 2 if 2 in C.offered(m) else 1), m.name
+    # every W-first instantiation of 5 .. 8 k-steps, the range where auto takes the form, runs on auto too
+    assert {(C.plan_of(m)["wR"], C.plan_of(m)["wplan.ks"]) for m in models if R.auto_variant(C.plan_of(m), 0) == 2} \
+        == {(r, ks) for r in (4, 8, 12) for ks in range(5, 9)}
+
+
+def test_the_tail_and_persistent_models_run_the_kernels_their_tests_name():
+    tails = C.mfma_tail_models()
+    assert [(C.plan_of(m)["cls"], C.plan_of(m)["wR"], v) for m, v in tails] == [(0, 0, 1), (1, 0, 1), (2, 0, 1), (0, 4, 2), (0, 12, 2), (0, 8, 3)]
+    assert all(m.rows == 300 > max(C.MFMA_TAIL_NS) and v in C.offered(m) for m, v in tails)
+    assert tails[0][0].number == C.mfma_models()[-1].number + 1
+    (wide, v0, p0), (w12, v1, p1), (d4, v2, p2) = C.persistent_models()
+    assert (v0, p0, C.plan_of(wide)["wR"]) == (2, 256, 4) and (v1, p1, C.plan_of(w12)["wR"]) == (2, 64, 12) and (v2, p2) == (3, 64)
+    assert C.plan_of(d4)["d4RA"] == 3 and wide.number == tails[-1][0].number + 1
+    # residency by LDS alone, and the host array of 3 x 4 x resident x CUs batches on a device of 256 CUs
+    assert [C.CU_LDS_BYTES // C.launch_lds(m, v) for m, v, _ in C.persistent_models()] == [1, 1, 2]
+    for m, v, per in C.persistent_models():
+        assert (3 * 4 * (C.CU_LDS_BYTES // C.launch_lds(m, v)) * 256 * per + 777) * len(m.n) * 8 < 100e6
+    assert C.launch_lds(wide._replace(ranks=wide.ranks[:-2] + (1,), n=wide.n[:-1]), 2) <= C.CU_LDS_BYTES // 2     # d = 11: two resident
+
+
 # ------------------------------------------------------------------------------------------------ the tolerance
 def test_the_restatement_sets_every_K():
     """The float64 restatement against the long-double chain on every case of every model, per list and family: the
     worst |y - ref| / (eps A_row) is the figure tt_chain.RESTATEMENT_WORST records (the arithmetic is a fixed sequence
-    of elementwise operations: the same bits everywhere), and K is 16 times it, rounded up to a power of two, <= 64."""
-    worst = {group: dict.fromkeys(C.FAMILIES, 0.0) for group in C.K}
+    of elementwise operations: the same bits everywhere), and K is 16 times it, rounded up to a power of two, <= 64.
+    The MFMA forms' lists are lists of eval_batch: their value rows alone."""
+    worst = {group: dict.fromkeys(fam, 0.0) for group, fam in C.K.items()}
     for m in C.sweep_models() + C.edge_models() + (C.tail_model(),):
         for family, r in C.restatement_ratios(C.build(m)).items():
             w = worst[C.group_of(m)]
             w[family] = max(w[family], r)
+    for m in C.mfma_models() + C.mfma_extra_models():
+        w = worst[C.group_of(m)]
+        w["value"] = max(w["value"], C.restatement_value_ratio(C.build(m)))
+    assert set(worst["mfma"]) == set(worst["mfma-lowd"]) == {"value"}
     for group, fam in worst.items():
         print(group, {f: round(r, 4) for f, r in fam.items()}, "K", C.K[group])
         for family, r in fam.items():

@@ -1,7 +1,10 @@
-"""Shared by the tensor-train lane-body tests: the TT chain  v <- v . (sum_j q_j G_k[:, j, :])  in ``np.longdouble`` with
+"""Shared by the tensor-train body tests: the TT chain  v <- v . (sum_j q_j G_k[:, j, :])  in ``np.longdouble`` with
 the four bases the device kernels use, the amplitude of every row, the same chain restated in float64, and the seeded
-model list of the sweep (tests/test_tt_chain_host.py inspects it, tests/test_gpu_tt_lane_bodies.py runs it).  Plain
-NumPy, no GPU, nothing from the reference checkout.
+model lists: the sweep of the lane-per-row kernels (tests/test_gpu_tt_lane_bodies.py runs it) and mfma_models(), the
+list of the three MFMA forms of eval_batch (tests/test_gpu_tt_mfma_bodies.py; 220 models that reach 83 + 48 + 108
+bodies of the 16x16x4, W-first and 4x4x4 forms; worst rows on MI355X 1.72 eps A_row against the restatement's 1.21,
+K = 32, and 0.61 against 0.63, K = 16, for d <= 2).  tests/test_tt_chain_host.py inspects both lists.  Plain NumPy, no
+GPU, nothing from the reference checkout.
 
 Frames: ``cores`` and ``domain`` are indexed by STORAGE position k; ``dim_order[k]`` is the user dimension stored there;
 rows (``pts``), specs, ``dims``, ``bounds`` and ``xs`` are in the USER's frame, as the public calls take them.
@@ -30,6 +33,8 @@ import collections
 import functools
 
 import numpy as np
+
+import tt_plan_rule as plan_rule
 
 LD = np.longdouble
 # a platform whose long double is float64 would compare double with double: refuse to import
@@ -131,6 +136,20 @@ class Chain:
 
     def value(self):
         return self._run([self.fold(k, 0) for k in range(self.d)])
+
+    def value_s(self):
+        """The value with the amplitude  A_row + sum_k A_k:  A_k is the chain on |G| with |T_j'(s_k)| in place of
+        |T_j(s_k)| at storage position k -- the first-order size of the row's change under an absolute error of one eps
+        in s_k (see RESTATEMENT_WORST on why A_row alone cannot see it)."""
+        val, amp = self.value()
+        one = np.ones((self.pts.shape[0], 1), dtype=self.dt)
+        for k in range(self.d):
+            q1 = np.abs(deriv_basis(self.s(k, self.pts[:, self.order[k]]), self.n[k], 1, self.dt(1)))
+            a = one
+            for i in range(self.d):
+                a = _step(a, _fold(self.absG[k], q1) if i == k else self.fold(i, 0)[1])
+            amp = amp + a[:, 0]
+        return val, amp
 
     def deriv(self, spec):
         """spec: an order 0, 1 or 2 per USER dimension."""
@@ -263,6 +282,201 @@ def all_lane_bodies():
     return {(cap, uni, rl, n) for cap in CAPS for uni in (True, False) for rl in range(1, cap + 1) for n in range(1, MAX_N + 1)}
 
 
+# ---------------------------------------------------------------------------------------------- the MFMA forms' models
+# The list of tests/test_gpu_tt_mfma_bodies.py: the 16x16x4 direct form (variant 1), the W-first form (2) and the 4x4x4
+# form (3) of ChebyshevTT.eval_batch.  Which body a model runs is read off tests/tt_plan_rule.py's restatement of the
+# planner, so tests/test_tt_chain_host.py proves the coverage below without a GPU.
+SMALL_CHAINS = ((1, 2, 4, 3, 1), (1, 5, 8, 7, 1), (1, 9, 12, 11, 1))        # largest rank in (0, 4], (4, 8], (8, 12]; d = 4
+LARGE_CHAINS = ((1, 14, 16, 15, 1), (1, 17, 1, 32, 21, 1), (1, 33, 64, 50, 1))   # 13 .. 16; 17 .. 32, a rank-1 bond inside; 33 .. 64
+DIRECT_NS = (1, 2, 3, 4, 5, 8)     # the ping-pong loop: no pair, one pair, pair + peel, two pairs, two + peel, four pairs
+DIRECT_RCS = (1, 2, 3, 4, 8, 16)   # k_tt_eval_mfma<RC, RT, NT>: <1|2|3|4, 1, 4>, <8, 2, 2>, <16, 4, 1>
+W_MAX_N = 32
+D4_MAX_N = 16
+LOWD = (((1, 1), (1,)), ((1, 1), (7,)), ((1, 1), (32,)),
+        ((1, 4, 1), (5, 3)), ((1, 12, 1), (7, 10)), ((1, 16, 1), (6, 5)), ((1, 64, 1), (4, 9)))
+MFMA_TAIL_ROWS = 300
+MFMA_TAIL_NS = (1, 15, 16, 17, 63, 64, 65, 127, 128, 129, 255, 256, 257)
+CU_LDS_BYTES = 160 * 1024
+
+
+@functools.lru_cache(maxsize=None)
+def _plan(ranks, n):
+    d = len(n)
+    made = plan_rule.plan(d, list(n), list(ranks), [0.0] * d, [1.0] * d, None)
+    assert made["rc"] == 0, made
+    return made["plan"]
+
+
+def plan_of(model):
+    """The planner's decisions about a model (tests/tt_plan_rule.py); none of those read here depends on the domain."""
+    return _plan(tuple(model.ranks), tuple(model.n))
+
+
+def offered(model):
+    """The forced variants among (1, 2, 3) the model's plan offers (every image uploaded)."""
+    p = plan_of(model)
+    return tuple(v for v in (1, 2, 3) if plan_rule.auto_variant(p, v) == v)
+
+
+def first_global_last(ranks, head):
+    """The smallest last node count whose padded last core the direct form no longer copies to LDS
+    (last_lds_doubles == 0), behind the node counts ``head``."""
+    return next(n for n in range(1, 4097) if not _plan(tuple(ranks), tuple(head) + (n,))["last_lds_doubles"])
+
+
+def mixed_counts(m):
+    """d = 4 node counts whose largest, m >= 2, stands alone at position m % 4.  The others: 4 KS - 4 (KS = ceil(m / 4);
+    from KS = 2 on, the W-first image of that dimension ends in a whole k-step of zero rows), m - 1 and m // 2, rotated."""
+    ks = -(-m // 4)
+    others = [max(1, 4 * (ks - 1)), m - 1, max(1, m // 2)]
+    turn = (m // 4) % 3
+    others = others[turn:] + others[:turn]
+    return tuple(others[:m % 4] + [m] + others[m % 4:])
+
+
+@functools.lru_cache(maxsize=None)
+def mfma_models():
+    """220 models of ROWS rows, numbered behind tail_model():
+      small chains   SMALL_CHAINS x (every uniform node count 1 .. 32, and mixed_counts(m), m = 2 .. 32: m = 1 leaves no
+                     smaller count for the other dimensions, the uniform n = 1 model is that case)
+      large chains   LARGE_CHAINS x uniform n in DIRECT_NS
+      global last    every chain with small leading node counts and the first last node count that the direct form reads
+                     from global memory instead of its LDS copy
+      low dimension  LOWD: d = 1 with n = 1, 7, 32; d = 2 with largest rank 4, 12, 16, 64"""
+    first = tail_model().number + 1
+    out = []
+
+    def add(name, mode, ranks, n):
+        out.append(Model(first + len(out), name, 0, mode, tuple(ranks), tuple(n), ROWS))
+    for c, ranks in enumerate(SMALL_CHAINS):
+        for n in range(1, W_MAX_N + 1):
+            add(f"small{c}-uniform-n{n}", "mfma-uniform", ranks, (n,) * 4)
+        for m in range(2, W_MAX_N + 1):
+            add(f"small{c}-mixed-max{m}", "mfma-mixed", ranks, mixed_counts(m))
+    for c, ranks in enumerate(LARGE_CHAINS):
+        for n in DIRECT_NS:
+            add(f"large{c}-uniform-n{n}", "mfma-uniform", ranks, (n,) * (len(ranks) - 1))
+    for c, ranks in enumerate(SMALL_CHAINS + LARGE_CHAINS):
+        head = tuple(2 + k % 2 for k in range(len(ranks) - 2))
+        add(f"{'small' if c < 3 else 'large'}{c % 3}-global-last", "mfma-global", ranks, head + (first_global_last(ranks, head),))
+    for ranks, n in LOWD:
+        add(f"lowd-d{len(n)}-r{max(ranks)}-n{'x'.join(map(str, n))}", "mfma-lowd", ranks, n)
+    return tuple(out)
+
+
+def _mfma(name):
+    return next(m for m in mfma_models() if m.name == name)
+
+
+@functools.lru_cache(maxsize=None)
+def mfma_tail_models():
+    """((model of MFMA_TAIL_ROWS rows, forced variant), ...): one per kernel family -- direct NT = 4, 2, 1, W-first
+    NT = 4 (R = 4) and NT = 1 (R = 12), 4x4x4.  Numbered behind mfma_models()."""
+    picks = (("large0-uniform-n5", 1), ("large1-uniform-n5", 1), ("large2-uniform-n3", 1),
+             ("small0-mixed-max19", 2), ("small2-mixed-max22", 2), ("small1-mixed-max13", 3))
+    first = mfma_models()[-1].number + 1
+    return tuple((_mfma(name)._replace(number=first + i, name="tail-" + name, rows=MFMA_TAIL_ROWS), variant)
+                 for i, (name, variant) in enumerate(picks))
+
+
+@functools.lru_cache(maxsize=None)
+def persistent_models():
+    """((model, forced variant, points per batch of a workgroup), ...) for the persistent batch loops of k_tt_eval_wfirst
+    and k_tt_eval_d4.  Launch LDS above half (a third) of a CU's 160 KiB: at most one (two) workgroups resident per CU,
+    so 3 x 4 x resident x CUs batches stay a host array of under 80 MB.  The R = 4 model is the list's only 12-D one: the
+    smallest d at which the NT = 4 launch (image + 6 x 64 d query-row doubles) passes 80 KiB."""
+    wide = Model(mfma_tail_models()[-1][0].number + 1, "persistent-r4-d12", 0, "mfma-mixed",
+                 (1, 2, 4, 3, 4, 1, 3, 4, 2, 4, 3, 2, 1), tuple(32 - k % 4 for k in range(12)), ROWS)
+    return ((wide, 2, 256), (_mfma("small2-uniform-n32"), 2, 64), (_mfma("small2-uniform-n16"), 3, 64))
+
+
+def mfma_extra_models():
+    """The models of the tail and persistent-loop tests that are not in mfma_models() themselves."""
+    return tuple(m for m, _ in mfma_tail_models()) + (persistent_models()[0][0],)
+
+
+def launch_lds(model, variant):
+    """Dynamic LDS bytes of the model's launch on a forced variant (tests/tt_plan_rule.py)."""
+    p = plan_of(model)
+    lds = plan_rule.lds(p)
+    if variant == 3:
+        return lds["d4"]
+    if variant == 2:
+        return lds["wfirst"][1 if p["wR"] == 4 else 0]                # R = 4 runs NT = 4, R = 8 and 12 NT = 1
+    return lds["direct"][(2, 1, 0)[p["cls"]]]                         # NT = 4, 2, 1 by rank class
+
+
+def n_class(n):
+    """How the direct form's two-node loop ends: (pairs, capped at 2; a peeled odd node)."""
+    return min(n // 2, 2), n % 2
+
+
+N_CLASSES = ((0, 1), (1, 0), (1, 1), (2, 0), (2, 1))
+
+
+def direct_bodies(models):
+    """Of k_tt_eval_mfma<RC, RT, NT>, RC naming the instantiation:
+      ("shape", RC, "d1" | "d2" | "d3+")                             the d == 1 branch, no middle dimension, the loop over k
+      ("nodes", RC, "dim0" | "mid", "ping-pong" | "plain", n class)  tt_mfma_nodes<1 | RC, RT, NT>: F = RCX RT <= 8 or not
+      ("last", RC, "lds" | "global")                                 where the last core is read from"""
+    out = set()
+    for m in models:
+        p = plan_of(m)
+        if p["generic"]:
+            continue
+        d, RC, RT = p["d"], p["last_rows"] // 4, p["rk.rt"][0]
+        out.add(("shape", RC, "d1" if d == 1 else "d2" if d == 2 else "d3+"))
+        for k in range(d - 1):
+            out.add(("nodes", RC, "mid" if k else "dim0", "ping-pong" if p["rk.rc"][k] * RT <= 8 else "plain", n_class(m.n[k])))
+        out.add(("last", RC, "lds" if p["last_lds_doubles"] else "global"))
+    return out
+
+
+def all_direct_bodies():
+    """83: the d = 1 model has rank 1 and the d = 2 models largest rank 4, 12, 16, 64; 6 x 2 x 5 node loops; 6 x 2 last cores."""
+    out = {("shape", 1, "d1")} | {("shape", rc, "d2") for rc in (1, 3, 4, 16)} | {("shape", rc, "d3+") for rc in DIRECT_RCS}
+    for rc in DIRECT_RCS:
+        rt = max(1, rc // 4)
+        for cls in N_CLASSES:
+            out.add(("nodes", rc, "dim0", "ping-pong", cls))
+            out.add(("nodes", rc, "mid", "ping-pong" if rc * rt <= 8 else "plain", cls))
+        out |= {("last", rc, "lds"), ("last", rc, "global")}
+    return out
+
+
+def wfirst_bodies(models):
+    """{(R, KS, "spread" | "none")}: the k_tt_eval_wfirst<R, KS, NT> instantiation and its middle dimensions, k < d - 2
+    (v' is spread to every lane) and k = d - 2 (it is not)."""
+    out = set()
+    for m in models:
+        p = plan_of(m)
+        if p["wR"]:
+            out |= {(p["wR"], p["wplan.ks"], "spread" if k < p["d"] - 2 else "none") for k in range(1, p["d"] - 1)}
+    return out
+
+
+def all_wfirst_bodies():
+    return {(R, ks, pos) for R in (4, 8, 12) for ks in range(1, 9) for pos in ("spread", "none")}
+
+
+def d4_bodies(models):
+    """{("ks0", RA, k-steps of dimension 0), ("mid", RA, NJ), ("last", RA, NJ)} of k_tt_eval_d4<RA>."""
+    out = set()
+    for m in models:
+        p = plan_of(m)
+        RA, d = p["d4RA"], p["d"]
+        if RA:
+            if d > 1:
+                out.add(("ks0", RA, -(-m.n[0] // 4)))
+            out |= {("mid", RA, m.n[k]) for k in range(1, d - 1)} | {("last", RA, m.n[-1])}
+    return out
+
+
+def all_d4_bodies():
+    return ({("ks0", RA, s) for RA in (1, 2, 3) for s in range(1, 5)}
+            | {(part, RA, n) for part in ("mid", "last") for RA in (1, 2, 3) for n in range(1, D4_MAX_N + 1)})
+
+
 Built = collections.namedtuple("Built", "model cores domain order udom pts")
 
 
@@ -391,6 +605,18 @@ def restatement_ratios(built):
     return worst
 
 
+def restatement_value_ratio(built):
+    """The worst ratio of the float64 restatement's value chain alone (the MFMA forms' lists: eval_batch only)."""
+    ref = value_pair(Chain(built.cores, built.domain, built.order, built.pts, LD), group_of(built.model))
+    got = Chain(built.cores, built.domain, built.order, built.pts, np.float64).value()
+    return float(np.max(ratios(got[0], ref[0], ref[1])))
+
+
+def value_pair(chain, group):
+    """(values, amplitudes) a group's value rows are held to: "mfma-lowd" counts the one-eps error of s (Chain.value_s)."""
+    return chain.value_s() if group == "mfma-lowd" else chain.value()
+
+
 # Worst |y - ref| / (eps A_row) of the float64 restatement, measured by
 # test_tt_chain_host.py::test_the_restatement_sets_every_K (which asserts these figures), and the row bound's factor K
 # per family: 16 times that, rounded up to a power of two.  The 16 covers what the kernels do differently from the
@@ -404,9 +630,24 @@ def restatement_ratios(built):
 # row as eps |c_1| while A_row holds only |c_1| |s|.  In a 2-D model of rank 1 nothing dilutes it (worst rows: s near 0);
 # in the sweep's 4-D and 6-D models the rank sums' amplitudes do.  The kernels form s by the same rule, so this is the
 # restatement's own error, not slack: stronger decay does not move it (0.55 -> 0.25: 1.8 .. 3.2 -> 2.4 .. 3.4).
+#
+# "mfma": mfma_models() of d >= 3 and mfma_extra_models(), value rows only (the MFMA forms are forms of eval_batch).
+# Higher than the sweep: node counts up to 32 (513 in a last dimension) against 16, and rank sums of up to 64 terms.
+#
+# "mfma-lowd": mfma_models() of d <= 2.  Against A_row alone this list measures 4.02 (K would be 128): the d = 1,
+# n = 32 model has a row at s = 0.95, and towards the ends |T_j'| grows to j^2, so the one-eps error of s described
+# above enters as eps sum_j |c_j T_j'(s)| -- 5.7 times that row's A_row = sum_j |c_j T_j(s)| -- and a 1-D model has
+# nothing to dilute it (its n = 7 model: 1.79).
+# The mechanism is a property of the argument, not of the sum, so this group's amplitude states it: Chain.value_s adds to
+# A_row the chain with |T_j'(s_k)| at position k, for every k -- the row's first-order change under one eps in s_k.  In
+# those units the restatement's worst is 0.63 and K = 16: tighter than K = 128 on A_row for every row away from the
+# ends, and still eps times sums of the row's own terms.  The device forms derive s by x - lo and one FMA, or (W-first)
+# by the reference's division: at most the same one eps.
 RESTATEMENT_WORST = {
     "sweep": {"value": 0.270, "order1": 0.405, "order2": 0.467, "box": 0.735, "ladder": 0.366},
     "edge": {"value": 1.842, "order1": 1.812, "order2": 3.244, "box": 2.908, "ladder": 2.797},
+    "mfma": {"value": 1.208},
+    "mfma-lowd": {"value": 0.628},
 }
 K_CAP = 64
 
@@ -419,4 +660,6 @@ K = {group: {family: K_of(w) for family, w in fam.items()} for group, fam in RES
 
 
 def group_of(model):
+    if model.mode.startswith("mfma"):
+        return "mfma" if len(model.n) >= 3 else "mfma-lowd"
     return "edge" if model.mode == "generic" else "sweep"
