@@ -479,6 +479,26 @@ int pcx_tt_deriv_batch_dev(pcx_tt *h, const double *d_pts, int64_t N, const int3
  * pcx_tt_deriv_batch[_dev]. */
 int pcx_tt_grad_batch(pcx_tt *h, const double *pts, int64_t N, int second, double *out);
 int pcx_tt_grad_batch_dev(pcx_tt *h, const double *d_pts, int64_t N, int second, double *d_out, void *stream);
+/* Value, gradient and the full Hessian, batched: out is N x C row-major with C = 1 + d + d * d; column 0 is the value,
+ * column 1 + u the first partial derivative and column 1 + d + u * d + v the second partial derivative along
+ * dimensions u and v of the USER's dimension order (both triangles are written from the one computed number; u = v is
+ * the diagonal of pcx_tt_grad_batch).  The sweeps of pcx_tt_grad_batch, with the vector D_i = L_i M1_i that its left sweep
+ * forms at storage position i kept and carried to the right beside L: at every later position k two vector-matrix
+ * products with folds the sweep holds anyway give D_i M_k and the mixed partial (D_i M1_k) . R_{k+1}.  A carried vector
+ * takes LDS, so the left sweep runs in passes of `block` sources each (pass 0 is the gradient's sweep; a later pass
+ * repeats the one-basis fold up to its first source): block = 0 takes the planner's choice, 1 .. max(1, d - 1) forces
+ * one, a forced block whose launch does not fit the LDS of a workgroup is PCX_ERR_UNSUPPORTED, any other block
+ * PCX_ERR_INVALID.  A row's bits depend neither on block nor on the batch; the first 1 + d columns and the diagonal are
+ * pcx_tt_grad_batch's, bit for bit.  The Hessian row and column of a one-node dimension and the diagonal entry of a
+ * two-node dimension are exactly 0.  N < 0 or a NULL buffer with N > 0 is PCX_ERR_INVALID; every check comes before any
+ * launch; N = 0 returns PCX_OK without one.  Staging and the two kernel forms as pcx_tt_grad_batch[_dev], the host
+ * entry's pieces shortened by (1 + 2 d) / C.
+ * pcx_tt_hess_info: info_out[0] = the form (1 lane-per-row, 2 wave-per-row), [1] = the planner's block, [2] = the
+ * dynamic LDS bytes of a workgroup at that block, [3] = the largest block that fits (0: none, every call is
+ * PCX_ERR_UNSUPPORTED; [1] is then 0 and [2] the bytes at block 1). */
+int pcx_tt_hess_batch(pcx_tt *h, const double *pts, int64_t N, int block, double *out);
+int pcx_tt_hess_batch_dev(pcx_tt *h, const double *d_pts, int64_t N, int block, double *d_out, void *stream);
+int pcx_tt_hess_info(pcx_tt *h, int32_t *info_out);
 /* Kernel selection: 0 = auto, 1 = direct form on v_mfma_f64_16x16x4 (one GEMM over (node, left
  * rank) per dimension; ranks <= 64), 2 = small-rank "W first" form (ranks <= 12, cores in LDS),
  * 3 = small-rank direct form on v_mfma_f64_4x4x4_4b (ranks <= 12, n <= 16, cores in LDS),

@@ -44,6 +44,7 @@ SOURCES = {
     "pcx_tt_box.hip": TT_H + ["tt_lpp_kernels.h", "tt_wave_kernels.h", "tt_box_kernels.h"],
     "pcx_tt_deriv.hip": TT_H + ["tt_lpp_kernels.h", "tt_wave_kernels.h", "tt_deriv_kernels.h"],
     "pcx_tt_grad.hip": TT_H + ["tt_lpp_kernels.h", "tt_wave_kernels.h", "tt_grad_kernels.h"],
+    "pcx_tt_hess.hip": TT_H + ["tt_lpp_kernels.h", "tt_wave_kernels.h", "tt_grad_kernels.h", "tt_hess_kernels.h"],
     "pcx_tt_ladder.hip": TT_H + ["tt_lpp_kernels.h", "tt_wave_kernels.h", "tt_ladder_kernels.h"],
     "pcx_ttbuild.hip": HOST_H + ["ttcross_kernels.h", "ttsvd_kernels.h", "tt_round_kernels.h"],
     "pcx_tt_als.hip": HOST_H + ["tt_als_kernels.h"],

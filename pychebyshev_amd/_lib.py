@@ -150,6 +150,9 @@ SIGNATURES = {
     "pcx_tt_deriv_batch_dev": (_I, [_V, _V, _L, c_i32p, _I, _V, _V]),
     "pcx_tt_grad_batch": (_I, [_V, c_f64p, _L, _I, c_f64p]),
     "pcx_tt_grad_batch_dev": (_I, [_V, _V, _L, _I, _V, _V]),
+    "pcx_tt_hess_batch": (_I, [_V, c_f64p, _L, _I, c_f64p]),
+    "pcx_tt_hess_batch_dev": (_I, [_V, _V, _L, _I, _V, _V]),
+    "pcx_tt_hess_info": (_I, [_V, c_i32p]),
     "pcx_tt_set_kernel": (_I, [_V, _I]),
     "pcx_tt_cross_step": (_I, [_I, c_f64p, _I, _I, _I, _D, c_f64p, c_i64p, c_i32p]),
     "pcx_maxvol": (_I, [_I, c_f64p, _I, _I, _D, _I, c_i64p]),

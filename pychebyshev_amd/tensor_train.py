@@ -34,7 +34,8 @@ basis of a differentiated dimension, one launch for all rows and specs (``pcx_tt
 ``csrc/tt_deriv_kernels.h``).  ``differentiate`` returns the derivative as a model: the coefficient-derivative
 recurrence on the host cores.  ``gradient_batch`` / ``gradient`` give the value, every first partial derivative and,
 on request, every dimension's own second derivative from one forward-backward pass per row (``pcx_tt_grad_batch``,
-``csrc/tt_grad_kernels.h``) instead of one chain per spec.
+``csrc/tt_grad_kernels.h``) instead of one chain per spec; ``hessian_batch`` / ``hessian`` add every mixed second
+partial from the same sweeps (``pcx_tt_hess_batch``, ``csrc/tt_hess_kernels.h``).
 
 ``orth_left`` / ``orth_right`` run their Householder QR sweep on the device (``pcx_tt_orth``).  ``run_completion`` --
 fixed-rank alternating least squares against the values on the whole grid -- runs all its outer iterations in one
@@ -864,6 +865,45 @@ class ChebyshevTT(ErgonomicsMixin, FibreCalculusMixin):
             _lib.check(host_entry(t.handle, _lib.p_f64(pts), pts.shape[0], _lib.p_i32(block), m, _lib.p_f64(out)), t.lib)
         return out
 
+    def _sweep_batch(self, points, out, C, entry, arg):
+        """The ``(N, C)`` result of ``gradient_batch`` / ``hessian_batch``: the argument checks, then ``entry`` on host
+        points (or ``entry + "_dev"`` when the points or ``out=`` are on the device) with the integer ``arg`` between N
+        and the result.  A NumPy array or a :class:`~pychebyshev_amd.device.DeviceArray`, ``out`` itself when given."""
+        self._check_built()
+        from .device import DeviceArray, as_device_array, check_points, is_device_array
+        d = self.num_dimensions
+        t = self._dev()
+        if is_device_array(points):
+            dev_pts, pts = as_device_array(points), None
+            n = check_points(dev_pts, d, t.device)
+        else:
+            pts = _lib.f64(np.asarray(points, dtype=float))
+            if pts.ndim != 2 or pts.shape[1] != d:
+                raise ValueError(f"points must have shape (N, {d}), got {pts.shape}")
+            dev_pts, n = None, pts.shape[0]
+        host_out, dev_out = _calculus.validate_ladder_out(out, (n, C))
+        if dev_out is not None and dev_out.size and dev_out.device != t.device:
+            raise ValueError(f"out lives on device {dev_out.device} but the model is on device {t.device}; "
+                             f"call to_device({dev_out.device}) on the model first")
+        if dev_pts is None and dev_out is None:
+            res = np.empty((n, C)) if host_out is None else host_out
+            if n:
+                _lib.check(getattr(t.lib, entry)(t.handle, _lib.p_f64(pts), n, arg, _lib.p_f64(res)), t.lib)
+        else:
+            res = DeviceArray.empty((n, C), t.device) if dev_out is None else dev_out
+            if n:
+                d_pts = dev_pts if dev_pts is not None else DeviceArray.from_host(pts, t.device)
+                st = ctypes.c_void_p()
+                _lib.check(t.lib.pcx_tt_stream(t.handle, ctypes.byref(st)), t.lib)
+                _lib.check(getattr(t.lib, entry + "_dev")(t.handle, ctypes.c_void_p(d_pts.ptr), n, arg,
+                                                          ctypes.c_void_p(res.ptr), st), t.lib)
+                _lib.check(t.lib.pcx_stream_synchronize(st), t.lib)
+            if host_out is not None:              # device points, host out=
+                if n:
+                    host_out[...] = res.to_host()
+                res = host_out
+        return res
+
     def gradient_batch(self, points, *, second: bool = False, out=None):
         """Value and every first partial derivative of the interpolant at ``(N, d)`` points, exact as
         ``eval_multi_batch(..., method="analytic")`` (extension): ``(values (N,), grad (N, d))``, and with
@@ -883,40 +923,11 @@ class ChebyshevTT(ErgonomicsMixin, FibreCalculusMixin):
         ``view.parent`` once and slice it).  ``out=`` is that ``(N, C)`` result preallocated, a C-contiguous float64 NumPy array or
         a device array; the views are then of ``out``."""
         self._check_built()
-        from .device import DeviceArray, DeviceColumns, as_device_array, check_points, is_device_array
+        from .device import DeviceColumns
         d = self.num_dimensions
         second = bool(second)
         C = 1 + (2 if second else 1) * d
-        t = self._dev()
-        if is_device_array(points):
-            dev_pts, pts = as_device_array(points), None
-            n = check_points(dev_pts, d, t.device)
-        else:
-            pts = _lib.f64(np.asarray(points, dtype=float))
-            if pts.ndim != 2 or pts.shape[1] != d:
-                raise ValueError(f"points must have shape (N, {d}), got {pts.shape}")
-            dev_pts, n = None, pts.shape[0]
-        host_out, dev_out = _calculus.validate_ladder_out(out, (n, C))
-        if dev_out is not None and dev_out.size and dev_out.device != t.device:
-            raise ValueError(f"out lives on device {dev_out.device} but the model is on device {t.device}; "
-                             f"call to_device({dev_out.device}) on the model first")
-        if dev_pts is None and dev_out is None:
-            res = np.empty((n, C)) if host_out is None else host_out
-            if n:
-                _lib.check(t.lib.pcx_tt_grad_batch(t.handle, _lib.p_f64(pts), n, int(second), _lib.p_f64(res)), t.lib)
-        else:
-            res = DeviceArray.empty((n, C), t.device) if dev_out is None else dev_out
-            if n:
-                d_pts = dev_pts if dev_pts is not None else DeviceArray.from_host(pts, t.device)
-                st = ctypes.c_void_p()
-                _lib.check(t.lib.pcx_tt_stream(t.handle, ctypes.byref(st)), t.lib)
-                _lib.check(t.lib.pcx_tt_grad_batch_dev(t.handle, ctypes.c_void_p(d_pts.ptr), n, int(second),
-                                                       ctypes.c_void_p(res.ptr), st), t.lib)
-                _lib.check(t.lib.pcx_stream_synchronize(st), t.lib)
-            if host_out is not None:              # device points, host out=
-                if n:
-                    host_out[...] = res.to_host()
-                res = host_out
+        res = self._sweep_batch(points, out, C, "pcx_tt_grad_batch", int(second))
         if isinstance(res, np.ndarray):
             parts = (res[:, 0], res[:, 1:1 + d]) + ((res[:, 1 + d:],) if second else ())
         else:
@@ -929,6 +940,40 @@ class ChebyshevTT(ErgonomicsMixin, FibreCalculusMixin):
         along each dimension as a third ``(d,)`` array: row 0 of a one-row :meth:`gradient_batch`."""
         parts = self.gradient_batch(np.asarray([list(point)], dtype=float), second=second)
         return (float(parts[0][0]),) + tuple(np.array(p[0]) for p in parts[1:])
+
+    def hessian_batch(self, points, *, out=None):
+        """Value, gradient and the full Hessian of the interpolant at ``(N, d)`` points, exact as
+        ``eval_multi_batch(..., method="analytic")`` (extension): ``(values (N,), grad (N, d), hess (N, d, d))``,
+        ``hess[:, u, v]`` the second partial derivative along the user's dimensions ``u`` and ``v``; both triangles hold
+        the one computed number.
+
+        The sweeps of :meth:`gradient_batch` (``pcx_tt_hess_batch``, ``csrc/tt_hess_kernels.h``): the vector the left
+        sweep forms for ``grad[:, i]`` is kept and carried to the right beside the left partial product, and at every
+        later position two vector-matrix products with folds the sweep holds anyway give the mixed partial -- where the
+        analytic ``eval_multi_batch`` walks one chain per (row, spec), ``1 + 2 d + d (d - 1) / 2`` of them.  The carried
+        vectors live in LDS, so the left sweep runs in as many passes as the model needs; a row's bits depend neither on
+        that nor on the batch, and the value, the gradient and ``diag(hess)`` are ``gradient_batch(points, second=True)``'s
+        bit for bit.
+
+        The returns are views of one ``(N, C)`` result, ``C = 1 + d + d * d``: column 0 the value, ``1 + u`` the
+        gradient, ``1 + d + u * d + v`` the Hessian.  Host points give NumPy arrays, ``hess = res[:, 1 + d:].reshape(N,
+        d, d)``; a device array in, or a device ``out=``, gives :class:`~pychebyshev_amd.device.DeviceColumns` of one
+        :class:`~pychebyshev_amd.device.DeviceArray`, complete on return, ``hess`` then ``(N, d * d)``, row-major in
+        ``(u, v)``.  ``out=`` is the ``(N, C)`` result preallocated, as in :meth:`gradient_batch`."""
+        self._check_built()
+        from .device import DeviceColumns
+        d = self.num_dimensions
+        C = 1 + d + d * d
+        res = self._sweep_batch(points, out, C, "pcx_tt_hess_batch", 0)      # block = 0: the planner's
+        if isinstance(res, np.ndarray):
+            return res[:, 0], res[:, 1:1 + d], res[:, 1 + d:].reshape(res.shape[0], d, d)
+        return DeviceColumns(res, 0, 1, squeeze=True), DeviceColumns(res, 1, 1 + d), DeviceColumns(res, 1 + d, C)
+
+    def hessian(self, point):
+        """Value, gradient and Hessian at one point, ``(float, (d,) array, (d, d) array)``: row 0 of a one-row
+        :meth:`hessian_batch`."""
+        value, grad, hess = self.hessian_batch(np.asarray([list(point)], dtype=float))
+        return float(value[0]), np.array(grad[0]), np.array(hess[0])
 
     def _eval_multi_batch_host(self, points, derivative_orders, *, chunk: int = 1 << 18) -> np.ndarray:
         """The finite-difference rules on NumPy columns -- the same record / replay traversal as :meth:`eval_multi`
