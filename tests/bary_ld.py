@@ -142,10 +142,16 @@ def _next_to(node, sign):
     return x
 
 
-def _special_rows(rng, nodes, dom, seed):
-    """The fixed kinds of rows inside one box: (rows, position of the grid-point row, its multi-index)."""
+def _special_rows(rng, nodes, dom, seed, head=None):
+    """The fixed kinds of rows inside one box: (rows, position of the grid-point row, its multi-index).  head (the
+    row-code MFMA models of tests/bary_mfma_ld.py): the "outer" dimension of rows 4 and 6 is drawn from the head
+    dimensions [0, head) that have two nodes or more, where there is one; None draws it from all but the last."""
     d = len(nodes)
     shape = [len(x) for x in nodes]
+    pool = [k for k in range(head or 0) if shape[k] >= 2]
+
+    def outer():
+        return pool[int(rng.integers(0, len(pool)))] if pool else int(rng.integers(0, d - 1))
 
     def uniform():
         return [rng.uniform(lo, hi) for lo, hi in dom]
@@ -156,14 +162,14 @@ def _special_rows(rng, nodes, dom, seed):
     r[d - 1] = nodes[d - 1][-1 if seed % 2 else 0]                              # on a node of the register dimension only:
     rows.append(r)                                                              # the prefix / suffix products end there
     if d >= 2:
-        r, k = uniform(), int(rng.integers(0, d - 1))
+        r, k = uniform(), outer()
         r[k] = nodes[k][int(rng.integers(0, shape[k]))]                         # on a node of an outer (LDS) dimension only
         rows.append(r)
     r = uniform()
     r[d - 1] = _next_to(nodes[d - 1][int(rng.integers(0, shape[d - 1]))], 1 if seed % 4 < 2 else -1)
     rows.append(r)                                                              # next to a node, last dimension
     if d >= 2:
-        r, k = uniform(), int(rng.integers(0, d - 1))
+        r, k = uniform(), outer()
         r[k] = _next_to(nodes[k][int(rng.integers(0, shape[k]))], -1 if seed % 4 < 2 else 1)
         rows.append(r)                                                          # next to a node, an outer dimension
     return rows, 2, idx
@@ -177,15 +183,15 @@ class Built(NamedTuple):
     grid_idx: Tuple[int, ...]
 
 
-def build(model):
-    """The single model of a list entry on the host (no device call) and its rows."""
+def build(model, head=None):
+    """The single model of a list entry on the host (no device call) and its rows (head: see _special_rows)."""
     assert model.knots is None
     rng = np.random.default_rng(model.seed)
     d = len(model.shape)
     T = rng.standard_normal(model.shape)
     dom = _domain(rng, d)
     c = ChebyshevApproximation.from_values(T, d, dom, list(model.shape))
-    rows, at, idx = _special_rows(rng, c.nodes, dom, model.seed)
+    rows, at, idx = _special_rows(rng, c.nodes, dom, model.seed, head)
     pts = np.column_stack([rng.uniform(lo, hi, model.rows) for lo, hi in dom])
     pts[:len(rows)] = rows
     return Built(model, c, np.ascontiguousarray(pts), at, idx)
@@ -424,9 +430,10 @@ def K_of(worst):
 K = {family: {order: K_of(w) for order, w in orders.items()} for family, orders in RESTATEMENT_WORST.items()}
 
 
-def check(seen, got, pair, family, order, group, what):
+def check(seen, got, pair, family, order, group, what, k=None):
     """One call against the long-double reference: the normwise bar, then every row against its own amplitude
-    (tests/tt_rows.check for these models).  ``seen`` collects the worst row per (family, order, group)."""
+    (tests/tt_rows.check for these models).  ``seen`` collects the worst row per (family, order, group).  k: the row
+    bound's factor of a family whose K lives elsewhere (tests/bary_mfma_ld.py); None: K[family][order]."""
     ref, amp = pair
     got = np.asarray(got)
     assert got.shape == ref.shape and got.dtype == np.float64, what
@@ -436,7 +443,7 @@ def check(seen, got, pair, family, order, group, what):
     worst = float(np.max(r))
     key = f"{family} {order} {group}"
     seen[key] = max(seen.get(key, 0.0), worst)
-    k = K[family][order]
+    k = K[family][order] if k is None else k
     print(f"{what}: E_norm {float(np.max(err)) / scale if scale else 0.0:.2e}, worst row {worst:.3f} eps A_row (K = {k})")
     assert float(np.max(err)) <= 1e-12 * scale, f"{what}: E_norm {float(np.max(err)) / scale:.3e}"
     at = int(np.argmax(r))

@@ -663,8 +663,9 @@ def test_error_threshold_build_follows_the_reference(tag, f, d, dom, n, thr, max
 
 # ------------------------------------------------------------------ seeded fuzz over shapes
 def test_fuzz_random_tensor_shapes_against_oracle(oracle_mod):
-    """40 seeded random shapes (d 1..10, n 1..13): narrow and wide row codes, every k-step
-    count the planner picks, derivative specs, batch sizes around the tile boundaries."""
+    """40 seeded random shapes (d 1..10, n 1..13) on whatever kernel auto picks for them -- at these sizes mostly a
+    lane-per-point kernel --: narrow and wide row codes, derivative specs, batch sizes around the tile boundaries.
+    The k-step counts of the row-code kernels are covered body by body in test_gpu_bary_mfma_bodies.py."""
     rng = np.random.default_rng(20260102)
     for case in range(40):
         d = int(rng.integers(1, 11))
