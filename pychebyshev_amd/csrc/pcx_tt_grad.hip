@@ -1,8 +1,6 @@
 // pcx_tt_grad.hip -- C ABI of libpcx_hip.so (see include/pcx.h): value, gradient and Hessian diagonal of a tensor
 // train in one forward-backward pass per row, batched.  gfx950 only.
 
-#include <atomic>
-
 #include "pcx_internal.h"
 #include "tt_grad_kernels.h"
 
@@ -12,14 +10,8 @@ template <int RCAP, int NJ, bool SECOND>
 static int tt_grad_launch_lpp(const TTBoxView &v, size_t lds, long blocks, const double *d_pts, long N, double *d_out,
                               hipStream_t st) {
     const auto kernel = k_tt_grad_lpp<RCAP, NJ, SECOND>;
-    // above the 64 KiB default: lifted to the 160 KiB of a workgroup once per instantiation and device (bit = device;
-    // a device index past 63 lifts it at every launch), so that it stays off the launch path of a batch in pieces
     static std::atomic<unsigned long long> lifted{0};
-    const unsigned long long bit = v.device < 64 ? 1ull << v.device : 0;
-    if (lds > 64 * 1024 && !(lifted.load(std::memory_order_relaxed) & bit)) {
-        HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        lifted.fetch_or(bit, std::memory_order_relaxed);
-    }
+    if (const int rc = tt_grad_lift_lds((const void *)kernel, lifted, v.device, lds)) return rc;
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(PCX_LPP_WG), lds, st, v.d_lpp_tab, v.plan->dims.d,
                        v.d_lpp_img, d_pts, d_out, N);
     HIP_TRY(hipGetLastError());
@@ -30,12 +22,14 @@ static int tt_grad_launch_lpp(const TTBoxView &v, size_t lds, long blocks, const
 static int tt_grad_launch(const TTBoxView &v, int second, const double *d_pts, long N, double *d_out, hipStream_t st) {
     if (N == 0) return PCX_OK;
     const int d = v.plan->dims.d;
-    if (v.d_lpp_img) {
-        const long blocks = (N + PCX_LPP_WG - 1) / PCX_LPP_WG;
-        if (blocks > 0x7fffffffL) return fail(PCX_ERR_UNSUPPORTED, "batch too large for one launch");
+    bool lane;
+    int rc = tt_grad_form(v, &lane);
+    if (rc) return rc;
+    if (lane) {
+        long blocks;
+        if ((rc = tt_grad_lpp_blocks(N, &blocks))) return rc;
         // a lane-per-point image has d <= 16 and ranks <= 16: 128 KiB at most, inside the 160 KiB of a workgroup
         const size_t lds = tt_grad_lpp_columns(v.plan->ranks, d, v.plan->rmax) * PCX_LPP_WG * sizeof(double);
-        int rc = PCX_OK;
         tt_lpp_for_model(v.plan->lppCap, v.plan->lpp_nodes, [&](auto rcap, auto nj) {
             constexpr int RCAP = decltype(rcap)::value, NJ = decltype(nj)::value;
             rc = second ? tt_grad_launch_lpp<RCAP, NJ, true>(v, lds, blocks, d_pts, N, d_out, st)
@@ -43,16 +37,12 @@ static int tt_grad_launch(const TTBoxView &v, int second, const double *d_pts, l
         });
         return rc;
     }
-    if (!v.d_cores) return fail(PCX_ERR_UNSUPPORTED, "the handle holds neither a lane-per-point image nor plain cores");
-    TTGradGeneric gd{};
-    gd.g = tt_wave_model(v);
-    for (int k = 0; k < d; ++k) gd.col[k] = v.plan->dims.col[k];
-    for (int k = 1; k < d; ++k) gd.rsum += v.plan->ranks[k];
+    const TTGradGeneric gd = tt_grad_generic_model(v);
     const void *kernel = second ? (const void *)k_tt_grad_generic<true> : (const void *)k_tt_grad_generic<false>;
     size_t lds;
-    const int rc = tt_wave_lds(kernel, v, tt_grad_generic_doubles(gd), "gradient", "sum of ranks + 2 rank + 3 nodes", &lds);
-    if (rc) return rc;
-    const long blocks = std::min<long>((N + 3) / 4, 256L * 8);
+    if ((rc = tt_wave_lds(kernel, v, tt_grad_generic_doubles(gd.rsum, gd.g.rmax, gd.g.nmax), "gradient", "sum of ranks + 2 rank + 3 nodes", &lds)))
+        return rc;
+    const long blocks = tt_grad_generic_blocks(N);
     if (second) hipLaunchKernelGGL(k_tt_grad_generic<true>, dim3((unsigned)blocks), dim3(256), lds, st, gd, v.d_cores, d_pts, d_out, N);
     else hipLaunchKernelGGL(k_tt_grad_generic<false>, dim3((unsigned)blocks), dim3(256), lds, st, gd, v.d_cores, d_pts, d_out, N);
     HIP_TRY(hipGetLastError());

@@ -1,8 +1,6 @@
 // pcx_tt_hess.hip -- C ABI of libpcx_hip.so (see include/pcx.h): value, gradient and full Hessian of a tensor train
 // from one right sweep and one blocked left sweep per row, batched.  gfx950 only.
 
-#include <atomic>
-
 #include "pcx_internal.h"
 #include "tt_hess_kernels.h"
 
@@ -12,13 +10,8 @@ template <int RCAP, int NJ>
 static int tt_hess_launch_lpp(const TTBoxView &v, size_t lds, long blocks, int B, const double *d_pts, long N, double *d_out,
                               hipStream_t st) {
     const auto kernel = k_tt_hess_lpp<RCAP, NJ>;
-    // above the 64 KiB default: lifted once per instantiation and device, as tt_grad_launch_lpp does
     static std::atomic<unsigned long long> lifted{0};
-    const unsigned long long bit = v.device < 64 ? 1ull << v.device : 0;
-    if (lds > 64 * 1024 && !(lifted.load(std::memory_order_relaxed) & bit)) {
-        HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PCX_TT_HESS_LDS_MAX));
-        lifted.fetch_or(bit, std::memory_order_relaxed);
-    }
+    if (const int rc = tt_grad_lift_lds((const void *)kernel, lifted, v.device, lds)) return rc;
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(PCX_LPP_WG), lds, st, v.d_lpp_tab, v.plan->dims.d, v.plan->rmax, B,
                        v.d_lpp_img, d_pts, d_out, N);
     HIP_TRY(hipGetLastError());
@@ -29,36 +22,24 @@ static int tt_hess_launch_lpp(const TTBoxView &v, size_t lds, long blocks, int B
 // Caller holds the handle's mutex.
 static int tt_hess_launch(const TTBoxView &v, int B, const double *d_pts, long N, double *d_out, hipStream_t st) {
     if (N == 0) return PCX_OK;
-    const int d = v.plan->dims.d;
+    int rc;
     if (v.d_lpp_img) {
-        const long blocks = (N + PCX_LPP_WG - 1) / PCX_LPP_WG;
-        if (blocks > 0x7fffffffL) return fail(PCX_ERR_UNSUPPORTED, "batch too large for one launch");
+        long blocks;
+        if ((rc = tt_grad_lpp_blocks(N, &blocks))) return rc;
         const size_t lds = tt_hess_lds_bytes(*v.plan, true, B);
-        int rc = PCX_OK;
         tt_lpp_for_model(v.plan->lppCap, v.plan->lpp_nodes, [&](auto rcap, auto nj) {
             rc = tt_hess_launch_lpp<decltype(rcap)::value, decltype(nj)::value>(v, lds, blocks, B, d_pts, N, d_out, st);
         });
         return rc;
     }
-    TTHessGeneric hd{};
-    hd.gd.g = tt_wave_model(v);
-    for (int k = 0; k < d; ++k) hd.gd.col[k] = v.plan->dims.col[k];
-    for (int k = 1; k < d; ++k) hd.gd.rsum += v.plan->ranks[k];
-    hd.B = B;
+    const TTHessGeneric hd{tt_grad_generic_model(v), B};
     size_t lds;
-    const int rc = tt_wave_lds((const void *)k_tt_hess_generic, v, tt_hess_generic_doubles(hd.gd.rsum, v.plan->rmax, v.plan->nmax, B),
-                               "Hessian", "sum of ranks + 2 rank + 3 nodes + B (2 rank + 192)", &lds);
-    if (rc) return rc;
-    const long blocks = std::min<long>((N + 3) / 4, 256L * 8);
+    if ((rc = tt_wave_lds((const void *)k_tt_hess_generic, v, tt_hess_generic_doubles(hd.gd.rsum, v.plan->rmax, v.plan->nmax, B),
+                          "Hessian", "sum of ranks + 2 rank + 3 nodes + B (2 rank + 192)", &lds)))
+        return rc;
+    const long blocks = tt_grad_generic_blocks(N);
     hipLaunchKernelGGL(k_tt_hess_generic, dim3((unsigned)blocks), dim3(256), lds, st, hd, v.d_cores, d_pts, d_out, N);
     HIP_TRY(hipGetLastError());
-    return PCX_OK;
-}
-
-// the handle's form (true: lane-per-row), or an error for a handle that holds neither image nor cores
-static int tt_hess_form(const TTBoxView &v, bool *lane) {
-    *lane = v.d_lpp_img != nullptr;
-    if (!*lane && !v.d_cores) return fail(PCX_ERR_UNSUPPORTED, "the handle holds neither a lane-per-point image nor plain cores");
     return PCX_OK;
 }
 
@@ -73,11 +54,11 @@ static int tt_hess_args(pcx_tt *h, TTBoxView *v, const void *pts, int64_t N, int
     if (block < 0 || block > limit) return fail(PCX_ERR_INVALID, "block = %d is neither 0 nor in 1 .. %d", block, limit);
     if (N > 0 && (!pts || !out)) return fail(PCX_ERR_INVALID, "NULL buffer");
     bool lane;
-    if ((rc = tt_hess_form(*v, &lane))) return rc;
+    if ((rc = tt_grad_form(*v, &lane))) return rc;
     const int fits = tt_hess_block_max(*v->plan, lane);
     if (block > fits || fits == 0)
         return fail(PCX_ERR_UNSUPPORTED, "block = %d: the Hessian launch takes %zu bytes of LDS a workgroup, above %d (largest block that fits: %d)",
-                    block ? block : 1, tt_hess_lds_bytes(*v->plan, lane, block ? block : 1), PCX_TT_HESS_LDS_MAX, fits);
+                    block ? block : 1, tt_hess_lds_bytes(*v->plan, lane, block ? block : 1), PCX_TT_GRAD_LDS_MAX, fits);
     *B = block ? block : tt_hess_block_plan(*v->plan, lane);
     *go = N > 0;
     return PCX_OK;
@@ -90,7 +71,7 @@ extern "C" int pcx_tt_hess_info(pcx_tt *h, int32_t *info_out) {
     if (rc) return rc;
     if (!info_out) return fail(PCX_ERR_INVALID, "NULL info_out");
     bool lane;
-    if ((rc = tt_hess_form(v, &lane))) return rc;
+    if ((rc = tt_grad_form(v, &lane))) return rc;
     const int fits = tt_hess_block_max(*v.plan, lane);
     const int B = fits ? tt_hess_block_plan(*v.plan, lane) : 0;
     info_out[0] = lane ? 1 : 2;

@@ -25,7 +25,14 @@
 //
 // No atomics; every sum in a fixed order (b ascending, the two partial sums of tt_lpp_contract over a from RL = 4): a
 // row's bits depend on nothing but the row.
+//
+// k_tt_hess_lpp and k_tt_hess_generic (tt_hess_kernels.h) restate both sweeps with vectors carried beside L and must give
+// these kernels' bits: an edit to a sweep, a basis or a left body here has its twin there.  Restated, not shared: moved
+// into functions both pairs call, each changed the generated code of the kernels it touched.  What the
+// launchers of the two pairs share is at the end of this file.
 #pragma once
+
+#include <atomic>
 
 #include "tt_lpp_kernels.h"
 #include "tt_wave_kernels.h"
@@ -158,12 +165,14 @@ __device__ __forceinline__ void tt_grad_left_dim(int rl, pcx_lpp_cptr G, int rr,
     tt_lpp_for_rank<RCAP>(rl, [&](auto r) { tt_grad_left<decltype(r)::value, NJ, SECOND>(G, rr, q0, q1, q2, L, rnext, g, h); });
 }
 
-// columns (of 64 doubles) of dynamic LDS k_tt_grad_lpp takes: R_1 .. R_{d-1}, then L
-static inline size_t tt_grad_lpp_columns(const int *ranks, int d, int rmax) {
-    size_t cols = (size_t)rmax;
-    for (int k = 1; k < d; ++k) cols += (size_t)ranks[k];
-    return cols;
+// r_1 + ... + r_{d-1}: what R_1 .. R_{d-1} take, in columns (lane-per-row) or doubles (wave-per-row)
+static inline int tt_grad_rank_sum(const int *ranks, int d) {
+    int sum = 0;
+    for (int k = 1; k < d; ++k) sum += ranks[k];
+    return sum;
 }
+// columns (of 64 doubles) of dynamic LDS k_tt_grad_lpp takes: R_1 .. R_{d-1}, then L
+static inline size_t tt_grad_lpp_columns(const int *ranks, int d, int rmax) { return (size_t)tt_grad_rank_sum(ranks, d) + rmax; }
 
 // One wave per workgroup, one row per lane; dynamic LDS = (r_1 + ... + r_{d-1} + max rank) * 64 * 8 bytes: R_k in its
 // own lane-private columns at r_1 + ... + r_{k-1}, L in the last max-rank columns.  RCAP and NJ as k_tt_deriv_lpp.  The
@@ -229,8 +238,8 @@ k_tt_grad_lpp(const TTLppDim *__restrict__ tab, int d, const double *__restrict_
 
 // Every other model (rank > 16 or n > 16): one wave per row on the plain cores G_k[a][j][b].  Per wave in LDS:
 // R_1 .. R_{d-1} (r_1 + ... + r_{d-1} doubles), two rank vectors L alternates between, the three bases
-// (sum of ranks + 2 rmax + 3 nmax doubles; without SECOND the third basis is neither formed nor read).  Lane 0 forms
-// the bases; the lanes share the left rank on the right sweep
+// (tt_grad_generic_doubles: sum of ranks + 2 rmax + 3 nmax; without SECOND the third basis is neither formed nor read).
+// Lane 0 forms the bases; the lanes share the left rank on the right sweep
 // and the right rank b on the left sweep (tt_wave_left), where each lane adds its own b's terms of g and h in ascending
 // order and a butterfly over the wave adds the lanes: a fixed order.  col[k] = the user column of storage position k.
 struct TTGradGeneric {
@@ -239,8 +248,9 @@ struct TTGradGeneric {
     int rsum;                     // r_1 + ... + r_{d-1}
 };
 
-static inline size_t tt_grad_generic_doubles(const TTGradGeneric &gd) {
-    return (size_t)gd.rsum + 2 * (size_t)gd.g.rmax + 3 * (size_t)gd.g.nmax;
+// doubles of LDS per wave: the launcher's size and the kernel's slice stride
+__host__ __device__ static inline size_t tt_grad_generic_doubles(int rsum, int rmax, int nmax) {
+    return (size_t)rsum + 2 * rmax + 3 * nmax;
 }
 
 __device__ __forceinline__ double tt_grad_wave_sum(double x) {
@@ -260,7 +270,7 @@ k_tt_grad_generic(TTGradGeneric gd, const double *__restrict__ cores, const doub
     const int wave = threadIdx.x >> 6;
     const int d = gi.d;
     const long C = 1 + (SECOND ? 2 : 1) * d;
-    double *R = lds_gradg + (size_t)wave * ((size_t)gd.rsum + 2 * gi.rmax + 3 * gi.nmax);
+    double *R = lds_gradg + (size_t)wave * tt_grad_generic_doubles(gd.rsum, gi.rmax, gi.nmax);
     double *l0 = R + gd.rsum;
     double *q0 = l0 + 2 * gi.rmax;
     double *q1 = q0 + gi.nmax;
@@ -352,4 +362,38 @@ k_tt_grad_generic(TTGradGeneric gd, const double *__restrict__ cores, const doub
         }
         if (lane == 0) o[0] = lin[0];
     }
+}
+
+// ---- host side: what the launchers of pcx_tt_grad.hip and pcx_tt_hess.hip share -----------------------------------------
+#define PCX_TT_GRAD_LDS_MAX (160 * 1024)      // the LDS of a workgroup
+// the handle's form (true: lane-per-row), or an error for a handle that holds neither image nor cores
+static inline int tt_grad_form(const TTBoxView &v, bool *lane) {
+    *lane = v.d_lpp_img != nullptr;
+    if (!*lane && !v.d_cores) return fail(PCX_ERR_UNSUPPORTED, "the handle holds neither a lane-per-point image nor plain cores");
+    return PCX_OK;
+}
+// A lane-per-row launch above the 64 KiB default of dynamic LDS: lifted to a workgroup's 160 KiB once per instantiation and
+// device (`lifted`: the instantiation's own static; bit = device, an index past 63 lifts at every launch), so that it stays
+// off the launch path of a batch in pieces
+static inline int tt_grad_lift_lds(const void *kernel, std::atomic<unsigned long long> &lifted, int device, size_t lds) {
+    const unsigned long long bit = device < 64 ? 1ull << device : 0;
+    if (lds > 64 * 1024 && !(lifted.load(std::memory_order_relaxed) & bit)) {
+        HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PCX_TT_GRAD_LDS_MAX));
+        lifted.fetch_or(bit, std::memory_order_relaxed);
+    }
+    return PCX_OK;
+}
+// workgroups of a lane-per-row launch (64 rows each), refused beyond one launch's grid
+static inline int tt_grad_lpp_blocks(long N, long *blocks) {
+    *blocks = (N + PCX_LPP_WG - 1) / PCX_LPP_WG;
+    return *blocks > 0x7fffffffL ? fail(PCX_ERR_UNSUPPORTED, "batch too large for one launch") : PCX_OK;
+}
+// workgroups of a wave-per-row launch (four rows each; from 2048 on the waves stride over the rows)
+static inline long tt_grad_generic_blocks(long N) { return std::min<long>((N + 3) / 4, 256L * 8); }
+static inline TTGradGeneric tt_grad_generic_model(const TTBoxView &v) {
+    TTGradGeneric gd{};
+    gd.g = tt_wave_model(v);
+    for (int k = 0; k < gd.g.d; ++k) gd.col[k] = v.plan->dims.col[k];
+    gd.rsum = tt_grad_rank_sum(v.plan->ranks, gd.g.d);
+    return gd;
 }

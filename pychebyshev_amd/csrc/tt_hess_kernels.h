@@ -36,22 +36,19 @@ static inline size_t tt_hess_lpp_columns(const int *ranks, int d, int rmax, int 
 // wave-per-row: doubles per wave -- the gradient's (R, two L, three bases), and per carried vector two rank vectors, the
 // 64 lanes' two products of the current b and the 64 lanes' partial sums of H_ik.
 static inline size_t tt_hess_generic_doubles(int rsum, int rmax, int nmax, int B) {
-    return (size_t)rsum + 2 * (size_t)rmax + 3 * (size_t)nmax + (size_t)B * (2 * (size_t)rmax + 3 * 64);
+    return tt_grad_generic_doubles(rsum, rmax, nmax) + (size_t)B * (2 * (size_t)rmax + 3 * 64);
 }
-#define PCX_TT_HESS_LDS_MAX (160 * 1024)
 // dynamic LDS bytes of a workgroup at block size B (lane: one wave of 64 rows; else four waves of one row each)
 static inline size_t tt_hess_lds_bytes(const TTPlan &p, bool lane, int B) {
     const int d = p.dims.d;
     if (lane) return tt_hess_lpp_columns(p.ranks, d, p.rmax, B) * PCX_LPP_WG * sizeof(double);
-    int rsum = 0;
-    for (int k = 1; k < d; ++k) rsum += p.ranks[k];
-    return 4 * tt_hess_generic_doubles(rsum, p.rmax, p.nmax, B) * sizeof(double);
+    return 4 * tt_hess_generic_doubles(tt_grad_rank_sum(p.ranks, d), p.rmax, p.nmax, B) * sizeof(double);
 }
 static inline int tt_hess_block_limit(int d) { return d - 1 > 1 ? d - 1 : 1; }
 // the largest B <= max(1, d - 1) whose launch fits a workgroup's LDS; 0: not even B = 1 does
 static inline int tt_hess_block_max(const TTPlan &p, bool lane) {
     int B = tt_hess_block_limit(p.dims.d);
-    while (B > 0 && tt_hess_lds_bytes(p, lane, B) > PCX_TT_HESS_LDS_MAX) --B;
+    while (B > 0 && tt_hess_lds_bytes(p, lane, B) > PCX_TT_GRAD_LDS_MAX) --B;
     return B;
 }
 // Folds of one row at block size B, in units of one core folded with one basis: the right sweep (d - 1), pass 0 (three
@@ -66,7 +63,7 @@ static inline int tt_hess_fold_units(int d, int B) {
 // not as three (3 x 53.0 = 159 KiB, but 3 x 43 granules are 161.25 KiB).
 static inline int tt_hess_resident_waves(size_t bytes, bool lane) {
     const size_t alloc = (bytes + 1279) / 1280 * 1280;
-    return (int)(PCX_TT_HESS_LDS_MAX / alloc) * (lane ? 1 : 4);
+    return (int)(PCX_TT_GRAD_LDS_MAX / alloc) * (lane ? 1 : 4);
 }
 // The planner's B: passes against LDS residency.  A later pass repeats the L fold up to its first source and the two
 // folds from there; a larger B keeps fewer waves on a CU, and these kernels are bound by the latency a second wave hides,
@@ -275,6 +272,7 @@ k_tt_hess_generic(TTHessGeneric hd, const double *__restrict__ cores, const doub
     const int d = gi.d;
     const long C = 1 + (long)d + (long)d * d;
     const size_t vec = (size_t)gi.rmax;
+    // tt_hess_generic_doubles, restated: calling it here changed this kernel's code (tt_grad_kernels.h)
     double *R = lds_hessg + (size_t)wave * ((size_t)rsum + 2 * vec + 3 * gi.nmax + (size_t)B * (2 * vec + 3 * 64));
     double *l0 = R + rsum;
     double *q0 = l0 + 2 * vec;
