@@ -2,11 +2,13 @@
 // stand-alone program, for tests/test_bary_plan_host.py: built with the address and undefined-behaviour sanitizers on the
 // host side.  No HIP call is made: the program needs no GPU.  It is also how a plan is printed on any machine:
 //
-//   echo "5 11 11 11 11 11  1 1 1 1 1" | bary_plan_main [--tables] [--kfold=0]
+//   echo "5 11 11 11 11 11  1 1 1 1 1" | bary_plan_main [--tables] [--kfold=0] [--kfold-eff=PERCENT] [--kfold-straddle=0]
 //
 // Input (a file named on the command line, else stdin), one case per line:
 //   d n_0 .. n_{d-1}  seed tail sq grid grid_prod        (the switches as PCX_BARY_SEED, _TAIL, _SQ, _GRID, _GRID_PROD set them)
 // --kfold=0 plans every case of the run as PCX_BARY_KFOLD=0 does (no k-fold form); without it the default, 1.
+// --kfold-eff=PERCENT and --kfold-straddle=0 do the same for PCX_BARY_KFOLD_EFF and PCX_BARY_KFOLD_STRADDLE
+// (BaryEnv::kfold_eff, ::kfold_straddle); without them the defaults, 0 and 1.
 // The nodes are Chebyshev points of the first kind on [-1, 1].  Output, one JSON object per case: "rc" and "error" of
 // bary_make_plan; every field of BaryLaunchPlan ("plan"); what the info entry points report of it ("kernel_info",
 // "grid_info", "tail_info" = entries 1 .. 3, "set_kernel" = variants 2 .. 5), computed by the functions those entry points
@@ -27,6 +29,8 @@ PCX_HIDDEN char *pcx_err_buf() noexcept {         // the library keeps it in pcx
 
 static bool g_dump = false;
 static bool g_kfold = true;
+static bool g_kfold_straddle = true;
+static int g_kfold_eff = 0;
 
 template <typename T>
 static void put_table(const char *name, const std::vector<T> &v, bool &first) {
@@ -81,6 +85,8 @@ int main(int argc, char **argv) {
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--tables")) g_dump = true;
         else if (!strncmp(argv[i], "--kfold=", 8)) g_kfold = argv[i][8] != '0';
+        else if (!strncmp(argv[i], "--kfold-eff=", 12)) g_kfold_eff = atoi(argv[i] + 12);
+        else if (!strncmp(argv[i], "--kfold-straddle=", 17)) g_kfold_straddle = argv[i][17] != '0';
         else if (!(in = fopen(argv[i], "r"))) { fprintf(stderr, "bary_plan_main: cannot open %s\n", argv[i]); return 2; }
     }
     const double pi = 3.14159265358979323846;
@@ -105,7 +111,7 @@ int main(int argc, char **argv) {
             if (fscanf(in, "%d", &v) != 1) { fprintf(stderr, "bary_plan_main: five switches per case\n"); return 2; }
         BaryEnv env;
         env.seed = sw[0] != 0; env.tail_mode = sw[1]; env.sq_auto = sw[2] != 0; env.grid = sw[3]; env.grid_prod = sw[4] != 0;
-        env.kfold = g_kfold;
+        env.kfold = g_kfold; env.kfold_eff = g_kfold_eff; env.kfold_straddle = g_kfold_straddle;
         std::vector<double> nodes((size_t)sum_n);            // exactly sum_n doubles: a read past them is the sanitizer's
         for (int k = 0; k < d; ++k)
             for (int j = 0; j < dm.n[k]; ++j) nodes[dm.off[k] + j] = -std::cos((2 * j + 1) * pi / (2.0 * dm.n[k]));
