@@ -710,6 +710,50 @@ int pcx_tt_als_qr(int device, const double *A, int64_t m, int c, double *Q, doub
  * (1 <= G <= PCX_TT_ALS_MAX_GRID), the convergence sums of one outer iteration.  The squares are not scaled.        */
 int pcx_tt_als_norms(int device, const double *tnew, const double *tprev, const double *target, int64_t G, double *out4);
 
+/* Least-squares fitting of a tensor train to scattered samples (ChebyshevTT.fit_samples / from_samples; extension: the
+ * reference has no builder for data off the grid).  A fit session holds N samples on the device for the whole of one
+ * fit: points N x d row-major in STORAGE order (column k belongs to storage position k: the caller permutes) and N
+ * values.  pcx_tt_fit_create copies host arrays; pcx_tt_fit_create_dev adopts device pointers without a copy (they must
+ * outlive the session).  lo / hi = the domain by storage position, d each, lo < hi.  Checked at creation, each
+ * PCX_ERR_INVALID: d in [1, PCX_MAX_DIMS], N >= 1, NULL, a value or coordinate that is not finite, a coordinate outside
+ * its dimension's domain (host arrays: a loop on the host before any launch; device arrays: one small kernel).  More
+ * than PCX_TT_FIT_MAX_SAMPLES samples are PCX_ERR_UNSUPPORTED.
+ *
+ * pcx_tt_fit_normal: the normal equations of position k (0 <= k < d) for the given COEFFICIENT cores (pcx_tt_create's
+ * layout, ranks[0] = ranks[d] = 1).  With the design row of sample i
+ *     a_i = L_i (x) T(t_k(x_ik)) (x) R_i          C order (a, j, b), the core's own layout, P = r_k n_k r_{k+1} entries,
+ * L_i / R_i the left / right partial products of the chain at x_i and T the n_k Chebyshev polynomials at
+ * t = 2 (x - lo) / (hi - lo) - 1 (-1 and +1 exactly at the domain's ends), G_out (host, P x P, both triangles, exactly symmetric) = sum_i a_i a_i^T and b_out
+ * (host, P) = sum_i y_i a_i.  Two kernels: one wave per sample forms (L_i, T, R_i), r_k + n_k + r_{k+1} numbers a sample;
+ * the Gram kernel forms the P-wide rows in registers from them (the N x P matrix never exists in memory) and adds the
+ * products over fixed chunks of samples, v_mfma_f64_16x16x4_f64 with the samples as K from P = 16 on, one output per
+ * lane on the VALU below; a third kernel adds the chunks' partial sums in ascending order.  No atomics: equal input
+ * gives equal bits.  pcx_tt_fit_set_form forces the Gram kernel: 0 the rule above, 1 VALU, 2 MFMA, each at any P
+ * (anything else: PCX_ERR_INVALID).  The device outputs start as a NaN pattern followed by 256 doubles of it: an
+ * element no kernel wrote comes back NaN, a disturbed tail is PCX_ERR_INTERNAL.
+ * Limits, each PCX_ERR_UNSUPPORTED before anything runs: ranks or node counts above 256, P > PCX_TT_FIT_MAX_P.
+ *
+ * pcx_tt_fit_residual: sumsq_out[0] = sum_i (TT(x_i) - y_i)^2, sumsq_out[1] = sum_i y_i^2 for the given cores: the
+ * evaluation kernels of pcx_tt_eval_batch_dev on the resident points, then a fixed-grid, fixed-tree reduction.  The
+ * squares are not scaled.
+ *
+ * pcx_tt_fit_times: ms_out[0 .. 2] = the device time in milliseconds of the three kernels of the session's last
+ * pcx_tt_fit_normal (interface vectors, Gram, reduction), from events recorded around each; zeros before the first.  */
+#define PCX_TT_FIT_MAX_P 4096
+#define PCX_TT_FIT_MAX_SAMPLES (1LL << 28)
+typedef struct pcx_tt_fit pcx_tt_fit;
+int pcx_tt_fit_create(int device, int d, const double *lo, const double *hi, const double *pts, const double *values,
+                      int64_t N, pcx_tt_fit **out);
+int pcx_tt_fit_create_dev(int device, int d, const double *lo, const double *hi, const double *d_pts,
+                          const double *d_values, int64_t N, pcx_tt_fit **out);
+int pcx_tt_fit_destroy(pcx_tt_fit *s);
+int pcx_tt_fit_set_form(pcx_tt_fit *s, int form);
+int pcx_tt_fit_normal(pcx_tt_fit *s, int d, const int32_t *n_nodes, const int32_t *ranks, const double *coeff_cores,
+                      int k, double *G_out, double *b_out);
+int pcx_tt_fit_residual(pcx_tt_fit *s, int d, const int32_t *n_nodes, const int32_t *ranks, const double *coeff_cores,
+                        double *sumsq_out);
+int pcx_tt_fit_times(pcx_tt_fit *s, float *ms_out);
+
 /* A sequence of adjacent swaps of storage axes (reference _algebra.py::_tt_swap_adjacent, driven by
  * ChebyshevTT.reorder): swap s exchanges axes swaps[s] and swaps[s] + 1 by one truncated SVD of the
  * merged pair (same rank rule).  Same input layout and limits as pcx_tt_round; a merged pair of more

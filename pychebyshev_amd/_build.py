@@ -48,6 +48,7 @@ SOURCES = {
     "pcx_tt_ladder.hip": TT_H + ["tt_lpp_kernels.h", "tt_wave_kernels.h", "tt_ladder_kernels.h"],
     "pcx_ttbuild.hip": HOST_H + ["ttcross_kernels.h", "ttsvd_kernels.h", "tt_round_kernels.h"],
     "pcx_tt_als.hip": HOST_H + ["tt_als_kernels.h"],
+    "pcx_tt_fit.hip": TT_H + ["tt_als_kernels.h", "tt_wave_kernels.h", "tt_fit_kernels.h"],
     "pcx_calculus.hip": BARY_H + ["pcx_slider_internal.h", "pcx_spline_internal.h", "gather_kernels.h",
                          "calculus_kernels.h", "slider_calc_kernels.h", "spline_calc_kernels.h", "invert_kernels.h"],
     "pcx_comm.hip": [PCX_H],

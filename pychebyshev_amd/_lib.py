@@ -166,6 +166,13 @@ SIGNATURES = {
     "pcx_tt_als_project": (_I, [_I, _I, _I, c_f64p, c_f64p, c_f64p, _I, _I, _L, c_i32p]),
     "pcx_tt_als_qr": (_I, [_I, c_f64p, _L, _I, c_f64p, c_f64p]),
     "pcx_tt_als_norms": (_I, [_I, c_f64p, c_f64p, c_f64p, _L, c_f64p]),
+    "pcx_tt_fit_create": (_I, [_I, _I, c_f64p, c_f64p, c_f64p, c_f64p, _L, c_vpp]),
+    "pcx_tt_fit_create_dev": (_I, [_I, _I, c_f64p, c_f64p, _V, _V, _L, c_vpp]),
+    "pcx_tt_fit_destroy": (_I, [_V]),
+    "pcx_tt_fit_set_form": (_I, [_V, _I]),
+    "pcx_tt_fit_normal": (_I, [_V, _I, c_i32p, c_i32p, c_f64p, _I, c_f64p, c_f64p]),
+    "pcx_tt_fit_residual": (_I, [_V, _I, c_i32p, c_i32p, c_f64p, c_f64p]),
+    "pcx_tt_fit_times": (_I, [_V, ctypes.POINTER(ctypes.c_float)]),
     "pcx_comm_unique_id": (_I, [_V]),
     "pcx_comm_create": (_I, [_I, _I, _I, _V, c_vpp]),
     "pcx_comm_destroy": (_I, [_V]),

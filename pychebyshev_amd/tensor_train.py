@@ -43,6 +43,14 @@ device call (``pcx_tt_als``, ``csrc/tt_als_kernels.h``): with the neighbouring c
 the projection ``C_k = L^T T R^T``, two chains of tall-skinny contractions over the target tensor, in place of the
 reference's dense ``lstsq``.  Its ``values=`` keyword passes the target as a tensor instead of through the callback.
 
+``fit_samples`` / ``from_samples`` fit the cores to samples at ARBITRARY points (extension: every other builder needs the
+function on the Chebyshev grid): alternating least squares over the coefficient cores, one position at a time.  The
+samples live on the device for the whole fit (a ``pcx_tt_fit`` session); per position the device accumulates the normal
+equations ``G = A^T A``, ``b = A^T y`` of the design matrix ``a_i = L_i (x) T (x) R_i`` without ever forming it
+(``pcx_tt_fit_normal``, ``csrc/tt_fit_kernels.h``: the N P^2 work of a step), and per outer iteration the residual on the
+samples (``pcx_tt_fit_residual``: the evaluation kernels on the resident points); the P x P solve and the QR steps that
+move the orthogonality centre are host NumPy on core-sized arrays.
+
 Out of scope in this tier: the ``method='als'`` builder (raises ``NotImplementedError``) and ``with_auto_order``.
 """
 from __future__ import annotations
@@ -510,6 +518,119 @@ def _tt_cross(func, grids, max_rank, tol, max_sweeps, verbose, seed=None):
 # --------------------------------------------------------------------------------------
 # ChebyshevTT
 # --------------------------------------------------------------------------------------
+
+# --------------------------------------------------------------------------------------
+# fitting to scattered samples: the host side of ChebyshevTT.fit_samples
+# --------------------------------------------------------------------------------------
+
+def _checked_sample_points(points, d: int) -> np.ndarray:
+    arr = np.asarray(points)
+    if arr.dtype.kind not in "fiu":
+        raise TypeError(f"points must be real numbers, got dtype {arr.dtype}")
+    if arr.ndim != 2 or arr.shape[1] != d:
+        raise ValueError(f"points must have shape (N, {d}), got {arr.shape}")
+    return _lib.f64(arr)
+
+
+def _checked_sample_values(values) -> np.ndarray:
+    arr = np.asarray(values)
+    if arr.dtype.kind not in "fiu":
+        raise TypeError(f"values must be real numbers, got dtype {arr.dtype}")
+    if arr.ndim != 1:
+        raise ValueError(f"values must have shape (N,), got {arr.shape}")
+    return _lib.f64(arr)
+
+
+def _fit_start_ranks(n: Sequence[int], rank: int) -> List[int]:
+    """The bonds of ``from_samples``' start: ``_CrossBuilder``'s caps, ``min(rank, prod(n[:k]), prod(n[k:]))``."""
+    d = len(n)
+    return [1] + [min(rank, int(np.prod(n[:k], dtype=np.int64)), int(np.prod(n[k:], dtype=np.int64)))
+                  for k in range(1, d)] + [1]
+
+
+def _fit_move_centre(cores: List[np.ndarray], k: int, to: int) -> None:
+    """Move the orthogonality centre from core ``k`` to its neighbour ``to`` in place: a reduced QR of core ``k``'s
+    unfolding, the triangular factor absorbed into the neighbour; the tensor is unchanged, the bond becomes
+    ``min(rows, columns)`` of the unfolding."""
+    rl, n, rr = cores[k].shape
+    if to == k + 1:
+        Q, R = np.linalg.qr(cores[k].reshape(rl * n, rr))
+        cores[k] = Q.reshape(rl, n, Q.shape[1])
+        nxt = cores[k + 1]
+        cores[k + 1] = (R @ nxt.reshape(rr, -1)).reshape(R.shape[0], nxt.shape[1], nxt.shape[2])
+    elif to == k - 1:
+        Q, R = np.linalg.qr(cores[k].reshape(rl, n * rr).T)
+        cores[k] = np.ascontiguousarray(Q.T).reshape(Q.shape[1], n, rr)
+        prv = cores[k - 1]
+        cores[k - 1] = (prv.reshape(-1, rl) @ R.T).reshape(prv.shape[0], prv.shape[1], R.shape[0])
+    else:
+        raise ValueError(f"the centre moves to a neighbour, not from {k} to {to}")
+
+
+class _FitSession:
+    """Owner of one ``pcx_tt_fit`` session: the samples of one ``fit_samples`` call, resident on the device."""
+
+    def __init__(self, tt: "ChebyshevTT", pts, vals, N: int, device: int | None = None):
+        from .device import DeviceArray
+        lib = _lib.load()
+        d = tt.num_dimensions
+        lo = _lib.f64([float(b[0]) for b in tt.domain])
+        hi = _lib.f64([float(b[1]) for b in tt.domain])
+        handle = ctypes.c_void_p()
+        self.handle, self._keep = None, None
+        if isinstance(pts, DeviceArray):
+            dev = pts.device
+            self._keep = (pts, vals)            # adopted, not copied: alive as long as the session
+            rc = lib.pcx_tt_fit_create_dev(dev, d, _lib.p_f64(lo), _lib.p_f64(hi), ctypes.c_void_p(pts.ptr),
+                                           ctypes.c_void_p(vals.ptr), N, ctypes.byref(handle))
+        else:
+            dev = device if device is not None else (_lib.default_device() if tt._device_index is None else tt._device_index)
+            rc = lib.pcx_tt_fit_create(int(dev), d, _lib.p_f64(lo), _lib.p_f64(hi), _lib.p_f64(pts), _lib.p_f64(vals), N,
+                                       ctypes.byref(handle))
+        _lib.check(rc, lib)
+        self.lib, self.handle, self.device, self.d = lib, handle, int(dev), d
+
+    def set_form(self, form: int) -> None:
+        _lib.check(self.lib.pcx_tt_fit_set_form(self.handle, int(form)), self.lib)
+
+    def normal(self, cores, k: int):
+        """``(G, b)`` of position ``k`` for ``cores``."""
+        from . import _algebra
+        n, ranks, cat = _algebra._shape_args(cores)
+        P = cores[k].size
+        G, b = np.empty((P, P)), np.empty(P)
+        _lib.check(self.lib.pcx_tt_fit_normal(self.handle, self.d, _lib.p_i32(n), _lib.p_i32(ranks), _lib.p_f64(cat), int(k),
+                                              _lib.p_f64(G), _lib.p_f64(b)), self.lib)
+        return G, b
+
+    def sumsq(self, cores) -> np.ndarray:
+        """``[sum (TT(x_i) - y_i)^2, sum y_i^2]`` for ``cores``."""
+        from . import _algebra
+        n, ranks, cat = _algebra._shape_args(cores)
+        out = np.empty(2)
+        _lib.check(self.lib.pcx_tt_fit_residual(self.handle, self.d, _lib.p_i32(n), _lib.p_i32(ranks), _lib.p_f64(cat),
+                                                _lib.p_f64(out)), self.lib)
+        return out
+
+    def residual(self, cores) -> float:
+        """``||TT(x) - y|| / ||y||``; 0 for an exact fit of all-zero values, inf for any other fit of them."""
+        s = self.sumsq(cores)
+        if s[1] > 0.0:
+            return float(np.sqrt(s[0]) / np.sqrt(s[1]))
+        return float("inf") if s[0] > 0.0 else 0.0
+
+    def close(self) -> None:
+        if self.handle:
+            self.lib.pcx_tt_fit_destroy(self.handle)
+            self.handle = None
+        self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 class _DeviceTT:
     """Owner of one ``pcx_tt`` handle (freed on garbage collection)."""
@@ -1402,6 +1523,164 @@ class ChebyshevTT(ErgonomicsMixin, FibreCalculusMixin):
             for i, x in enumerate(rel):
                 print(f"  ALS iter {i + 1}: rel_change = {x:.3e}")
         self.completion_info = {"iterations": int(iters.value), "rel_change": rel, "grid_residual": float(resid.value)}
+
+    # ---------------------------------------------------------------- fitting to scattered samples
+    fit_info = None             # set by fit_samples: {"iterations", "residual", "n_samples"}
+
+    def _check_samples(self, points, values, ridge):
+        """The argument checks of ``fit_samples``, before the library is loaded for host arrays: ``(points in STORAGE
+        column order, values, N)``, both NumPy arrays or both device arrays."""
+        from .device import is_device_array
+        d = self.num_dimensions
+        ridge = float(ridge)
+        if not (ridge >= 0.0) or not np.isfinite(ridge):
+            raise ValueError(f"ridge must be finite and >= 0, got {ridge!r}")
+        identity = self._dim_order == list(range(d))
+        if is_device_array(points) or is_device_array(values):
+            from .device import DeviceArray, as_device_array
+            dp = as_device_array(points) if is_device_array(points) else DeviceArray.from_host(_checked_sample_points(points, d))
+            dv = as_device_array(values) if is_device_array(values) else DeviceArray.from_host(_checked_sample_values(values))
+            if dp.ndim != 2 or dp.shape[1] != d:
+                raise ValueError(f"points must have shape (N, {d}), got {dp.shape}")
+            if dv.ndim != 1 or dv.shape[0] != dp.shape[0]:
+                raise ValueError(f"values must have shape ({dp.shape[0]},), got {dv.shape}")
+            if dp.shape[0] < 1:
+                raise ValueError("at least one sample is needed")
+            if dp.device != dv.device:
+                raise ValueError(f"points live on device {dp.device} but values on device {dv.device}")
+            if not identity:       # the session takes storage-order columns: a permuted model stages the points through the host
+                dp = DeviceArray.from_host(dp.to_host()[:, self._dim_order], dp.device)
+            return dp, dv, dp.shape[0]
+        pts = _checked_sample_points(points, d)
+        vals = _checked_sample_values(values)
+        if vals.shape[0] != pts.shape[0]:
+            raise ValueError(f"values must have shape ({pts.shape[0]},), got {vals.shape}")
+        if pts.shape[0] < 1:
+            raise ValueError("at least one sample is needed")
+        if not np.isfinite(vals).all():
+            raise ValueError("values contain NaN or Inf — every sample must be finite")
+        if not np.isfinite(pts).all():
+            raise ValueError("points contain NaN or Inf — every sample must be finite")
+        user_domain = self._user_frame_domain()
+        for u, (a, b) in enumerate(user_domain):
+            col = pts[:, u]
+            if col.min() < a or col.max() > b:
+                raise ValueError(f"points[:, {u}] leaves the domain [{a}, {b}] of dimension {u}: a Chebyshev basis "
+                                 "extrapolates explosively, drop or clip those samples")
+        if not identity:
+            pts = np.ascontiguousarray(pts[:, self._dim_order])
+        return pts, vals, pts.shape[0]
+
+    def fit_samples(self, points, values, *, max_iter: int = 20, tolerance: float = 1e-10, ridge: float = 1e-12,
+                    verbose: bool = False) -> None:
+        """Least-squares fit of the TT, at its current ranks and in place, to samples at arbitrary points (extension):
+        minimises ``sum_i (TT(x_i) - y_i)^2`` by alternating least squares over the coefficient cores.
+
+        ``points`` is ``(N, d)`` in the user's dimension order and ``values`` ``(N,)``; NumPy arrays, or device arrays
+        (:class:`~pychebyshev_amd.device.DeviceArray` or anything with ``__cuda_array_interface__``), which the fit
+        reads where they are.  Every coordinate must be finite and inside its dimension's domain and every value finite.
+
+        The algorithm: (1) cores ``d-1 .. 1`` are right-orthogonalised (QR of the unfoldings); (2) one outer iteration
+        visits the positions ``0, 1, .., d-1, d-2, .., 1``; (3) at position ``k`` the design row of sample ``i`` is
+        ``a_i = L_i (x) T(t_k(x_ik)) (x) R_i`` in the core's own C order, ``L_i`` / ``R_i`` the partial products of the
+        chain on either side; (4) ``G = A^T A``, ``b = A^T y`` are accumulated on the device (``pcx_tt_fit_normal``,
+        ``csrc/tt_fit_kernels.h``: the ``N x P`` matrix is never formed in memory) and ``lam = ridge trace(G) / P``;
+        (5) ``(G + lam I) c = b`` is solved on the host (a Cholesky factorisation tests that it is positive definite) and
+        becomes core ``k``; (6) the orthogonality
+        centre moves one step towards the next position (a QR of the core's unfolding, the factor absorbed into the
+        neighbour; a bond shrinks where the unfolding cannot hold it); (7) after each outer iteration ``res =
+        ||TT(x) - y|| / ||y||`` on the samples (``pcx_tt_fit_residual``) and the loop stops when ``|res_prev - res| <=
+        tolerance res_prev``, when ``res == 0`` or after ``max_iter`` iterations (``max_iter <= 0``: none).
+
+        ``self.fit_info`` records ``iterations``, the ``residual`` history and ``n_samples``.  With ``ridge == 0``
+        ``N`` must be at least the largest number of unknowns of a position.  A system that is not positive definite
+        raises ``ValueError`` naming the position.  The samples are uploaded (or adopted) once per call."""
+        self._check_built()
+        pts, vals, N = self._check_samples(points, values, ridge)
+        ridge, tolerance, max_iter = float(ridge), float(tolerance), int(max_iter)
+        if tolerance != tolerance:
+            raise ValueError("tolerance is NaN")
+        d = self.num_dimensions
+        cores = [np.array(c, dtype=np.float64) for c in self._coeff_cores]
+        sizes = [c.size for c in cores]
+        if ridge == 0.0 and N < max(sizes):
+            k = int(np.argmax(sizes))
+            raise ValueError(f"{N} samples cannot determine the {sizes[k]} unknowns of position {k} "
+                             f"(core shape {cores[k].shape}) with ridge = 0: pass more samples, lower the rank or set ridge > 0")
+        history: List[float] = []
+        if max_iter > 0:
+            session = _FitSession(self, pts, vals, N)
+            try:
+                for k in range(d - 1, 0, -1):
+                    _fit_move_centre(cores, k, k - 1)
+                order = list(range(d)) + list(range(d - 2, 0, -1))
+                for it in range(max_iter):
+                    for i, k in enumerate(order):
+                        G, b = session.normal(cores, k)
+                        P = b.size
+                        lam = ridge * float(np.trace(G)) / P
+                        if lam:
+                            G[np.diag_indices(P)] += lam
+                        try:
+                            chol = np.linalg.cholesky(G)
+                        except np.linalg.LinAlgError:
+                            raise ValueError(f"the normal equations of position {k} ({P} unknowns, {N} samples) are not "
+                                             f"positive definite: the samples do not determine this core; raise ridge "
+                                             f"(now {ridge:g}), lower the rank or pass more samples") from None
+                        del chol                                   # the factorisation is the definiteness test; LAPACK's
+                        c = np.linalg.solve(G, b)                  # solver (NumPy has no triangular one) gives the solution
+                        cores[k] = c.reshape(cores[k].shape)
+                        nxt = order[(i + 1) % len(order)]
+                        if nxt != k:
+                            _fit_move_centre(cores, k, nxt)
+                    res = session.residual(cores)
+                    history.append(res)
+                    if verbose:
+                        print(f"  fit_samples iter {it + 1}: residual = {res:.6e}")
+                    if res == 0.0 or (it > 0 and abs(history[-2] - res) <= tolerance * history[-2]):
+                        break
+            finally:
+                session.close()
+            self._set_cores(cores)
+        self.fit_info = {"iterations": len(history), "residual": history, "n_samples": int(N)}
+
+    @classmethod
+    def from_samples(cls, points, values, num_dimensions: int, domain, n_nodes, *, rank: int, seed=None,
+                     max_iter: int = 20, tolerance: float = 1e-10, ridge: float = 1e-12, max_derivative_order: int = 2,
+                     descriptor: str = "") -> "ChebyshevTT":
+        """A TT of fixed ``rank`` fitted to samples ``(points (N, d), values (N,))`` at arbitrary points of ``domain``
+        (extension).  The start is random: ``np.random.default_rng(seed).standard_normal((r_l, n_k, r_r))`` core by core
+        from ``k = 0``, every interior bond ``min(rank, prod(n[:k]), prod(n[k:]))``; then :meth:`fit_samples`.  The result
+        has ``function = None``, ``method = "samples"`` and the identity ``dim_order``."""
+        from . import Domain, Ns
+        if isinstance(domain, Domain):
+            domain = list(domain.bounds)
+        if isinstance(n_nodes, Ns):
+            n_nodes = list(n_nodes.counts)
+        d = int(num_dimensions)
+        if int(rank) != rank or int(rank) < 1:
+            raise ValueError(f"rank must be a positive integer, got {rank!r}")
+        n = [int(v) for v in n_nodes]
+        if len(domain) != d or len(n) != d:
+            raise ValueError(f"domain and n_nodes must have {d} entries, got {len(domain)} and {len(n)}")
+        if min(n) < 1:
+            raise ValueError(f"every dimension needs at least one node, got {n}")
+        for k, (a, b) in enumerate(domain):
+            if not (np.isfinite(a) and np.isfinite(b) and a < b):
+                raise ValueError(f"domain of dimension {k} must be finite with lo < hi, got {(a, b)}")
+        bonds = _fit_start_ranks(n, int(rank))
+        obj = cls(None, d, [list(b) for b in domain], n, max_rank=int(rank), tolerance=float(tolerance),
+                  max_derivative_order=max_derivative_order)
+        obj.descriptor = descriptor
+        obj.method = "samples"
+        rng = np.random.default_rng(seed)
+        obj._coeff_cores = [rng.standard_normal((bonds[k], n[k], bonds[k + 1])) for k in range(d)]
+        obj._tt_ranks = list(bonds)
+        obj._built = True
+        start = time.time()
+        obj.fit_samples(points, values, max_iter=max_iter, tolerance=tolerance, ridge=ridge)
+        obj._build_time = time.time() - start
+        return obj
 
     # ---------------------------------------------------------------- algebra
     # Reference tensor_train.py:3287-3458 and :2575-2676.  Scalars scale core 0 on the host; a sum stacks the cores
